@@ -18,6 +18,16 @@ does on top of that -- host-resident data handed over per minibatch through the 
 first time an angle is met -- is timed separately, on reconstruct_ptychography itself, in the `driver` keys (mean per
 minibatch over 16 first-touch angles; 1.04x the engine loop).  With N ranks the global batch is N x 32 positions (the
 reference's `mpirun -n N` semantics): weak scaling.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (`value`, `ms_per_step`, the roofline of
+the timed launches).  Everything else -- the CPU baselines, the fused full-chip legs (per angle, virtual ranks, kernel
+sweep), the driver legs and, with N > 1 ranks, the second exchange and the peer-to-peer transport legs -- runs only with
+--full; the --no-* and --legs options select among them there.
+
+--dump-outputs DIR writes what the last timed step computed, as rank 0 holds it after the timed loop (before any --full
+leg): DIR/loss.npy (float64, shape (1,): the minibatch loss of that step) and DIR/object_sample.npy (float32: every
+OBJECT_SAMPLE_STRIDE-th value of the updated [Y, X, Z, 2] object, flattened in C order -- 4.8 M values, 19 MB).  Inputs
+are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -32,6 +42,14 @@ sys.path.insert(0, ROOT)
 
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 EXIT_LEG_ABANDONED = 5      # a secondary leg of an N > 1 run hung: the headline line was printed, with `legs_abandoned`
+OBJECT_SAMPLE_STRIDE = 7    # --dump-outputs: odd, so that delta and beta are both sampled
+
+
+def dump_outputs(d, loss, obj_flat):
+    """--dump-outputs: the last timed step's loss and a fixed sample of the object it updated."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'loss.npy'), np.array([loss], dtype=np.float64))
+    np.save(os.path.join(d, 'object_sample.npy'), np.ascontiguousarray(obj_flat[::OBJECT_SAMPLE_STRIDE], dtype=np.float32))
 
 
 def algorithmic_bytes_fwd_grad(B, Py, Px, S, V):
@@ -355,11 +373,16 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--minibatch', type=int, default=32)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-per-angle', action='store_true', help="skip the secondary full-chip legs (per angle, virtual ranks, sweep)")
-    ap.add_argument('--no-driver', action='store_true', help='skip timing reconstruct_ptychography itself')
-    ap.add_argument('--no-driver-epoch', action='store_true', help='skip the whole-epoch (500 angles) run of reconstruct_ptychography (~25 s)')
-    ap.add_argument('--legs', default='per_angle,vr8,vr16,sweep', help='which secondary full-chip legs to run (profiling aid)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the secondary measurements: CPU baselines, full-chip legs, driver legs and, '
+                         'with N > 1 ranks, the other-exchange and peer-to-peer legs (the --no-* and --legs options select among them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's loss and a fixed sample of the updated object to DIR/*.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baselines')
+    ap.add_argument('--no-per-angle', action='store_true', help="--full: skip the secondary full-chip legs (per angle, virtual ranks, sweep)")
+    ap.add_argument('--no-driver', action='store_true', help='--full: skip timing reconstruct_ptychography itself')
+    ap.add_argument('--no-driver-epoch', action='store_true', help='--full: skip the whole-epoch (500 angles) run of reconstruct_ptychography (~25 s)')
+    ap.add_argument('--legs', default='per_angle,vr8,vr16,sweep', help='--full: which secondary full-chip legs to run (profiling aid)')
     ap.add_argument('--force-dist', action='store_true', help='use the multi-GPU (RCCL) code path even with one rank')
     ap.add_argument('--comm', choices=('rccl', 'p2p', 'host'), default=os.environ.get('ADM_COMM', 'rccl'),
                     help="rccl (default): RCCL reduce-scatter / all-gather behind libadm's C ABI; p2p: direct all-pairs exchange through "
@@ -376,7 +399,7 @@ def main():
                          'faster (an experiment: ask for it explicitly)')
     ap.add_argument('--leg-timeout', type=int, default=int(os.environ.get('ADM_BENCH_LEG_TIMEOUT', '240')),
                     help='N > 1: seconds a secondary leg may take before it is abandoned and the line is printed without it (0 = no watchdog)')
-    ap.add_argument('--no-p2p-leg', action='store_true', help='N > 1: skip the extra leg that repeats the headline loop through the peer-to-peer transport')
+    ap.add_argument('--no-p2p-leg', action='store_true', help='N > 1, --full: skip the extra leg that repeats the headline loop through the peer-to-peer transport')
     ap.add_argument('--test-hang-leg', action='store_true', help=argparse.SUPPRESS)     # tests/: the last secondary leg never returns
     ap.add_argument('--test-crash-leg', action='store_true', help=argparse.SUPPRESS)    # tests/: rank 0 abort()s inside the last secondary leg
     ap.add_argument('--restricted-exchange', action='store_true',
@@ -636,6 +659,9 @@ def main():
 
     dt, kern_ms, phases = timed_loop()
     loss_headline = loss_box[0]
+    if args.dump_outputs and rank == 0:
+        ctx.sync()
+        dump_outputs(args.dump_outputs, loss_headline, state.obj.view(0, (state.n,)).get())
 
     restricted = leg['restricted']
 
@@ -724,7 +750,7 @@ def main():
     # secondary leg on EVERY rank count: update_scheme='per angle' -- all minibatches of an angle fused, ONE exchange per step.
     # (N > 1: the same two collectives on the same communicator as the headline loop that has just run.)
     per_angle = None
-    if not args.no_per_angle and 'per_angle' in args.legs.split(',') and args.scaling == 'weak':
+    if args.full and not args.no_per_angle and 'per_angle' in args.legs.split(',') and args.scaling == 'weak':
         k_angle = -(-n_pos // (B * world))
         with Watchdog('per_angle'):
             per_angle = fused_batch_measure(ctx, eng, state, probe, tables, cfg, targets, check, k_angle, {'update_scheme': 'per angle'},
@@ -734,7 +760,7 @@ def main():
 
     # last leg with several ranks: the headline loop again with the footprint-restricted exchange (or, if that was asked for as
     # the headline, with the full exchange), from the same initial state
-    if use_dist and world > 1 and args.scaling == 'weak':
+    if args.full and use_dist and world > 1 and args.scaling == 'weak':
         with Watchdog('immediate_restricted' if not leg['restricted'] else 'immediate_full_exchange'):
             if args.test_hang_leg:
                 time.sleep(10 ** 6)
@@ -754,7 +780,7 @@ def main():
     # run on a multi-GPU node decides between them.  The peer-to-peer group shares the control plane; its buffers are its own.
     # A transport that cannot come up (no peer access between two GPUs, ...) raises on every rank together: the leg is
     # recorded as unavailable, the line is unaffected.
-    if use_dist and world > 1 and args.scaling == 'weak' and args.comm != 'p2p' and not args.no_p2p_leg:
+    if args.full and use_dist and world > 1 and args.scaling == 'weak' and args.comm != 'p2p' and not args.no_p2p_leg:
         with Watchdog('immediate_p2p'):
             p2p_leg = {'transport': 'p2p'}
             p2p = C.P2PComm(device_index=local_rank, group=comm.group_)
@@ -785,7 +811,7 @@ def main():
         if out is not None:
             out['immediate_p2p'] = p2p_leg
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(cfg)
         if world == 1 and not args.no_per_angle:
