@@ -11,6 +11,7 @@ import pytest
 
 import cases
 from oracle import adorym_oracle as O      # checker only
+from tests import ms_matrix as MM
 
 pytestmark = pytest.mark.gpu
 
@@ -261,33 +262,8 @@ def test_probe_gradient_is_bitwise_reproducible(A, ctx):
 
 def _generic_case(A, ctx, Py, Px, S=5, B=3, free_prop='inf', binning=1, n_modes=1, unknown_type='delta_beta', generic=False, seed=0):
     """Forward + gradients of one minibatch against the fp64 oracle (and its fp32 run for the 3x rule)."""
-    r = cases.rng(900 + Py * 7 + Px + seed)
-    Y, X = Py + 9, Px + 11
-    if unknown_type == 'delta_beta':
-        mk = lambda: np.stack([2e-3 * r.uniform(size=(Y, X, S)), 2e-4 * r.uniform(size=(Y, X, S))], -1)
-    else:
-        mk = lambda: np.stack([1 + 1e-2 * r.standard_normal((Y, X, S)), 2e-2 * r.standard_normal((Y, X, S))], -1)
-    obj, truth = mk(), mk()
-    pos = np.stack([r.integers(-3, 9, B), r.integers(-3, 11, B)], 1)
-    probes = (0.5 + r.uniform(0, 1, (n_modes, Py, Px))) * np.exp(1j * r.uniform(-np.pi, np.pi, (n_modes, Py, Px)))
-    phys = O.Physics((Py, Px), 5000., 1e-7, free_prop_cm=free_prop, binning=binning, unknown_type=unknown_type)
-    tt, _ = O.extract_tiles(truth, pos, (Py, Px), unknown_type)
-    target = O.predict(tt, probes, phys, 'float64')[0]
-    loss_o, pred_o, g_o, gp_o = O.forward_adjoint_object(obj, None, probes, pos, target, phys, 'float64')
-    _, _, g32, _ = O.forward_adjoint_object(obj.astype(np.float32), None, probes, pos, target, phys, 'float32')
-    eng = A.MultisliceEngine(ctx, (Y, X, S), (Py, Px), pos, 5000., 1e-7, free_prop_cm=free_prop, binning=binning,
-                             n_probe_modes=n_modes, unknown_type=unknown_type, generic=generic)
-    d_grad = ctx.zeros(obj.shape)
-    d_gp = ctx.zeros((n_modes, Py, Px, 2))
-    eng.set_batch(pos, target)
-    eng.rotate(ctx.array(obj, np.float32), None)
-    eng.multislice(ctx.array(np.stack([probes.real, probes.imag], -1).astype(np.float32)), grad_probe=d_gp, want_pred=True)
-    eng.rotate_adjoint(d_grad, None)
-    assert rel(eng.pred(), pred_o) < 5e-6, rel(eng.pred(), pred_o)
-    assert abs(eng.loss() - loss_o) <= 3e-5 * abs(loss_o)
-    e, e32 = rel(d_grad.get(), g_o), rel(g32, g_o)
-    assert e < 2e-4 and e <= 3 * e32 + 2e-5, (Py, Px, e, e32)
-    assert rel(d_gp.get(), np.stack([gp_o.real, gp_o.imag], -1)) < 2e-4
+    MM.check(MM.run_case(A, ctx, (Py, Px), S=S, B=B, free_prop=free_prop, binning=binning, n_modes=n_modes, unknown_type=unknown_type,
+                         generic=generic, margin=(9, 11), seed=seed), MM.GENERIC)
 
 
 @pytest.mark.parametrize('Py,Px', [(48, 48), (96, 96), (128, 128), (100, 100), (40, 56), (26, 35), (13, 22), (72, 64)])
