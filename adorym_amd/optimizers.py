@@ -124,20 +124,27 @@ class MomentumOptimizer(Optimizer):
         return x
 
 
+def plain_adam(opts):
+    """The (b1, b2, eps) that ``opts`` share when every one of them is a plain AdamOptimizer (no option beyond step_size, b1, b2,
+    eps), else None.  Under this rule alone a fused launch that updates several arrays gives the bits of their own apply_gradient."""
+    if not all(type(o) is AdamOptimizer and set(o.options_dict) <= {'step_size', 'b1', 'b2', 'eps'} for o in opts):
+        return None
+    keys = {(float(o.options_dict.get('b1', 0.9)), float(o.options_dict.get('b2', 0.999)), float(o.options_dict.get('eps', 1e-7)))
+            for o in opts}
+    return next(iter(keys)) if len(keys) == 1 else None
+
+
 def apply_small_params(ctx, items, i_batch):
     """The small optimisable parameters of one minibatch (adorym/optimizers.py:1022-1083: probe, probe_pos_correction,
     free_prop_cm, prj_affine_ls) in ONE launch (adm_adam_step_small) when every one of them is driven by a plain AdamOptimizer with
     the same (b1, b2, eps); otherwise one by one through the optimisers' own apply_gradient.  ``items``: dicts with
     opt, x, g (DeviceArrays), and optionally center_cols (drift guard, :1046-1048), pin (DeviceArray copied over the first
     entries of x, :1067-1073), zero_grad (the gradient accumulator is zero-filled once used).  Same arithmetic either way."""
-    import ctypes as C
     from ._lib import SmallParam, SMALL_PARAMS_MAX
     if not items:
         return
-    keys = {(float(it['opt'].options_dict.get('b1', 0.9)), float(it['opt'].options_dict.get('b2', 0.999)),
-             float(it['opt'].options_dict.get('eps', 1e-7))) for it in items}
-    plain = all(type(it['opt']) is AdamOptimizer and set(it['opt'].options_dict) <= {'step_size', 'b1', 'b2', 'eps'} for it in items)
-    if plain and len(keys) == 1 and len(items) <= SMALL_PARAMS_MAX:
+    betas = plain_adam([it['opt'] for it in items])
+    if betas is not None and len(items) <= SMALL_PARAMS_MAX:
         # the descriptor array is the same minibatch after minibatch (same buffers, same step sizes): build it once per combination
         sig = tuple((it['x'].ptr, it['g'].ptr, it['opt'].params_whole_array_dict['m'].ptr, it['opt'].params_whole_array_dict['v'].ptr,
                      it['x'].size, float(it['opt'].options_dict.get('step_size', 0.001)), int(it.get('center_cols', 0)),
@@ -158,7 +165,7 @@ def apply_small_params(ctx, items, i_batch):
             cache[sig] = arr
         for it in items:
             it['opt'].i_batch += 1
-        b1, b2, eps = next(iter(keys))
+        b1, b2, eps = betas
         check(ctx.lib.adm_adam_step_small(ctx.handle, arr, len(items), int(i_batch), b1, b2, eps))
         return
     for it in items:

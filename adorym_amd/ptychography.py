@@ -17,6 +17,7 @@ reference line by line so that runs are comparable minibatch for minibatch:
 import datetime
 import os
 import sys
+import threading
 import time
 import warnings
 
@@ -25,17 +26,16 @@ import numpy as np
 from . import _lib
 from . import global_settings
 from .array_ops import ObjectFunction, Gradient, Mask
-from .comm import LocalComm, from_env
-from .util import epoch_task_list, rank_batch
+from .comm import from_env
+from .util import epoch_task_list, rank_batch, initialize_probe
 from .constants import PI
-from .device import Context
+from .device import Context, DeviceArray
 from .differentiator import Differentiator
 from .dp import DataParallelObject, HipOps, constraint_flags
-from .forward_model import ForwardModel, PtychographyModel, MultiDistModel
-from .optimizers import Optimizer, AdamOptimizer, GDOptimizer, MomentumOptimizer, apply_small_params
+from .forward_model import PtychographyModel, MultiDistModel
+from .optimizers import Optimizer, AdamOptimizer, GDOptimizer, MomentumOptimizer, apply_small_params, plain_adam
 from .propagate import MultisliceEngine, RotationTable, get_kernel
-from .regularizers import L1Regularizer, TVRegularizer, ReweightedL1Regularizer
-from .util import rotation_lookup, split_tasks, initialize_probe
+from .regularizers import L1Regularizer, TVRegularizer, ReweightedL1Regularizer, combined_weights
 from ._io import DataFile, write_tiff, read_tiff
 
 
@@ -178,47 +178,33 @@ def create_summary(save_path, values, verbose=True):
         print('========================================')
 
 
-def _write_intermediate(output_folder, arr, unknown_type, i_epoch, i_batch, save_history, opt_ls, probe_dev, params, n_theta,
-                        is_multi_dist):
-    """output_object(full_output=False) + output_intermediate_parameters of the reference: object TIFFs under
-    intermediate/object (named by (epoch, batch) when save_history, else overwritten), and one file set per optimised
-    parameter under intermediate/<what>."""
-    tag = '_{}_{}'.format(i_epoch, i_batch) if save_history else ''
-    od = os.path.join(output_folder, 'intermediate', 'object')
-    os.makedirs(od, exist_ok=True)
+def _host(v):
+    return v.get() if hasattr(v, 'get') else v
+
+
+def _mag_phase(a):
+    return np.sqrt(a[..., 0] ** 2 + a[..., 1] ** 2), np.arctan2(a[..., 1], a[..., 0])
+
+
+def _write_images(obj_dir, probe_dir, tag, arr, unknown_type, probe=None, complex_probe=False):
+    """The object's images (delta / beta, or obj_mag / obj_phase for unknown_type='real_imag', util.py:1990-2005) under ``obj_dir``
+    and, given ``probe`` [modes, Py, Px, 2], probe_mag / probe_phase under ``probe_dir``; every name ends in ``tag``.
+    ``complex_probe``: the probe's images are np.abs / np.angle of the complex probe (the outputs after an epoch) instead of
+    sqrt(re^2 + im^2) / arctan2 (the intermediate ones); the two can differ in the last bit."""
     if unknown_type == 'delta_beta':
-        write_tiff(arr[..., 0], os.path.join(od, 'delta' + tag), dtype='float32')
-        write_tiff(arr[..., 1], os.path.join(od, 'beta' + tag), dtype='float32')
+        images = [(obj_dir, 'delta', arr[..., 0]), (obj_dir, 'beta', arr[..., 1])]
     else:
-        write_tiff(np.sqrt(arr[..., 0] ** 2 + arr[..., 1] ** 2), os.path.join(od, 'obj_mag' + tag), dtype='float32')
-        write_tiff(np.arctan2(arr[..., 1], arr[..., 0]), os.path.join(od, 'obj_phase' + tag), dtype='float32')
-    host = lambda v: v.get() if hasattr(v, 'get') else np.asarray(v)
-    for o_ in opt_ls:
-        if o_.name == 'obj':
-            continue
-        if o_.name == 'probe':
-            pd_ = os.path.join(output_folder, 'intermediate', 'probe')
-            os.makedirs(pd_, exist_ok=True)
-            pa = probe_dev.get()
-            write_tiff(np.sqrt(pa[..., 0] ** 2 + pa[..., 1] ** 2), os.path.join(pd_, 'probe_mag' + tag), dtype='float32')
-            write_tiff(np.arctan2(pa[..., 1], pa[..., 0]), os.path.join(pd_, 'probe_phase' + tag), dtype='float32')
-        elif o_.name == 'probe_pos_correction':
-            pd_ = os.path.join(output_folder, 'intermediate', 'probe_pos')
-            os.makedirs(pd_, exist_ok=True)
-            corr = host(params['probe_pos_correction'])
-            if is_multi_dist:
-                np.savetxt(os.path.join(pd_, 'probe_pos_correction_{}_{}.txt'.format(i_epoch, i_batch)), corr)
-            else:
-                for i_t in range(n_theta):
-                    np.savetxt(os.path.join(pd_, 'probe_pos_correction_{}_{}_{}.txt'.format(i_epoch, i_batch, i_t)), corr[i_t])
-        elif o_.name == 'prj_affine_ls':
-            pd_ = os.path.join(output_folder, 'intermediate', 'prj_affine')
-            os.makedirs(pd_, exist_ok=True)
-            np.savetxt(os.path.join(pd_, 'prj_affine_{}.txt'.format(i_epoch)), np.concatenate(host(params['prj_affine_ls']), 0))
+        images = list(zip((obj_dir,) * 2, ('obj_mag', 'obj_phase'), _mag_phase(arr)))
+    if probe is not None:
+        if complex_probe:
+            pc = probe[..., 0] + 1j * probe[..., 1]
+            mag_phase = np.abs(pc), np.angle(pc)
         else:
-            pd_ = os.path.join(output_folder, 'intermediate', o_.name)
-            os.makedirs(pd_, exist_ok=True)
-            np.savetxt(os.path.join(pd_, '{}_{}.txt'.format(o_.name, i_epoch)), np.atleast_1d(host(params[o_.name])))
+            mag_phase = _mag_phase(probe)
+        images += zip((probe_dir,) * 2, ('probe_mag', 'probe_phase'), mag_phase)
+    for d_, name, im in images:
+        os.makedirs(d_, exist_ok=True)
+        write_tiff(im, os.path.join(d_, name + tag), dtype='float32')
 
 
 def _not_implemented(cond, what):
@@ -290,254 +276,296 @@ def reconstruct_ptychography(
     """
     _call_args = dict(locals())         # the keyword surface as called (for summary.txt); first statement on purpose
     _call_args.update(_call_args.pop('kwargs', {}))
-    t_zero = time.time()
-    comm = kwargs.pop('comm', None) or from_env()
-    return_state = kwargs.pop('return_state', False)
-    fuse_per_angle = kwargs.pop('fuse_per_angle', True)
-    n_ranks, rank = comm.size, comm.rank
-    if backend != 'hip':
-        warnings.warn("adorym_amd has a single backend ('hip'); backend='%s' is ignored." % backend)
-    global_settings.backend = 'hip'
+    run = _Run(_call_args, kwargs)
+    run.refuse_unsupported()
+    run.open_device()
+    run.read_data()
+    run.create_engines()
+    run.create_object()
+    run.create_forward_model()
+    run.create_probe_and_small_params()
+    run.run_epochs()
+    return run.finish()
 
-    # ---- combinations outside the accelerated path: fail loudly -------------------------------------
-    _not_implemented(distribution_mode is not None, "distribution_mode='%s'" % distribution_mode)
-    if cpu_only:
-        # (demos/2d_ptychography_w_position_correction.py asks for it; there is no CPU path here and none is substituted)
-        warnings.warn('cpu_only=True is ignored: adorym_amd computes on the GPU only.')
-    _not_implemented(run_bfloat16 or run_float64, 'run_bfloat16 / run_float64')
-    if unknown_type not in ('delta_beta', 'real_imag'):
-        raise ValueError("unknown_type must be 'delta_beta' or 'real_imag'")
-    if unknown_type == 'real_imag':
-        # accelerated subset for complex-transmission unknowns: no masks / object-type constraints / binning yet
-        _not_implemented(finite_support_mask_path is not None, "finite support mask with unknown_type='real_imag'")
-        _not_implemented(object_type != 'normal', "object_type='%s' with unknown_type='real_imag'" % object_type)
-        _not_implemented(binning != 1, "binning > 1 with unknown_type='real_imag'")
-    _not_implemented(multiscale_level != 1, 'multiscale_level > 1')
-    _not_implemented(pure_projection or forward_algorithm != 'fresnel', 'pure_projection / CTF forward algorithm')
-    _not_implemented(use_epie, 'ePIE')
-    _not_implemented(is_minus_logged, 'is_minus_logged')
-    _not_implemented(not common_probe_pos, 'common_probe_pos=False')
-    _not_implemented(not shared_probe_among_angles, 'shared_probe_among_angles=False')
-    _not_implemented(update_using_external_algorithm is not None, 'update_using_external_algorithm')
-    _not_implemented(shrink_cycle is not None, 'shrink-wrap mask updates')
-    _not_implemented(initial_tilt is not None, 'initial_tilt')
-    _not_implemented(interpolation != 'bilinear', "interpolation='%s'" % interpolation)
-    for nm, flag in (('optimize_probe_defocusing', optimize_probe_defocusing), ('optimize_probe_pos_offset', optimize_probe_pos_offset),
-                     ('optimize_prj_pos_offset', optimize_prj_pos_offset),
-                     ('optimize_slice_pos', optimize_slice_pos), ('optimize_tilt', optimize_tilt),
-                     ('optimize_ctf_lg_kappa', optimize_ctf_lg_kappa)):
-        _not_implemented(flag, nm)
-    if update_scheme not in ('immediate', 'per angle'):
-        raise ValueError("update_scheme must be 'immediate' or 'per angle'")
 
-    # ---- device -----------------------------------------------------------------------------------
-    stream = comm.stream_handle() if hasattr(comm, 'stream_handle') else None
-    dev_index = getattr(comm, 'device_index', None)
-    ctx = Context(gpu_index if dev_index is None else dev_index, stream=stream)
-    if hasattr(comm, 'attach'):
-        comm.attach(ctx)            # RCCL communicator of this rank on the context's stream (adm_comm_init)
+class _SmallParam(object):
+    """One optimised small parameter (optimizers.py:1022-1083): its ``key`` in optimizable_params, its optimiser, device value ``x``,
+    gradient accumulator ``g``, index ``i_grad`` in the gradient tuple, the extras of its update (``pin``: copied over the first entries
+    of x; ``center_cols``: the drift guard) and the global minibatch indices [delay, limit) in which it is updated."""
 
-    if rank == 0:
-        timestr = str(datetime.datetime.today())
-        timestr = timestr[:timestr.find('.')]
-        for i in [':', '-', ' ']:
-            timestr = timestr.replace(i, '_' if i == ' ' else '')
-    else:
-        timestr = None
-    timestr = comm.bcast_object(timestr, root=0)
-    if output_folder is None:
-        output_folder = 'recon_{}'.format(timestr)
-    if save_path != '.':
-        output_folder = os.path.join(save_path, output_folder)
-    stdout_options = {'save_stdout': save_stdout, 'output_folder': output_folder, 'timestamp': timestr}
-    sto_rank = 0 if not debug else rank
-    print_flush('Output folder is {}'.format(output_folder), sto_rank, rank, **stdout_options)
+    def __init__(self, key, opt, x, i_grad, delay, limit, **extras):
+        self.key, self.opt, self.x, self.i_grad, self.delay, self.limit, self.extras = key, opt, x, i_grad, delay, limit, extras
+        self.g = x.ctx.zeros(x.shape)
 
-    # ---- data and metadata (ptychography.py:237-323) ------------------------------------------------
-    t0 = time.time()
-    f = DataFile(fname if not isinstance(fname, str) else os.path.join(save_path, fname))
-    prj = f.data
-    obj_size = [int(v) for v in obj_size]
-    if obj_size[-1] == 1:
-        two_d_mode = True
-    if n_theta is None:
-        n_theta = prj.shape[0]
-    if two_d_mode:
-        n_theta = 1
-    try:
-        theta_ls = np.asarray(f.get('metadata/theta'))
-    except Exception:
-        theta_ls = np.linspace(theta_st, theta_end, n_theta, dtype='float32')
-    if theta_downsample is not None:
-        theta_ls = theta_ls[::theta_downsample]
-        n_theta = len(theta_ls)
-    if probe_pos is None:
-        probe_pos = np.array(f.get('metadata/probe_pos_px')).astype(float)
-    else:
-        probe_pos = np.array(probe_pos).astype(float)
-    if energy_ev is None:
-        energy_ev = float(f.get('metadata/energy_ev'))
-    if psize_cm is None:
-        psize_cm = float(f.get('metadata/psize_cm'))
-    _not_implemented(slice_pos_cm_ls is not None and len(slice_pos_cm_ls) > 1, 'sparse multislice (slice_pos_cm_ls)')
-    if free_prop_cm is None:
-        free_prop_cm = f.get('metadata/free_prop_cm')
-    is_multi_dist = np.array(free_prop_cm).size != 1          # ptychography.py:296-305
-    holo_tiled = False
-    if is_multi_dist:
-        # one object slice; config 5 is one undivided field of view (n_blocks == 1) without a safe zone
-        free_prop_cm = np.asarray(free_prop_cm, dtype=float).reshape(-1)
-        n_dists = len(free_prop_cm)
-        safe_zone_width = int(safe_zone_width or 0)
-        if prj.shape[1] != n_dists * len(probe_pos):
-            raise ValueError('multi-distance data: prj.shape[1] = %d is not n_dists x n_blocks = %d x %d' % (prj.shape[1], n_dists, len(probe_pos)))
-        _not_implemented(not two_d_mode, 'multi-distance holography of a 3-D object')
-        _not_implemented(n_probe_modes != 1, 'several probe modes with multi-distance data')
-        _not_implemented(loss_function_type != 'lsq', 'Poisson loss with multi-distance data')
-        holo_tiled = len(probe_pos) > 1 or safe_zone_width > 0
-        if holo_tiled:
-            # data divided into sub-tiles and / or a safe zone around every tile (adorym/forward_model.py:884-1034)
-            tile_size = [int(v) + 2 * safe_zone_width for v in prj.shape[-2:]]
-            _not_implemented(max(tile_size) > 128, 'sub-hologram + 2 safe zones larger than 128 pixels (%d x %d)' % tuple(tile_size))
-            _not_implemented(optimize_free_prop or optimize_prj_affine or optimize_probe or optimize_all_probe_pos,
-                             'optimize_free_prop / optimize_prj_affine / optimize_probe / optimize_all_probe_pos with multi-distance data divided into sub-tiles')
-            _not_implemented(beamstop is not None, 'a beamstop with multi-distance data divided into sub-tiles')
-            pp_ = np.round(np.asarray(probe_pos)).astype(int)
-            if safe_zone_width == 0:
-                # (:921-925 resets pad_arr to zero while the object has been padded: a tile hanging over the edge is misread there)
-                _not_implemented(bool(np.any(pp_ < 0) or np.any(pp_ + np.array(prj.shape[-2:]) > np.array(obj_size[:2]))),
-                                 'tiles hanging over the object edge with safe_zone_width = 0')
-            if len(probe_pos) > 1:
-                # (:931-943, the branch for a chunk of ONE tile, cuts object and probe to different sizes and fails in the reference)
-                mb_ = minibatch_size if minibatch_size is not None else len(probe_pos)
-                _not_implemented(mb_ % n_dp_batch == 1, 'a minibatch whose last n_dp_batch chunk holds a single tile')
+    def due(self, i_global):
+        return self.delay <= i_global < self.limit
+
+
+# the small parameters that the fused holography launch (adm_holo_fwd_adj_adam) updates, with its argument for each; a run that
+# optimises any other one takes the separate launches
+_HOLO_FUSED_SLOTS = {'free_prop_cm': 'dists', 'prj_affine_ls': 'affine'}
+
+
+class _Run(object):
+    """One call of reconstruct_ptychography.  The named keywords are its attributes and every stage adds what it builds.  Like the
+    reference's locals, some keywords are rewritten once: output_folder (save_path joined), obj_size, two_d_mode, n_theta, probe_pos,
+    energy_ev, psize_cm, free_prop_cm, safe_zone_width and minibatch_size by open_device / read_data; fuse_per_angle and forward_model
+    ('auto' or a class, then the model itself) by create_forward_model."""
+
+    def __init__(self, call_args, kwargs):
+        self.call_args = call_args
+        self.__dict__.update((k, v) for k, v in call_args.items() if k not in kwargs)
+        self.t_zero = time.time()
+        self.comm = kwargs.pop('comm', None) or from_env()       # (the private keywords; the rest of kwargs goes to initialize_probe)
+        self.return_state = kwargs.pop('return_state', False)
+        self.fuse_per_angle = kwargs.pop('fuse_per_angle', True)
+        self.ops = kwargs.pop('ops', None)
+        kwargs.pop('probe_size', None)
+        self.kwargs = kwargs
+        self.n_ranks, self.rank = self.comm.size, self.comm.rank
+
+    def log(self, msg):
+        print_flush(msg, self.sto_rank, self.rank, **self.stdout_options)
+
+    def refuse_unsupported(self):
+        """Combinations outside the accelerated path fail loudly (the ones that need the data's shape: read_data)."""
+        if self.backend != 'hip':
+            warnings.warn("adorym_amd has a single backend ('hip'); backend='%s' is ignored." % self.backend)
+        global_settings.backend = 'hip'
+        _not_implemented(self.distribution_mode is not None, "distribution_mode='%s'" % self.distribution_mode)
+        if self.cpu_only:
+            # (demos/2d_ptychography_w_position_correction.py asks for it; there is no CPU path here and none is substituted)
+            warnings.warn('cpu_only=True is ignored: adorym_amd computes on the GPU only.')
+        _not_implemented(self.run_bfloat16 or self.run_float64, 'run_bfloat16 / run_float64')
+        if self.unknown_type not in ('delta_beta', 'real_imag'):
+            raise ValueError("unknown_type must be 'delta_beta' or 'real_imag'")
+        if self.unknown_type == 'real_imag':
+            # accelerated subset for complex-transmission unknowns: no masks / object-type constraints / binning yet
+            _not_implemented(self.finite_support_mask_path is not None, "finite support mask with unknown_type='real_imag'")
+            _not_implemented(self.object_type != 'normal', "object_type='%s' with unknown_type='real_imag'" % self.object_type)
+            _not_implemented(self.binning != 1, "binning > 1 with unknown_type='real_imag'")
+        _not_implemented(self.multiscale_level != 1, 'multiscale_level > 1')
+        _not_implemented(self.pure_projection or self.forward_algorithm != 'fresnel', 'pure_projection / CTF forward algorithm')
+        _not_implemented(self.use_epie, 'ePIE')
+        _not_implemented(self.is_minus_logged, 'is_minus_logged')
+        _not_implemented(not self.common_probe_pos, 'common_probe_pos=False')
+        _not_implemented(not self.shared_probe_among_angles, 'shared_probe_among_angles=False')
+        _not_implemented(self.update_using_external_algorithm is not None, 'update_using_external_algorithm')
+        _not_implemented(self.shrink_cycle is not None, 'shrink-wrap mask updates')
+        _not_implemented(self.initial_tilt is not None, 'initial_tilt')
+        _not_implemented(self.interpolation != 'bilinear', "interpolation='%s'" % self.interpolation)
+        for nm in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_prj_pos_offset', 'optimize_slice_pos',
+                   'optimize_tilt', 'optimize_ctf_lg_kappa'):
+            _not_implemented(getattr(self, nm), nm)
+        if self.update_scheme not in ('immediate', 'per angle'):
+            raise ValueError("update_scheme must be 'immediate' or 'per angle'")
+
+    def open_device(self):
+        """This rank's device context and the run's output folder."""
+        comm = self.comm
+        stream = comm.stream_handle() if hasattr(comm, 'stream_handle') else None
+        dev_index = getattr(comm, 'device_index', None)
+        self.ctx = Context(self.gpu_index if dev_index is None else dev_index, stream=stream)
+        if hasattr(comm, 'attach'):
+            comm.attach(self.ctx)            # RCCL communicator of this rank on the context's stream (adm_comm_init)
+        now = str(datetime.datetime.today())
+        timestr = now[:now.find('.')].replace(':', '').replace('-', '').replace(' ', '_') if self.rank == 0 else None
+        timestr = comm.bcast_object(timestr, root=0)
+        if self.output_folder is None:
+            self.output_folder = 'recon_{}'.format(timestr)
+        if self.save_path != '.':
+            self.output_folder = os.path.join(self.save_path, self.output_folder)
+        self.stdout_options = {'save_stdout': self.save_stdout, 'output_folder': self.output_folder, 'timestamp': timestr}
+        self.sto_rank = 0 if not self.debug else self.rank
+        self.log('Output folder is {}'.format(self.output_folder))
+
+    def read_data(self):
+        """Data and metadata (ptychography.py:237-346): angles, positions, distances, probe size, minibatch size."""
+        t0 = time.time()
+        self.f = DataFile(self.fname if not isinstance(self.fname, str) else os.path.join(self.save_path, self.fname))
+        prj = self.prj = self.f.data
+        obj_size = self.obj_size = [int(v) for v in self.obj_size]
+        if obj_size[-1] == 1:
+            self.two_d_mode = True
+        if self.n_theta is None:
+            self.n_theta = prj.shape[0]
+        if self.two_d_mode:
+            self.n_theta = 1
+        try:
+            self.theta_ls = np.asarray(self.f.get('metadata/theta'))
+        except Exception:
+            self.theta_ls = np.linspace(self.theta_st, self.theta_end, self.n_theta, dtype='float32')
+        if self.theta_downsample is not None:
+            self.theta_ls = self.theta_ls[::self.theta_downsample]
+            self.n_theta = len(self.theta_ls)
+        probe_pos = self.probe_pos = np.array(self.f.get('metadata/probe_pos_px') if self.probe_pos is None else self.probe_pos).astype(float)
+        if self.energy_ev is None:
+            self.energy_ev = float(self.f.get('metadata/energy_ev'))
+        if self.psize_cm is None:
+            self.psize_cm = float(self.f.get('metadata/psize_cm'))
+        _not_implemented(self.slice_pos_cm_ls is not None and len(self.slice_pos_cm_ls) > 1, 'sparse multislice (slice_pos_cm_ls)')
+        if self.free_prop_cm is None:
+            self.free_prop_cm = self.f.get('metadata/free_prop_cm')
+        self.is_multi_dist = np.array(self.free_prop_cm).size != 1          # ptychography.py:296-305
+        self.holo_tiled = False
+        if self.is_multi_dist:
+            # SURVEY section 8 f1: one object slice; config 5 is one undivided field of view (n_blocks == 1) without a safe zone
+            free_prop_cm = self.free_prop_cm = np.asarray(self.free_prop_cm, dtype=float).reshape(-1)
+            n_dists = self.n_dists = len(free_prop_cm)
+            safe_zone_width = self.safe_zone_width = int(self.safe_zone_width or 0)
+            if prj.shape[1] != n_dists * len(probe_pos):
+                raise ValueError('multi-distance data: prj.shape[1] = %d is not n_dists x n_blocks = %d x %d' % (prj.shape[1], n_dists, len(probe_pos)))
+            _not_implemented(not self.two_d_mode, 'multi-distance holography of a 3-D object')
+            _not_implemented(self.n_probe_modes != 1, 'several probe modes with multi-distance data')
+            _not_implemented(self.loss_function_type != 'lsq', 'Poisson loss with multi-distance data')
+            self.holo_tiled = len(probe_pos) > 1 or safe_zone_width > 0
+            if self.holo_tiled:
+                # data divided into sub-tiles and / or a safe zone around every tile (adorym/forward_model.py:884-1034)
+                tile_size = self.tile_size = [int(v) + 2 * safe_zone_width for v in prj.shape[-2:]]
+                _not_implemented(max(tile_size) > 128, 'sub-hologram + 2 safe zones larger than 128 pixels (%d x %d)' % tuple(tile_size))
+                _not_implemented(self.optimize_free_prop or self.optimize_prj_affine or self.optimize_probe or self.optimize_all_probe_pos,
+                                 'optimize_free_prop / optimize_prj_affine / optimize_probe / optimize_all_probe_pos with multi-distance data divided into sub-tiles')
+                _not_implemented(self.beamstop is not None, 'a beamstop with multi-distance data divided into sub-tiles')
+                pp_ = np.round(np.asarray(probe_pos)).astype(int)
+                if safe_zone_width == 0:
+                    # (:921-925 resets pad_arr to zero while the object has been padded: a tile hanging over the edge is misread there)
+                    _not_implemented(bool(np.any(pp_ < 0) or np.any(pp_ + np.array(prj.shape[-2:]) > np.array(obj_size[:2]))),
+                                     'tiles hanging over the object edge with safe_zone_width = 0')
+                if len(probe_pos) > 1:
+                    # (:931-943, the branch for a chunk of ONE tile, cuts object and probe to different sizes and fails in the reference)
+                    mb_ = self.minibatch_size if self.minibatch_size is not None else len(probe_pos)
+                    _not_implemented(mb_ % self.n_dp_batch == 1, 'a minibatch whose last n_dp_batch chunk holds a single tile')
+            else:
+                _not_implemented(list(prj.shape[-2:]) != list(obj_size[:2]), 'holograms whose size differs from the object size')
+                # one (sy, sx) per distance on the measured holograms (forward_model.py:1075-1085): beside the object and the probe only
+                _not_implemented(self.optimize_all_probe_pos and (self.optimize_free_prop or self.optimize_prj_affine),
+                                 'optimize_all_probe_pos together with optimize_free_prop / optimize_prj_affine')
+            self.probe_size = [int(v) for v in obj_size[:2]]          # subdiv_probe (ptychography.py:312-314)
         else:
-            _not_implemented(list(prj.shape[-2:]) != list(obj_size[:2]), 'holograms whose size differs from the object size')
-            # one (sy, sx) per distance on the measured holograms (forward_model.py:1075-1085): beside the object and the probe only
-            _not_implemented(optimize_all_probe_pos and (optimize_free_prop or optimize_prj_affine),
-                             'optimize_all_probe_pos together with optimize_free_prop / optimize_prj_affine')
-        probe_size = [int(v) for v in obj_size[:2]]          # subdiv_probe (ptychography.py:312-314)
-    else:
-        _not_implemented(optimize_free_prop or optimize_prj_affine, 'optimize_free_prop / optimize_prj_affine without multi-distance data')
-        if isinstance(free_prop_cm, np.ndarray):
-            free_prop_cm = free_prop_cm.reshape(-1)[0]
-            free_prop_cm = free_prop_cm if isinstance(free_prop_cm, str) else float(free_prop_cm)
-        probe_size = [int(v) for v in prj.shape[-2:]]
-    print_flush('Data reading: {} s'.format(time.time() - t0), sto_rank, rank, **stdout_options)
-    print_flush('Data shape: {}'.format([n_theta, *prj.shape[1:]]), sto_rank, rank, **stdout_options)
-    kwargs.pop('probe_size', None)
+            _not_implemented(self.optimize_free_prop or self.optimize_prj_affine, 'optimize_free_prop / optimize_prj_affine without multi-distance data')
+            if isinstance(self.free_prop_cm, np.ndarray):
+                free_prop_cm = self.free_prop_cm.reshape(-1)[0]
+                self.free_prop_cm = free_prop_cm if isinstance(free_prop_cm, str) else float(free_prop_cm)
+            self.probe_size = [int(v) for v in prj.shape[-2:]]
+        self.log('Data reading: {} s'.format(time.time() - t0))
+        self.log('Data shape: {}'.format([self.n_theta, *prj.shape[1:]]))
 
-    if minibatch_size is None:
-        minibatch_size = len(probe_pos)
-    if minibatch_size > 1 and len(probe_pos) == 1:
-        warnings.warn('Undivided fullfield data with minibatch > 1: setting minibatch_size to 1 (ptychography.py:342-346).')
-        minibatch_size = 1
+        if self.minibatch_size is None:
+            self.minibatch_size = len(probe_pos)
+        if self.minibatch_size > 1 and len(probe_pos) == 1:
+            warnings.warn('Undivided fullfield data with minibatch > 1: setting minibatch_size to 1 (ptychography.py:342-346).')
+            self.minibatch_size = 1
+        self.ds_level = 1
+        if self.rank == 0:
+            os.makedirs(self.output_folder, exist_ok=True)
+        self.comm.barrier()
 
-    ds_level = 1
-    this_obj_size = obj_size
-    if rank == 0:
-        os.makedirs(output_folder, exist_ok=True)
-    comm.barrier()
+    def create_engines(self):
+        """Physics (ptychography.py:388-391) and the multislice / holography engines."""
+        ctx, obj_size, probe_size = self.ctx, self.obj_size, self.probe_size
+        voxel_nm = np.array([self.psize_cm] * 3) * 1.e7 * self.ds_level
+        self.lmbda_nm = 1240. / self.energy_ev
+        self.h = get_kernel(voxel_nm[-1] * self.binning, self.lmbda_nm, voxel_nm, probe_size, fresnel_approx=self.fresnel_approx,
+                            sign_convention=self.sign_convention) if not self.is_multi_dist else None
+        self.probe_pos_int = np.round(self.probe_pos).astype(int)
+        self.holo_engine = self.tile_engine = None
+        common = dict(sign_convention=self.sign_convention, scale_ri_by_k=self.scale_ri_by_k, unknown_type=self.unknown_type)
+        if self.holo_tiled:
+            # one engine for all distances: tile = sub-hologram + 2 safe zones at (position - safe zone), every tile listed n_dists
+            # times in a row and entry b Fresnel-propagated to distance b % n_dists after the slice (fresnel_propagate,
+            # adorym/propagate.py:282-288), loss over the sub-hologram's window only (forward_model.py:1027-1029) -- the detector mask
+            # that also serves the beamstop
+            szw, tile_size = self.safe_zone_width, self.tile_size
+            window = np.zeros(tile_size, np.float32)
+            window[szw:tile_size[0] - szw, szw:tile_size[1] - szw] = 1
+            self.engine = self.tile_engine = MultisliceEngine(
+                ctx, obj_size, tile_size, np.repeat(self.probe_pos_int - szw, self.n_dists, axis=0), self.energy_ev, self.psize_cm,
+                free_prop_cm=self.free_prop_cm, max_batch=self.minibatch_size * self.n_dists, beamstop=window, **common)
+        elif self.is_multi_dist:
+            from .holography import HolographyEngine
+            self.holo_engine = HolographyEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm, raw_data_type=self.raw_data_type,
+                                                **common)
+            # a minimal multislice plan is still created: it carries the object geometry for the regulariser kernels
+            self.engine = MultisliceEngine(ctx, obj_size, (8, 8), np.zeros((1, 2), int), self.energy_ev, self.psize_cm, free_prop_cm=0,
+                                           max_batch=1, unknown_type=self.unknown_type)
+        else:
+            self.engine = MultisliceEngine(
+                ctx, obj_size, probe_size, self.probe_pos_int, self.energy_ev, self.psize_cm, free_prop_cm=self.free_prop_cm,
+                binning=self.binning, fresnel_approx=self.fresnel_approx, normalize_fft=self.normalize_fft, kernel=self.h,
+                n_probe_modes=self.n_probe_modes, max_batch=self.minibatch_size, loss_function_type=self.loss_function_type,
+                poisson_multiplier=self.poisson_multiplier, beamstop=self.beamstop,
+                # the rotation stores slice transmissions only; rotate_out_of_loop and plugin models read obj_rot
+                transmissions_only=(self.forward_model == 'auto' and not self.rotate_out_of_loop), **common)
+        tables, theta_ls = {}, self.theta_ls
 
-    # ---- physics (ptychography.py:388-391) ----------------------------------------------------------
-    voxel_nm = np.array([psize_cm] * 3) * 1.e7 * ds_level
-    lmbda_nm = 1240. / energy_ev
-    delta_nm = voxel_nm[-1]
-    h = get_kernel(delta_nm * binning, lmbda_nm, voxel_nm, probe_size, fresnel_approx=fresnel_approx, sign_convention=sign_convention) \
-        if not is_multi_dist else None
-    probe_pos_int = np.round(probe_pos).astype(int)
-    holo_engine = tile_engine = None
-    if holo_tiled:
-        # one engine for all distances: tile = sub-hologram + 2 safe zones at (position - safe zone), every tile listed n_dists
-        # times in a row and entry b Fresnel-propagated to distance b % n_dists after the slice (fresnel_propagate,
-        # adorym/propagate.py:282-288), loss over the sub-hologram's window only (forward_model.py:1027-1029) -- the detector mask
-        # that also serves the beamstop
-        window = np.zeros(tile_size, np.float32)
-        window[safe_zone_width:tile_size[0] - safe_zone_width, safe_zone_width:tile_size[1] - safe_zone_width] = 1
-        engine = tile_engine = MultisliceEngine(ctx, this_obj_size, tile_size, np.repeat(probe_pos_int - safe_zone_width, n_dists, axis=0),
-                                                energy_ev, psize_cm, free_prop_cm=free_prop_cm, sign_convention=sign_convention,
-                                                scale_ri_by_k=scale_ri_by_k, max_batch=minibatch_size * n_dists, unknown_type=unknown_type,
-                                                beamstop=window)
-    elif is_multi_dist:
-        from .holography import HolographyEngine
-        holo_engine = HolographyEngine(ctx, probe_size, n_dists, energy_ev, psize_cm, sign_convention=sign_convention,
-                                       unknown_type=unknown_type, raw_data_type=raw_data_type, scale_ri_by_k=scale_ri_by_k)
-        # a minimal multislice plan is still created: it carries the object geometry for the regulariser kernels
-        engine = MultisliceEngine(ctx, this_obj_size, (8, 8), np.zeros((1, 2), int), energy_ev, psize_cm, free_prop_cm=0,
-                                  max_batch=1, unknown_type=unknown_type)
-    else:
-        engine = MultisliceEngine(ctx, this_obj_size, probe_size, probe_pos_int, energy_ev, psize_cm, free_prop_cm=free_prop_cm,
-                                  binning=binning, fresnel_approx=fresnel_approx, sign_convention=sign_convention,
-                                  normalize_fft=normalize_fft, kernel=h, scale_ri_by_k=scale_ri_by_k, n_probe_modes=n_probe_modes,
-                                  max_batch=minibatch_size, loss_function_type=loss_function_type,
-                                  poisson_multiplier=poisson_multiplier, unknown_type=unknown_type, beamstop=beamstop,
-                                  # the rotation stores slice transmissions only; rotate_out_of_loop and plugin models read obj_rot
-                                  transmissions_only=(forward_model == 'auto' and not rotate_out_of_loop))
+        def rotation_tables(i_theta):
+            """Rotation lookup tables: computed like save_rotation_lookup (util.py:492-516), cached on the device per angle (the
+            reference caches them as .npy files in ./arrsize_*; no files are written here)."""
+            if i_theta not in tables:
+                tables[i_theta] = RotationTable(ctx, obj_size, theta_ls[i_theta])
+            return tables[i_theta]
+        self.rotation_tables = rotation_tables      # (not a method: the model keeps it, and a run it held would outlive the driver)
 
-    # rotation lookup tables: computed like save_rotation_lookup (util.py:492-516), cached on the device per angle
-    # (the reference caches them as .npy files in ./arrsize_*; no files are written here)
-    _tables = {}
+    def create_object(self):
+        """Seed (ptychography.py:410-412), object optimiser (:417-453), object / gradient / moments (:492-576), checkpoint restore."""
+        ctx, comm, obj_size = self.ctx, self.comm, self.obj_size
+        seed = comm.bcast_object(int(time.time() / 60), root=0)
+        np.random.seed(seed)
 
-    def rotation_tables(i_theta):
-        if i_theta not in _tables:
-            _tables[i_theta] = RotationTable(ctx, this_obj_size, theta_ls[i_theta])
-        return _tables[i_theta]
+        optimizer = self.optimizer
+        if isinstance(optimizer, Optimizer):
+            opt = optimizer
+            opt.name = 'obj'
+        elif optimizer in ('adam', 'gd', 'momentum'):
+            cls, extra = {'adam': (AdamOptimizer, {}), 'gd': (GDOptimizer, dict(dynamic_rate=True, first_downrate_iteration=20)),
+                          'momentum': (MomentumOptimizer, {})}[optimizer]
+            opt = cls('obj', output_folder=self.output_folder, distribution_mode=self.distribution_mode,
+                      options_dict=dict(step_size=self.learning_rate, **extra))
+        elif optimizer in ('curveball', 'cg', 'scipy'):
+            raise NotImplementedError("optimizer '%s' is outside the accelerated path" % optimizer)
+        else:
+            raise ValueError('Invalid optimizer type. Must be "gd" or "adam" or "cg" or "scipy".')
+        opt.set_index_in_grad_return(0)
+        self.opt = opt
+        self.fused = type(opt) in (AdamOptimizer, GDOptimizer, MomentumOptimizer)
+        _not_implemented(not self.fused and self.n_ranks > 1, 'user-defined object optimizers with more than one rank')
+        self.opt_kind = 'adam' if isinstance(opt, AdamOptimizer) else ('momentum' if isinstance(opt, MomentumOptimizer) else 'gd')
 
-    # ---- seed (ptychography.py:410-412) ---------------------------------------------------------------
-    seed = comm.bcast_object(int(time.time() / 60), root=0)
-    np.random.seed(seed)
+        self.ops = self.ops or HipOps(ctx)
+        state = self.state = DataParallelObject(self.ops, comm, [*obj_size, 2], n_moments={'adam': 2, 'momentum': 1, 'gd': 0}[self.opt_kind])
+        if self.fused:
+            if self.opt_kind == 'adam':
+                opt.params_whole_array_dict = {'m': state.moments[0], 'v': state.moments[1]}   # shard-sized under DP
+            elif self.opt_kind == 'momentum':
+                opt.params_whole_array_dict = {'v': state.moments[0]}
+        else:
+            opt.create_container([*obj_size, 2], self.use_checkpoint, ctx)
+        obj = self.obj = ObjectFunction([*obj_size, 2], distribution_mode=self.distribution_mode, output_folder=self.output_folder,
+                                        ds_level=self.ds_level, object_type=self.object_type, device=ctx)
+        init = ObjectFunction.initial_values(obj_size, self.initial_guess, self.random_guess_means_sigmas, self.object_type,
+                                             self.non_negativity, unknown_type=self.unknown_type)
+        init = comm.bcast_object(init, root=0) if (self.initial_guess is None and self.n_ranks > 1) else init
+        obj.arr = state.obj.view(0, (*obj_size, 2))
+        obj.arr.set(init)
+        del init
+        self._resume()
+        self.gradient = Gradient(obj)
+        self.gradient.arr = state.grad.view(0, (*obj_size, 2))
 
-    # ---- object optimiser (ptychography.py:417-453) -----------------------------------------------------
-    if isinstance(optimizer, Optimizer):
-        opt = optimizer
-        opt.name = 'obj'
-    elif optimizer == 'adam':
-        opt = AdamOptimizer('obj', output_folder=output_folder, distribution_mode=distribution_mode,
-                            options_dict={'step_size': learning_rate})
-    elif optimizer == 'gd':
-        opt = GDOptimizer('obj', output_folder=output_folder, distribution_mode=distribution_mode,
-                          options_dict={'step_size': learning_rate, 'dynamic_rate': True, 'first_downrate_iteration': 20})
-    elif optimizer == 'momentum':
-        opt = MomentumOptimizer('obj', output_folder=output_folder, distribution_mode=distribution_mode,
-                                options_dict={'step_size': learning_rate})
-    elif optimizer in ('curveball', 'cg', 'scipy'):
-        raise NotImplementedError("optimizer '%s' is outside the accelerated path" % optimizer)
-    else:
-        raise ValueError('Invalid optimizer type. Must be "gd" or "adam" or "cg" or "scipy".')
-    opt.set_index_in_grad_return(0)
-    fused = type(opt) in (AdamOptimizer, GDOptimizer, MomentumOptimizer)
-    _not_implemented(not fused and n_ranks > 1, 'user-defined object optimizers with more than one rank')
-    opt_kind = 'adam' if isinstance(opt, AdamOptimizer) else ('momentum' if isinstance(opt, MomentumOptimizer) else 'gd')
-
-    # ---- object, gradient, moments (ptychography.py:492-576) --------------------------------------------
-    ops = kwargs.pop('ops', None) or HipOps(ctx)
-    state = DataParallelObject(ops, comm, [*this_obj_size, 2], n_moments={'adam': 2, 'momentum': 1, 'gd': 0}[opt_kind])
-    if fused:
-        if opt_kind == 'adam':
-            opt.params_whole_array_dict = {'m': state.moments[0], 'v': state.moments[1]}   # shard-sized under DP
-        elif opt_kind == 'momentum':
-            opt.params_whole_array_dict = {'v': state.moments[0]}
-    else:
-        opt.create_container([*this_obj_size, 2], use_checkpoint, ctx)
-    obj = ObjectFunction([*this_obj_size, 2], distribution_mode=distribution_mode, output_folder=output_folder, ds_level=ds_level,
-                         object_type=object_type, device=ctx)
-    init = ObjectFunction.initial_values(this_obj_size, initial_guess, random_guess_means_sigmas, object_type, non_negativity,
-                                         unknown_type=unknown_type)
-    init = comm.bcast_object(init, root=0) if (initial_guess is None and n_ranks > 1) else init
-    obj.arr = state.obj.view(0, (*this_obj_size, 2))
-    obj.arr.set(init)
-    del init
-    # ---- checkpoint restore (ptychography.py:458-487) ----
-    # Read into temporaries, agree across ranks, then commit: either every rank resumes from the same (epoch, batch) or
-    # none does (the reference broadcasts rank 0's counters, :485-487).  The other optimisable parameters of the
-    # checkpoint (probe, position corrections, distances, affine matrices) are applied once they exist, further down.
-    starting_epoch, starting_batch = 0, 0
-    restored_params = None
-    if use_checkpoint:
+    def _resume(self):
+        """Checkpoint restore (ptychography.py:458-487).  Read into temporaries, agree across ranks, then commit: either every rank
+        resumes from the same (epoch, batch) or none does (the reference broadcasts rank 0's counters, :485-487).  The other
+        optimisable parameters of the checkpoint (probe, position corrections, distances, affine matrices) are applied once they
+        exist (create_probe_and_small_params)."""
+        comm, n_ranks, state = self.comm, self.n_ranks, self.state
+        self.starting_epoch, self.starting_batch = 0, 0
+        self.restored_params = None
+        if not self.use_checkpoint:
+            return
         loaded, why = None, ''
         try:
-            loaded = restore_checkpoint(output_folder, len(state.moments), rank=rank, n_ranks=n_ranks,
-                                        obj_shape=(*this_obj_size, 2), shard_size=state.per)
+            loaded = restore_checkpoint(self.output_folder, len(state.moments), rank=self.rank, n_ranks=n_ranks,
+                                        obj_shape=(*self.obj_size, 2), shard_size=state.per)
         except Exception as e:       # missing / partial / mismatching checkpoint
             why = repr(e)
         all_ok = comm.sum_over_ranks(1.0 if loaded is not None else 0.0) >= n_ranks
@@ -545,603 +573,575 @@ def reconstruct_ptychography(
             counters = comm.bcast_object((loaded[0], loaded[1]), root=0)
             all_ok = comm.sum_over_ranks(1.0 if counters == (loaded[0], loaded[1]) else 0.0) >= n_ranks
         if all_ok:
-            starting_epoch, starting_batch, obj_arr, mom, restored_params = loaded
-            obj.arr.set(obj_arr)
+            self.starting_epoch, self.starting_batch, obj_arr, mom, self.restored_params = loaded
+            self.obj.arr.set(obj_arr)
             for k_, m_ in enumerate(state.moments):
                 m_.set(np.ascontiguousarray(mom[k_]).reshape(-1)[:m_.size] if n_ranks == 1 else mom[k_])
-            print_flush('Resuming from checkpoint: epoch {}, batch {}.'.format(starting_epoch, starting_batch), sto_rank, rank,
-                        **stdout_options)
+            self.log('Resuming from checkpoint: epoch {}, batch {}.'.format(self.starting_epoch, self.starting_batch))
         else:
             msg = 'Checkpoint not used ({}); starting from epoch 0.'.format(why or 'another rank could not restore, or the ranks disagree')
-            if force_to_use_checkpoint:
+            if self.force_to_use_checkpoint:
                 raise RuntimeError(msg)
-            print_flush(msg, sto_rank, rank, **stdout_options)
-    gradient = Gradient(obj)
-    gradient.arr = state.grad.view(0, (*this_obj_size, 2))
+            self.log(msg)
 
-    # ---- forward model (ptychography.py:526-546) ---------------------------------------------------------
-    common_vars = dict(unknown_type=unknown_type, normalize_fft=normalize_fft, sign_convention=sign_convention,
-                       rotate_out_of_loop=rotate_out_of_loop, scale_ri_by_k=scale_ri_by_k, is_minus_logged=is_minus_logged,
-                       forward_algorithm=forward_algorithm, stdout_options=stdout_options, poisson_multiplier=poisson_multiplier,
-                       common_probe_pos=common_probe_pos, binning=binning, prj=prj, engine=engine, holo_engine=holo_engine, tile_engine=tile_engine,
-                       safe_zone_width=safe_zone_width, n_dp_batch=n_dp_batch,
-                       optimize_prj_affine=optimize_prj_affine, optimize_free_prop=optimize_free_prop, optimize_ctf_lg_kappa=optimize_ctf_lg_kappa,
-                       rotation_tables=rotation_tables, two_d_mode=two_d_mode, theta_downsample=theta_downsample,
-                       ds_level=ds_level, probe_size=probe_size, this_obj_size=this_obj_size, n_theta=n_theta,
-                       theta_ls=theta_ls, energy_ev=energy_ev, psize_cm=psize_cm, h=h, free_prop_cm=free_prop_cm,
-                       minibatch_size=minibatch_size, n_probe_modes=n_probe_modes, beamstop=beamstop,
-                       optimize_probe_defocusing=False, optimize_probe_pos_offset=False, optimize_prj_pos_offset=False,
-                       optimize_all_probe_pos=optimize_all_probe_pos, optimize_tilt=False, output_folder=output_folder, debug=debug)
-    fm_args = dict(loss_function_type=loss_function_type, distribution_mode=distribution_mode, device=ctx,
-                   common_vars_dict=common_vars, raw_data_type=raw_data_type, run_bfloat16=run_bfloat16, run_float64=run_float64)
-    if forward_model == 'auto':
-        forward_model = MultiDistModel(**fm_args) if is_multi_dist else PtychographyModel(**fm_args)
-    else:
-        forward_model = forward_model(**fm_args)
-    builtin_model = type(forward_model) in (PtychographyModel, MultiDistModel)
-    rool = bool(rotate_out_of_loop) and not two_d_mode and not is_multi_dist
-    if rool:
-        _not_implemented(not isinstance(forward_model, PtychographyModel), 'rotate_out_of_loop with a user-defined forward model')
-        fuse_per_angle = False
-    if is_multi_dist:
-        # (the multi-distance models evaluate one reference minibatch per call: their loss is a mean over distances x tiles, and
-        # 'per angle' adds the minibatches' gradients -- a fused call would average over all of them instead)
-        fuse_per_angle = False
-    print_flush('Forward model: {}.'.format(type(forward_model).__name__), sto_rank, rank, **stdout_options)
+    def create_forward_model(self):
+        """Forward model (ptychography.py:526-546), regularisers, finite support mask and constraint flags."""
+        ctx, unknown_type = self.ctx, self.unknown_type
+        common_vars = dict(unknown_type=unknown_type, normalize_fft=self.normalize_fft, sign_convention=self.sign_convention,
+                           rotate_out_of_loop=self.rotate_out_of_loop, scale_ri_by_k=self.scale_ri_by_k, is_minus_logged=self.is_minus_logged,
+                           forward_algorithm=self.forward_algorithm, stdout_options=self.stdout_options, poisson_multiplier=self.poisson_multiplier,
+                           common_probe_pos=self.common_probe_pos, binning=self.binning, prj=self.prj, engine=self.engine,
+                           holo_engine=self.holo_engine, tile_engine=self.tile_engine, safe_zone_width=self.safe_zone_width,
+                           n_dp_batch=self.n_dp_batch, optimize_prj_affine=self.optimize_prj_affine, optimize_free_prop=self.optimize_free_prop,
+                           optimize_ctf_lg_kappa=self.optimize_ctf_lg_kappa, rotation_tables=self.rotation_tables, two_d_mode=self.two_d_mode,
+                           theta_downsample=self.theta_downsample, ds_level=self.ds_level, probe_size=self.probe_size,
+                           this_obj_size=self.obj_size, n_theta=self.n_theta, theta_ls=self.theta_ls, energy_ev=self.energy_ev,
+                           psize_cm=self.psize_cm, h=self.h, free_prop_cm=self.free_prop_cm, minibatch_size=self.minibatch_size,
+                           n_probe_modes=self.n_probe_modes, beamstop=self.beamstop, optimize_probe_defocusing=False,
+                           optimize_probe_pos_offset=False, optimize_prj_pos_offset=False, optimize_all_probe_pos=self.optimize_all_probe_pos,
+                           optimize_tilt=False, output_folder=self.output_folder, debug=self.debug)
+        fm_args = dict(loss_function_type=self.loss_function_type, distribution_mode=self.distribution_mode, device=ctx,
+                       common_vars_dict=common_vars, raw_data_type=self.raw_data_type, run_bfloat16=self.run_bfloat16,
+                       run_float64=self.run_float64)
+        if self.forward_model == 'auto':
+            self.forward_model = MultiDistModel(**fm_args) if self.is_multi_dist else PtychographyModel(**fm_args)
+        else:
+            self.forward_model = self.forward_model(**fm_args)
+        fm = self.forward_model
+        self.builtin_model = type(fm) in (PtychographyModel, MultiDistModel)
+        self.rool = bool(self.rotate_out_of_loop) and not self.two_d_mode and not self.is_multi_dist
+        if self.rool:
+            _not_implemented(not isinstance(fm, PtychographyModel), 'rotate_out_of_loop with a user-defined forward model')
+            self.fuse_per_angle = False
+        if self.is_multi_dist:
+            # (the multi-distance models evaluate one reference minibatch per call: their loss is a mean over distances x tiles, and
+            # 'per angle' adds the minibatches' gradients -- a fused call would average over all of them instead)
+            self.fuse_per_angle = False
+        self.log('Forward model: {}.'.format(type(fm).__name__))
 
-    if regularizers is None:
-        regularizers = []
-        if alpha_d not in [0, None]:
-            if reweighted_l1:
-                regularizers.append(ReweightedL1Regularizer(alpha_d, alpha_b, unknown_type=unknown_type))
+        regularizers = self.regularizers
+        if regularizers is None:
+            regularizers = []
+            if self.alpha_d not in [0, None]:
+                rl1 = ReweightedL1Regularizer if self.reweighted_l1 else L1Regularizer
+                regularizers.append(rl1(self.alpha_d, self.alpha_b, unknown_type=unknown_type))
+            if self.gamma not in [0, None]:
+                regularizers.append(TVRegularizer(self.gamma, unknown_type=unknown_type))
+        fm.add_regularizers(regularizers)
+        self.reg_rwl1 = None
+        for r_ in regularizers:
+            if isinstance(r_, ReweightedL1Regularizer):
+                self.reg_rwl1 = r_
+                self.rwl1_weight = ctx.empty((*self.obj_size, 2))
+                self.rwl1_scratch = ctx.empty((2 * 1024 + 2,))
+
+        self.mask = None
+        if self.finite_support_mask_path is not None:
+            self.mask = Mask(self.obj_size, self.finite_support_mask_path, distribution_mode=self.distribution_mode,
+                             output_folder=self.output_folder, ds_level=self.ds_level, device=ctx)
+            mask_arr = self.finite_support_mask_path if isinstance(self.finite_support_mask_path, np.ndarray) else read_tiff(self.finite_support_mask_path)
+            self.mask.initialize_array_with_values(mask_arr, device=ctx)
+        self.flags = constraint_flags(self.non_negativity and unknown_type == 'delta_beta', self.object_type)   # (ptychography.py:1138)
+
+    def create_probe_and_small_params(self):
+        """The probe (ptychography.py:607-667), the optimisable parameters and the optimisers of the small ones (:673-735), the
+        checkpoint's values of them (load_params_checkpoint, :462), and the gradient's argument list."""
+        ctx, comm, n_probe_modes = self.ctx, self.comm, self.n_probe_modes
+        if self.rank == 0:
+            pk = dict(self.kwargs)
+            pk.update(lmbda_nm=self.lmbda_nm, psize_cm=self.psize_cm, normalize_fft=self.normalize_fft, n_probe_modes=n_probe_modes)
+            pk.pop('raw_data_type', None)
+            pr0, pi0 = initialize_probe(self.probe_size, self.probe_type, pupil_function=self.pupil_function, probe_initial=self.probe_initial,
+                                        rescale_intensity=self.rescale_probe_intensity, extra_defocus_cm=self.probe_extra_defocus_cm,
+                                        sign_convention=self.sign_convention, raw_data_type=self.raw_data_type,
+                                        data_first_angle=np.asarray(self.prj[0:1]) if self.rescale_probe_intensity else None,
+                                        data_all=self.prj if self.probe_type == 'ifft' else None, **pk)
+            if n_probe_modes == 1:
+                probe_real = np.stack([np.squeeze(pr0)]) if pr0.ndim != 3 else pr0[:1]
+                probe_imag = np.stack([np.squeeze(pi0)]) if pi0.ndim != 3 else pi0[:1]
+            elif pr0.ndim == 3 and len(pr0) > 1:
+                probe_real, probe_imag = pr0[:n_probe_modes], pi0[:n_probe_modes]
+                if len(probe_real) != n_probe_modes:
+                    raise RuntimeError('Length of supplied supplied probe does not match number of probe modes.')
             else:
-                regularizers.append(L1Regularizer(alpha_d, alpha_b, unknown_type=unknown_type))
-        if gamma not in [0, None]:
-            regularizers.append(TVRegularizer(gamma, unknown_type=unknown_type))
-    forward_model.add_regularizers(regularizers)
-    reg_rwl1 = None
-    for r_ in regularizers:
-        if isinstance(r_, ReweightedL1Regularizer):
-            reg_rwl1 = r_
-            rwl1_weight = ctx.empty((*this_obj_size, 2))
-            rwl1_scratch = ctx.empty((2 * 1024 + 2,))
-
-    mask = None
-    if finite_support_mask_path is not None:
-        mask = Mask(this_obj_size, finite_support_mask_path, distribution_mode=distribution_mode, output_folder=output_folder,
-                    ds_level=ds_level, device=ctx)
-        mask_arr = finite_support_mask_path if isinstance(finite_support_mask_path, np.ndarray) else read_tiff(finite_support_mask_path)
-        mask.initialize_array_with_values(mask_arr, device=ctx)
-    flags = constraint_flags(non_negativity and unknown_type == 'delta_beta', object_type)   # (ptychography.py:1138)
-
-    # ---- probe (ptychography.py:607-667) -------------------------------------------------------------------
-    if rank == 0:
-        pk = dict(kwargs)
-        pk.update(lmbda_nm=lmbda_nm, psize_cm=psize_cm, normalize_fft=normalize_fft, n_probe_modes=n_probe_modes)
-        pk.pop('raw_data_type', None)
-        pr0, pi0 = initialize_probe(probe_size, probe_type, pupil_function=pupil_function, probe_initial=probe_initial,
-                                    rescale_intensity=rescale_probe_intensity, extra_defocus_cm=probe_extra_defocus_cm,
-                                    sign_convention=sign_convention, raw_data_type=raw_data_type,
-                                    data_first_angle=np.asarray(prj[0:1]) if rescale_probe_intensity else None,
-                                    data_all=prj if probe_type == 'ifft' else None, **pk)
-        if n_probe_modes == 1:
-            probe_real = np.stack([np.squeeze(pr0)]) if pr0.ndim != 3 else pr0[:1]
-            probe_imag = np.stack([np.squeeze(pi0)]) if pi0.ndim != 3 else pi0[:1]
-        elif pr0.ndim == 3 and len(pr0) > 1:
-            probe_real, probe_imag = pr0[:n_probe_modes], pi0[:n_probe_modes]
-            if len(probe_real) != n_probe_modes:
-                raise RuntimeError('Length of supplied supplied probe does not match number of probe modes.')
+                # a single supplied / generated probe is spread over the modes with 20 % Gaussian jitter (ptychography.py:641-659)
+                pr0, pi0 = np.squeeze(pr0), np.squeeze(pi0)
+                probe_real, probe_imag = [], []
+                for i_mode in range(n_probe_modes):
+                    probe_real.append(np.random.normal(pr0, abs(pr0) * 0.2))
+                    probe_imag.append(np.random.normal(pi0, abs(pi0) * 0.2))
+                probe_real, probe_imag = np.stack(probe_real), np.stack(probe_imag)
         else:
-            # a single supplied / generated probe is spread over the modes with 20 % Gaussian jitter (ptychography.py:641-659)
-            pr0, pi0 = np.squeeze(pr0), np.squeeze(pi0)
-            probe_real, probe_imag = [], []
-            for i_mode in range(n_probe_modes):
-                probe_real.append(np.random.normal(pr0, abs(pr0) * 0.2))
-                probe_imag.append(np.random.normal(pi0, abs(pi0) * 0.2))
-            probe_real, probe_imag = np.stack(probe_real), np.stack(probe_imag)
-    else:
-        probe_real = probe_imag = None
-    probe_real = comm.bcast_object(probe_real, root=0)
-    probe_imag = comm.bcast_object(probe_imag, root=0)
-    probe_dev = ctx.array(np.stack([probe_real, probe_imag], -1), np.float32)       # [modes, Py, Px, 2]
+            probe_real = probe_imag = None
+        probe_real = comm.bcast_object(probe_real, root=0)
+        probe_imag = comm.bcast_object(probe_imag, root=0)
+        self.probe_dev = ctx.array(np.stack([probe_real, probe_imag], -1), np.float32)       # [modes, Py, Px, 2]
 
-    # ---- optimisable parameters and their optimisers (ptychography.py:673-735) -------------------------------
-    optimizable_params = {'probe_real': probe_dev, 'probe_imag': None, 'probe_defocus_mm': 0.0,
-                          'probe_pos_offset': np.zeros([n_theta, 2]), 'prj_pos_offset': np.zeros([n_theta, 2]),
-                          'probe_pos_correction': np.tile(probe_pos - probe_pos_int, [n_theta, 1, 1]),
-                          'tilt_ls': np.zeros([3, n_theta])}
-    opt_ls = [opt]
-    opt_args_ls = [0]
-    opt_probe = None
-    if optimize_probe:
-        if optimizer_probe is not None:
-            opt_probe = optimizer_probe
-            opt_probe.name = 'probe'
-        else:
-            opt_probe = AdamOptimizer('probe', output_folder=output_folder, options_dict={'step_size': probe_learning_rate},
-                                      forward_model=forward_model)
-        opt_probe.create_param_arrays([n_probe_modes, *probe_size, 2], device=ctx)
-        opt_probe.set_index_in_grad_return(len(opt_args_ls))
-        opt_args_ls = opt_args_ls + [forward_model.get_argument_index('probe_real'), forward_model.get_argument_index('probe_imag')]
-        opt_ls.append(opt_probe)
-        probe_grad_dev = ctx.zeros(probe_dev.shape)
+        n_theta = self.n_theta
+        params = self.optimizable_params = {
+            'probe_real': self.probe_dev, 'probe_imag': None, 'probe_defocus_mm': 0.0, 'probe_pos_offset': np.zeros([n_theta, 2]),
+            'prj_pos_offset': np.zeros([n_theta, 2]), 'probe_pos_correction': np.tile(self.probe_pos - self.probe_pos_int, [n_theta, 1, 1]),
+            'tilt_ls': np.zeros([3, n_theta])}
+        if self.is_multi_dist:
+            # ptychography.py:685-727, optimizers.py:905-943
+            params.update(probe_pos_correction=np.zeros([self.n_dists, 2]), free_prop_cm=self.free_prop_cm,
+                          safe_zone_width=self.safe_zone_width, ctf_lg_kappa=self.ctf_lg_kappa,
+                          prj_affine_ls=np.tile(np.array([[1., 0, 0], [0, 1., 0]]).reshape([1, 2, 3]), [self.n_dists, 1, 1]))
+        # The optimised ones, in the order of the gradient tuple; one entry each (+ its gradient in the forward model)
+        self.small, self.opt_args_ls = [], [0]
+        if self.optimize_probe:
+            self._add_small('probe_real', self.optimizer_probe, self.probe_learning_rate, name='probe', args=('probe_real', 'probe_imag'),
+                            delay=self.probe_update_delay, limit=np.inf if self.probe_update_limit is None else self.probe_update_limit)
+        if self.optimize_free_prop:
+            self._add_small('free_prop_cm', self.optimizer_free_prop, self.free_prop_learning_rate)
+        if self.optimize_prj_affine:
+            # (+ "regularize transformation of image 0": matrix 0 is pinned to the identity)
+            self._add_small('prj_affine_ls', self.optimizer_prj_affine, self.prj_affine_learning_rate,
+                            pin=ctx.array(np.array([[1., 0, 0], [0, 1., 0]]), np.float32))
+        if self.optimize_all_probe_pos:
+            # optimizers.py:877-889: Adam on probe_pos_correction [n_theta, n_pos, 2] (+ "prevent position drifting": subtract the
+            # mean over (theta, position))
+            self._add_small('probe_pos_correction', self.optimizer_all_probe_pos, self.all_probe_pos_learning_rate, center_cols=2)
 
-    opt_free_prop = opt_prj_affine = None
-    if is_multi_dist:
-        # ptychography.py:685-727, optimizers.py:905-943
-        optimizable_params['probe_pos_correction'] = np.zeros([n_dists, 2])
-        optimizable_params['free_prop_cm'] = ctx.array(free_prop_cm, np.float32) if optimize_free_prop else free_prop_cm
-        optimizable_params['safe_zone_width'] = safe_zone_width
-        optimizable_params['ctf_lg_kappa'] = ctf_lg_kappa
-        aff0 = np.tile(np.array([[1., 0, 0], [0, 1., 0]]).reshape([1, 2, 3]), [n_dists, 1, 1])
-        optimizable_params['prj_affine_ls'] = ctx.array(aff0, np.float32) if optimize_prj_affine else aff0
-        if optimize_free_prop:
-            opt_free_prop = optimizer_free_prop if optimizer_free_prop is not None else \
-                AdamOptimizer('free_prop_cm', output_folder=output_folder, options_dict={'step_size': free_prop_learning_rate},
-                              forward_model=forward_model)
-            opt_free_prop.name = 'free_prop_cm'
-            opt_free_prop.create_param_arrays([n_dists], device=ctx)
-            opt_free_prop.set_index_in_grad_return(len(opt_args_ls))
-            opt_args_ls = opt_args_ls + [forward_model.get_argument_index('free_prop_cm')]
-            opt_ls.append(opt_free_prop)
-            free_prop_grad_dev = ctx.zeros([n_dists])
-        if optimize_prj_affine:
-            opt_prj_affine = optimizer_prj_affine if optimizer_prj_affine is not None else \
-                AdamOptimizer('prj_affine_ls', output_folder=output_folder, options_dict={'step_size': prj_affine_learning_rate},
-                              forward_model=forward_model)
-            opt_prj_affine.name = 'prj_affine_ls'
-            opt_prj_affine.create_param_arrays([n_dists, 2, 3], device=ctx)
-            opt_prj_affine.set_index_in_grad_return(len(opt_args_ls))
-            opt_args_ls = opt_args_ls + [forward_model.get_argument_index('prj_affine_ls')]
-            opt_ls.append(opt_prj_affine)
-            affine_grad_dev = ctx.zeros([n_dists, 2, 3])
-            affine_identity_dev = ctx.array(np.array([[1., 0, 0], [0, 1., 0]]), np.float32)
+        restored = self.restored_params
+        if restored is not None:
+            if 'probe_real' in restored and 'probe_imag' in restored:
+                pr_ = np.stack([np.asarray(restored['probe_real']), np.asarray(restored['probe_imag'])], -1)
+                if pr_.shape != self.probe_dev.shape:
+                    raise ValueError('checkpointed probe has shape %s, this run uses %s' % (pr_.shape[:-1], self.probe_dev.shape[:-1]))
+                self.probe_dev.set(pr_.astype(np.float32))
+            for k_ in ('probe_pos_correction', 'free_prop_cm', 'prj_affine_ls', 'probe_defocus_mm', 'probe_pos_offset', 'prj_pos_offset',
+                       'tilt_ls'):
+                if k_ in restored and k_ in params:
+                    if hasattr(params[k_], 'set'):
+                        params[k_].set(np.asarray(restored[k_], dtype=np.float32).reshape(params[k_].shape))
+                    else:
+                        params[k_] = restored[k_]
 
-    opt_probe_pos = None
-    if optimize_all_probe_pos:
-        # optimizers.py:877-889: Adam on probe_pos_correction [n_theta, n_pos, 2], kept on the device
-        if optimizer_all_probe_pos is not None:
-            opt_probe_pos = optimizer_all_probe_pos
-            opt_probe_pos.name = 'probe_pos_correction'
-        else:
-            opt_probe_pos = AdamOptimizer('probe_pos_correction', output_folder=output_folder,
-                                          options_dict={'step_size': all_probe_pos_learning_rate}, forward_model=forward_model)
-        corr_shape = list(optimizable_params['probe_pos_correction'].shape)
-        optimizable_params['probe_pos_correction'] = ctx.array(optimizable_params['probe_pos_correction'], np.float32)
-        opt_probe_pos.create_param_arrays(corr_shape, device=ctx)
-        opt_probe_pos.set_index_in_grad_return(len(opt_args_ls))
-        opt_args_ls = opt_args_ls + [forward_model.get_argument_index('probe_pos_correction')]
-        opt_ls.append(opt_probe_pos)
-        pos_grad_dev = ctx.zeros(corr_shape)
+        self.diff = Differentiator()
+        self.diff.create_loss_node(self.forward_model.get_loss_function(), self.opt_args_ls)
 
-    # ---- the checkpoint's other parameters (load_params_checkpoint, adorym/ptychography.py:462) ----
-    def params_to_host():
-        """optimizable_params under the reference's keys, as host arrays (what the reference pickles into params_{rank})."""
-        pa_ = probe_dev.get()
+    def _add_small(self, key, user_opt, learning_rate, name=None, args=None, delay=None, limit=np.inf, **extras):
+        """Optimise optimizable_params[key] (moved to the device): the user's optimiser or Adam, its moments, its gradient accumulator
+        and its place in the gradient tuple (the probe takes two: probe_real, probe_imag)."""
+        name = name or key
+        opt = user_opt if user_opt is not None else \
+            AdamOptimizer(name, output_folder=self.output_folder, options_dict={'step_size': learning_rate}, forward_model=self.forward_model)
+        opt.name = name
+        x = self.optimizable_params[key]
+        if not isinstance(x, DeviceArray):
+            x = self.optimizable_params[key] = self.ctx.array(x, np.float32)
+        opt.create_param_arrays(list(x.shape), device=self.ctx)
+        opt.set_index_in_grad_return(len(self.opt_args_ls))
+        self.opt_args_ls += [self.forward_model.get_argument_index(a) for a in args or (key,)]
+        self.small.append(_SmallParam(key, opt, x, opt.index_in_grad_returns, self.other_params_update_delay if delay is None else delay,
+                                      limit, **extras))
+
+    def _params_to_host(self):
+        """optimizable_params under the reference's keys, as host arrays (pickled whole into params_{rank}, misc.py:179-194)."""
+        pa_ = self.probe_dev.get()
         out_ = {'probe_real': pa_[..., 0], 'probe_imag': pa_[..., 1]}
-        for k_, v_ in optimizable_params.items():
-            if k_ in ('probe_real', 'probe_imag'):
-                continue
-            out_[k_] = v_.get() if hasattr(v_, 'get') else v_
+        for k_, v_ in self.optimizable_params.items():
+            if k_ not in out_:
+                out_[k_] = _host(v_)
         return out_
 
-    if restored_params is not None:
-        if 'probe_real' in restored_params and 'probe_imag' in restored_params:
-            pr_ = np.stack([np.asarray(restored_params['probe_real']), np.asarray(restored_params['probe_imag'])], -1)
-            if pr_.shape != probe_dev.shape:
-                raise ValueError('checkpointed probe has shape %s, this run uses %s' % (pr_.shape[:-1], probe_dev.shape[:-1]))
-            probe_dev.set(pr_.astype(np.float32))
-        for k_ in ('probe_pos_correction', 'free_prop_cm', 'prj_affine_ls', 'probe_defocus_mm', 'probe_pos_offset', 'prj_pos_offset',
-                   'tilt_ls'):
-            if k_ in restored_params and k_ in optimizable_params:
-                cur_ = optimizable_params[k_]
-                if hasattr(cur_, 'set'):
-                    cur_.set(np.asarray(restored_params[k_], dtype=np.float32).reshape(cur_.shape))
-                else:
-                    optimizable_params[k_] = restored_params[k_]
+    def run_epochs(self):
+        """The convergence log and summary.txt, then the epoch loop (ptychography.py:783-1295) with the outputs of every epoch."""
+        rank, output_folder = self.rank, self.output_folder
+        if rank == 0:
+            os.makedirs(os.path.join(output_folder, 'convergence'), exist_ok=True)
+        self.comm.barrier()
+        self.f_conv = open(os.path.join(output_folder, 'convergence', 'loss_rank_{}.txt'.format(rank)), 'w')
+        self.f_conv.write('i_epoch,i_batch,loss,time\n')
+        if rank == 0:       # adorym/ptychography.py:776 -> misc.py:149-176
+            create_summary(output_folder, dict(self.call_args, output_folder=output_folder, probe_size=list(self.probe_size),
+                                               n_theta=self.n_theta, obj_size=list(self.obj_size)), verbose=False)
+        self.log('Optimizer started.')
+        self.loss_history = []
+        self.ckpt_thread = self.pending_log = None
+        self.straddle_warned = False
+        # Footprint-restricted gradient exchange (opt-in, ADM_RESTRICTED_EXCHANGE=1; DataParallelObject.exchange_and_update(touched=)):
+        # only the y-planes the global batch touches are summed over the ranks, the regulariser term -- identical on every rank -- is
+        # added R-fold by the shard owners.  Saves 1 - footprint/object of the reduce-scatter (58 % at 2 ranks, 20 % at 8 for
+        # config 3's scan); never run on real multi-GPU hardware, hence not the default.
+        self.restricted_exchange = (
+            os.environ.get('ADM_RESTRICTED_EXCHANGE', '0') == '1' and self.n_ranks > 1 and self.builtin_model and not self.is_multi_dist
+            and not self.rool and self.fused and self.optimize_object and self.unknown_type == 'delta_beta'
+            and not any(isinstance(r_, ReweightedL1Regularizer) for r_ in self.forward_model.reg_list)
+            and (self.update_scheme == 'immediate' or self.fuse_per_angle))
+        # A small object (2-D ptychography, holography: a few hundred thousand unknowns) on one rank, plain Adam, no constraint
+        # and no mask: its update is one more array of the ONE launch that updates the small parameters (same arithmetic --
+        # adam_value in adm_optim.h -- and same step counter) unless the fused holography launch has updated it; these paths are
+        # chains of 5-20 us kernels, where a launch saved is 5 % of a minibatch.
+        self.obj_with_small = (self.optimize_object and plain_adam([self.opt]) is not None and self.n_ranks == 1 and self.flags == 0
+                               and self.mask is None and self.state.n <= (1 << 22) and not self.restricted_exchange)
+        self.stage_next_targets = os.environ.get('ADM_STAGE_TARGETS', '1') == '1'
 
-    diff = Differentiator()
-    calculate_loss = forward_model.get_loss_function()
-    diff.create_loss_node(calculate_loss, opt_args_ls)
+        self.i_epoch = self.starting_epoch
+        while True:
+            t0 = time.time()
+            self.ind_list_rand = epoch_task_list(
+                self.i_epoch, self.n_theta, len(self.probe_pos), self.minibatch_size, self.n_ranks, update_scheme=self.update_scheme,
+                randomize_probe_pos=self.randomize_probe_pos,
+                fixed_theta=(int(np.nonzero(abs(self.theta_ls - self.theta_ls[0]) < 1e-5)[0][0]) if self.two_d_mode else None))
+            self.n_batch = len(self.ind_list_rand)
+            self.i_opt_batch = self.starting_epoch * self.n_batch + self.starting_batch     # (:848), re-evaluated every epoch like the reference
+            self.initialize_gradients = True
+            self.pending_ind = []
+            self.current_i_theta = -1                                                      # (:855)
+            self.zeroed_by_update = set()
+            for i_batch in range(self.starting_batch, self.n_batch):
+                self.starting_batch = 0
+                self.minibatch(i_batch)
+            self._flush_log()
+            self.state.finish_update()
+            last = self.n_epochs != 'auto' and self.i_epoch == self.n_epochs - 1
+            self.log('Epoch {} (rank {}); Delta-t = {} s; current time = {} s,'.format(self.i_epoch, rank, time.time() - t0,
+                                                                                        time.time() - self.t_zero))
+            self.i_epoch += 1
+            if rank == 0:       # outputs after an epoch (ptychography.py:1290-1294; util.py:1958-2028)
+                _write_images(output_folder, output_folder, '_ds_{}'.format(self.ds_level), self.obj.arr.get(), self.unknown_type,
+                              self.probe_dev.get(), complex_probe=True)
+            self.log('Current iteration finished.')
+            if last:
+                return
 
-    if rank == 0:
-        os.makedirs(os.path.join(output_folder, 'convergence'), exist_ok=True)
-    comm.barrier()
-    f_conv = open(os.path.join(output_folder, 'convergence', 'loss_rank_{}.txt'.format(rank)), 'w')
-    f_conv.write('i_epoch,i_batch,loss,time\n')
-    if rank == 0:       # adorym/ptychography.py:776 -> misc.py:149-176
-        create_summary(output_folder, dict(_call_args, output_folder=output_folder, probe_size=list(probe_size), n_theta=n_theta,
-                                           obj_size=list(this_obj_size)), verbose=False)
-    print_flush('Optimizer started.', sto_rank, rank, **stdout_options)
-    if probe_update_limit is None:
-        probe_update_limit = np.inf
-    loss_history = []
+    def minibatch(self, i_batch):
+        """Global batch ``i_batch`` of the epoch: checkpoint, look-ahead, gradient, object update, small-parameter update,
+        intermediate output, log."""
+        self._checkpoint(i_batch)
+        batch = self._start_batch(i_batch)
+        if batch is None:
+            return          # 'per angle': collected for the angle's one launch
+        this_i_theta, this_ind_batch, is_last_batch_of_this_theta, t00 = batch
+        # ---- reweighted-L1 weights, refreshed every 10 minibatches (ptychography.py:995-1000) ----
+        if self.reg_rwl1 is not None:
+            if i_batch % 10 == 0:
+                self.state.finish_update()
+                _lib.check(self.ctx.lib.adm_rwl1_update(self.engine.plan.handle, self.obj.arr.ptr, self.rwl1_weight.ptr, self.rwl1_scratch.ptr))
+            self.reg_rwl1.update_l1_weight(self.rwl1_weight)
+        self._look_ahead(i_batch, this_i_theta)
+        holo_fused = self._gradient(i_batch, this_i_theta, this_ind_batch)
+        if self.update_scheme == 'per angle' and not is_last_batch_of_this_theta:
+            self._flush_log()     # keeps at most one evaluation between a loss read-back and its use (two pinned slots)
+            return
+        self.initialize_gradients = True
+        obj_with_small = self._update_object(i_batch, holo_fused)
+        self._update_small_params(i_batch, obj_with_small, holo_fused)
 
-    # =========================================================================================================
-    # epoch loop (ptychography.py:783-1295)
-    # =========================================================================================================
-    cont = True
-    i_epoch = starting_epoch
-    _ckpt_thread = [None]
-    pending_log = [None]
-    straddle_warned = [False]
-    # Footprint-restricted gradient exchange (opt-in, ADM_RESTRICTED_EXCHANGE=1; DataParallelObject.exchange_and_update(touched=)):
-    # only the y-planes the global batch touches are summed over the ranks, the regulariser term -- identical on every rank -- is
-    # added R-fold by the shard owners.  Saves 1 - footprint/object of the reduce-scatter (58 % at 2 ranks, 20 % at 8 for
-    # config 3's scan); never run on real multi-GPU hardware, hence not the default.
-    from .regularizers import ReweightedL1Regularizer as _RW, combined_weights as _cw
-    restricted_exchange = (os.environ.get('ADM_RESTRICTED_EXCHANGE', '0') == '1' and n_ranks > 1 and builtin_model and not is_multi_dist
-                           and not rool and fused and optimize_object and unknown_type == 'delta_beta'
-                           and not any(isinstance(r_, _RW) for r_ in forward_model.reg_list)
-                           and (update_scheme == 'immediate' or fuse_per_angle))
+        # ---- intermediate output (ptychography.py:1231-1246; util.py:1958-2028, optimizers.py:1111-1160) ----
+        if self.save_intermediate and ((self.save_intermediate_level == 'epoch' and i_batch == self.n_batch - 1)
+                                       or self.save_intermediate_level == 'batch'):
+            # finish_update() may hold a deferred collective (the rest of the all-gather): every rank calls it (the
+            # condition is the same on all ranks)
+            if is_last_batch_of_this_theta:
+                self.state.finish_update()
+                if self.rank == 0:
+                    self._write_intermediate(i_batch)
+            self.comm.barrier()
 
-    stage_next_targets = os.environ.get('ADM_STAGE_TARGETS', '1') == '1'
+        # ---- finishing a batch (ptychography.py:1231-1271) ----
+        fm = self.forward_model
+        this_log = (self.i_epoch, i_batch, fm.take_loss_thunk() if self.builtin_model else (lambda v=fm.current_loss: v), t00)
+        self._flush_log()                     # the PREVIOUS minibatch: its loss is read after this one has been queued
+        self.pending_log = this_log
+        if self.optimizer_batch_number_increment == 'batch' or (self.optimizer_batch_number_increment == 'angle' and is_last_batch_of_this_theta):
+            self.i_opt_batch += 1
 
-    def _next_evaluation(i_b):
+    def _checkpoint(self, i_batch):
+        """Checkpoint (ptychography.py:879-895): device -> host copy here, file writes on a helper thread."""
+        if not (self.store_checkpoint and i_batch % self.n_batch_per_checkpoint == 0):
+            return
+        if self.ckpt_thread is not None:
+            self.ckpt_thread.join()
+        self.state.finish_update()
+        host_obj = self.obj.arr.get() if self.rank == 0 else None
+        host_mom = [m_.get() for m_ in self.state.moments] if (self.rank == 0 or self.n_ranks > 1) else []
+        self.ckpt_thread = threading.Thread(target=save_checkpoint, args=(self.i_epoch, i_batch, self.output_folder, host_obj, host_mom),
+                                            kwargs=dict(rank=self.rank, n_ranks=self.n_ranks, params=self._params_to_host()))
+        self.ckpt_thread.start()
+
+    def _start_batch(self, i_batch):
+        """Time limit, this rank's share of global batch ``i_batch`` and the rotate_out_of_loop rotation.  Returns (i_theta, position
+        indices, whether the batch is the last of its angle, start time), or None while 'per angle' collects an angle's batches."""
+        t_elapsed = (time.time() - self.t_zero) / 60
+        if self.t_max_min is not None and self.n_ranks > 1:
+            t_elapsed = self.comm.bcast_object(t_elapsed, root=0)     # one decision for all ranks: nobody is left in a collective
+        if self.t_max_min is not None and t_elapsed >= self.t_max_min:
+            self.log('Terminating program because maximum time limit is reached.')
+            sys.exit()
+        self.log('Epoch {}, batch {} of {} started.'.format(self.i_epoch, i_batch, self.n_batch))
+        t00 = time.time()
+        ind_list_rand = self.ind_list_rand
+        this_i_theta, this_ind_batch = rank_batch(ind_list_rand, i_batch, self.rank, self.minibatch_size, self.n_ranks)
+        # ONE decision for all ranks, taken on the angle the global batch starts with (rank 0's share).  The reference
+        # compares with each rank's own angle (adorym/ptychography.py:910): when a global batch straddles two angles its
+        # ranks then disagree, their optimiser counters i_opt_batch drift apart (:1266-1271) and the replicated objects
+        # stop being identical (golden F14 'immediate' records it; oracle.reconstruct(rank_local_counters=True) restates
+        # it).  Here the object is ONE sharded copy, so the step counter must be the same on every shard; the two rules
+        # coincide whenever no global batch straddles angles (always in 'per angle' mode).
+        is_last_batch_of_this_theta = i_batch == self.n_batch - 1 or ind_list_rand[i_batch + 1][0, 0] != ind_list_rand[i_batch][0, 0]
+        if self.n_ranks > 1 and self.rank == 0 and self.i_epoch == self.starting_epoch and not self.straddle_warned and \
+                len(np.unique(ind_list_rand[i_batch][:, 0])) > 1:
+            self.straddle_warned = True
+            self.log('  Note: this global batch holds positions of two angles.  adorym_amd keeps ONE optimiser step counter '
+                     'for the sharded object (decided on the angle the batch starts with); the reference keeps one per rank and '
+                     'its replicas drift apart in this case (INTEGRATION.md, "Deviations").  Use a position count that is a '
+                     'multiple of n_ranks * minibatch_size, or update_scheme="per angle", to reproduce a reference mpirun.')
+        self.log('  Current rank is processing angle ID {}.'.format(this_i_theta))
+
+        # 'per angle': the minibatches of one angle see the same object, so they are fused into ONE launch
+        # (identical sums; all CUs busy instead of `minibatch_size` of them).  The reference evaluates them
+        # one by one and only logs the last (ptychography.py:1095-1099 `continue`).
+        # ---- rotate_out_of_loop (ptychography.py:917-947): the object is rotated to the angle OUTSIDE the differentiated
+        # block, once per change of angle -- the minibatches of the same angle that follow an 'immediate' update keep seeing
+        # the object as it was rotated when the angle began, exactly like the reference ----
+        if self.rool and this_i_theta != self.current_i_theta:
+            self.state.finish_update()           # the whole object is read
+            self.forward_model.rotate_outside(self.obj.arr, this_i_theta)
+        self.current_i_theta = this_i_theta
+
+        if self.update_scheme == 'per angle' and self.fuse_per_angle:
+            self.pending_ind.append(this_ind_batch)
+            if not is_last_batch_of_this_theta:
+                return None
+            self.forward_model.batch_group = len(self.pending_ind)
+            this_ind_batch = np.concatenate(self.pending_ind)
+            self.pending_ind = []
+        return this_i_theta, this_ind_batch, is_last_batch_of_this_theta, t00
+
+    def _look_ahead(self, i_batch, this_i_theta):
+        """What the exchange and the next launches need before this minibatch's gradient is queued."""
+        ind_list_rand, n_ranks, minibatch_size, fm = self.ind_list_rand, self.n_ranks, self.minibatch_size, self.forward_model
+        # ---- footprint-restricted exchange: the planes the GLOBAL batch (all ranks) touches, the same on every rank ----
+        self.touched_planes = None
+        if self.restricted_exchange:
+            if self.update_scheme == 'per angle':
+                self.touched_planes = (0, self.obj_size[0])      # every position of the angle: the whole object
+            else:
+                gb_ = ind_list_rand[i_batch]
+                if len(gb_) < n_ranks * minibatch_size:     # (a short last batch was topped up from batch 0 by rank_batch)
+                    gb_ = np.concatenate([gb_, ind_list_rand[0][:n_ranks * minibatch_size - len(gb_)]])
+                self.touched_planes = self.engine.y_footprint(self.probe_pos_int[gb_[:, 1]])
+        fm.restricted_planes = self.touched_planes
+
+        # ---- the next angle's rotation data, one minibatch ahead: when the NEXT global batch starts a new angle, its lookup table
+        # is computed and uploaded now (host work while the GPU still runs the previous minibatch) and its adjoint CSR is built on
+        # the side stream beside this minibatch's multislice kernel.  Met cold, the first launch of an angle waited 2 - 2.5 ms for
+        # the host (table: NumPy + allocation; CSR: ~25 launches); the tables are kept for the whole reconstruction either way.
+        # (The table is computed TWO minibatches ahead, the CSR and -- for datasets small enough to live on the device -- the angle's
+        # measured data ONE ahead: the host is at most a minibatch ahead of the GPU and each of these costs it 1 - 2 ms.)
+        if self.builtin_model and not self.two_d_mode and not self.is_multi_dist and not self.rool:
+            def _angle_of(i_b):
+                nb_ = ind_list_rand[i_b]
+                return int(nb_[min(self.rank * minibatch_size, len(nb_) - 1), 0])
+            if i_batch + 2 < self.n_batch and _angle_of(i_batch + 2) != this_i_theta:
+                self.rotation_tables(_angle_of(i_batch + 2))
+            if i_batch + 1 < self.n_batch and _angle_of(i_batch + 1) != this_i_theta:
+                fm.prefetch_table = self.rotation_tables(_angle_of(i_batch + 1))
+                fm.prefetch_data(_angle_of(i_batch + 1))
+
+    def _next_evaluation(self, i_b):
         """(i_theta, position indices) of the evaluation that follows global batch ``i_b`` on this rank within the epoch, or None:
         the next minibatch ('immediate'), or all minibatches of the next angle as the fused 'per angle' launch takes them."""
+        ind_list_rand, n_batch = self.ind_list_rand, self.n_batch
         if i_b + 1 >= n_batch:
             return None
-        th, ind = rank_batch(ind_list_rand, i_b + 1, rank, minibatch_size, n_ranks)       # (tops up a short last batch now)
-        if not (update_scheme == 'per angle' and fuse_per_angle):
+        th, ind = rank_batch(ind_list_rand, i_b + 1, self.rank, self.minibatch_size, self.n_ranks)       # (tops up a short last batch now)
+        if not (self.update_scheme == 'per angle' and self.fuse_per_angle):
             return th, ind
         group, j = [ind], i_b + 2
         while j < n_batch and ind_list_rand[j][0, 0] == ind_list_rand[i_b + 1][0, 0]:
-            group.append(rank_batch(ind_list_rand, j, rank, minibatch_size, n_ranks)[1])
+            group.append(rank_batch(ind_list_rand, j, self.rank, self.minibatch_size, self.n_ranks)[1])
             j += 1
         return th, np.concatenate(group)
 
-    def flush_log():
-        if pending_log[0] is None:
-            return
-        e_, b_, thunk, t_start = pending_log[0]
-        pending_log[0] = None
-        current_loss = thunk()
-        loss_history.append(current_loss)
-        print_flush('Minibatch/angle done in {} s; loss (rank 0) is {}.'.format(time.time() - t_start, current_loss), sto_rank,
-                    rank, **stdout_options)
-        print_flush('Throughput: {} angles/sec'.format(minibatch_size / (time.time() - t_start)), sto_rank, rank, **stdout_options)
-        f_conv.write('{},{},{},{}\n'.format(e_, b_, current_loss, time.time() - t_zero))
-        f_conv.flush()
+    def _gradient(self, i_batch, this_i_theta, this_ind_batch):
+        """Gradients (ptychography.py:1017-1066): the object's into its buffer, the small parameters' added to their accumulators.
+        Returns the fused holography update's arguments when that launch has also updated them all, else None."""
+        ctx, state, fm = self.ctx, self.state, self.forward_model
+        t_grad_0 = time.time()
+        side_hook, init_grad = None, False
+        if self.initialize_gradients:
+            if self.builtin_model:
+                # queued by the model on the side stream after the rotation: the deferred part of the previous update,
+                # then the regulariser kernel in 'set' mode (or a zero fill) initialises the gradient buffer
+                side_hook, init_grad = state.finish_update, True
+            else:
+                state.zero_grad()
+            # (an accumulator that the last small-parameter update consumed was zero-filled by that launch)
+            for p in self.small:
+                if p.key not in self.zeroed_by_update:
+                    p.g.zero_()
+            self.zeroed_by_update = set()
+        given = {'obj': fm.arr_rot if self.rool else self.obj.arr,     # (:1009-1013)
+                 'this_i_theta': this_i_theta, 'this_pos_batch': self.probe_pos_int[this_ind_batch], 'this_ind_batch': this_ind_batch,
+                 'prj': self.prj}
+        grad_func_args = {arg: given[arg] if arg in given else self.optimizable_params[arg] for arg in fm.argument_ls}
+        fm.update_loss_args(grad_func_args)
+        holo_fused = self._holo_fused(i_batch, init_grad)
+        if self.is_multi_dist and self.builtin_model:
+            fm.fused_adam = holo_fused
+        # which measured data the NEXT evaluation needs, so that the model can send them to the device beside this one's launch
+        # (streamed datasets; resident ones are views of device arrays already)
+        if self.builtin_model and not self.is_multi_dist and self.stage_next_targets:
+            fm.next_batch = self._next_evaluation(i_batch)
+        grads = self.diff.get_gradients(_accumulate_into=self.gradient.arr, _side_hook=side_hook, _init_grad=init_grad, **grad_func_args)
+        self.log('  Gradient calculation done in {} s.'.format(time.time() - t_grad_0))
+        self.initialize_gradients = False
+        if self.rool:
+            # (:1066-1078) the gradient buffer is in the rotated frame: resample it with the -theta table, after EVERY
+            # minibatch and on everything accumulated so far.  In 'per angle' mode earlier contributions are therefore
+            # resampled again (the reference's TODO at :1075 says they should not be); kept literally -- golden F15
+            # pins it -- and the minibatches of an angle are not fused into one launch in this mode for that reason.
+            fm.resample_gradient(self.gradient.arr, this_i_theta)
+        if holo_fused is not None:
+            for o_ in holo_fused['opts']:
+                o_.i_batch += 1
+            return holo_fused
+        for p in self.small:
+            g_ = grads[p.i_grad]            # (the probe's: interleaved (real, imag))
+            _lib.check(ctx.lib.adm_axpy(ctx.handle, p.g.ptr, g_.ptr, 1.0, g_.size))
+        return None
 
-    while cont:
-        t0 = time.time()
-        n_tot_per_batch = minibatch_size * n_ranks
-        ind_list_rand = epoch_task_list(i_epoch, n_theta, len(probe_pos), minibatch_size, n_ranks, update_scheme=update_scheme,
-                                        randomize_probe_pos=randomize_probe_pos,
-                                        fixed_theta=(int(np.nonzero(abs(theta_ls - theta_ls[0]) < 1e-5)[0][0]) if two_d_mode else None))
-        n_batch = len(ind_list_rand)
-        i_opt_batch = starting_epoch * n_batch + starting_batch      # (:848), re-evaluated every epoch like the reference
-        initialize_gradients = True
-        pending_ind = []
-        current_i_theta = -1                                         # (:855)
-        zeroed_by_update = set()
+    def _holo_fused(self, i_batch, init_grad):
+        """Multi-distance holography whose update is exactly "Adam on what this minibatch's gradients say" -- one rank, an update per
+        minibatch, no regulariser, constraint or mask on the object, plain Adam with common (b1, b2, eps) on the object and on
+        whichever of free_prop_cm / prj_affine_ls are optimised: the steps run INSIDE the gradient launch group's last kernel
+        (adm_holo_fwd_adj_adam; same arithmetic, same bits), no gradient is stored and no optimiser launch follows."""
+        if not (self.is_multi_dist and not self.holo_tiled and self.builtin_model and init_grad and self.update_scheme == 'immediate'
+                and self.optimize_object and self.n_ranks == 1 and self.flags == 0 and self.mask is None
+                and all(p.key in _HOLO_FUSED_SLOTS for p in self.small) and not self.forward_model.reg_list
+                and os.environ.get('ADM_HOLO_FUSED_ADAM', '1') == '1'):
+            return None
+        betas = plain_adam([self.opt] + [p.opt for p in self.small])
+        if betas is None:
+            return None
+        holo_fused = dict(obj_mv=(self.state.moments[0], self.state.moments[1]), step_obj=float(self.opt.options_dict.get('step_size', 0.001)),
+                          i_batch=self.i_opt_batch, b1=betas[0], b2=betas[1], eps=betas[2], dists=None, affine=None, pin=None, opts=[self.opt])
+        for p in self.small:
+            if p.due(i_batch + self.i_epoch * self.n_batch):
+                o_, slot = p.opt, _HOLO_FUSED_SLOTS[p.key]
+                holo_fused[slot] = (o_.params_whole_array_dict['m'], o_.params_whole_array_dict['v'], float(o_.options_dict.get('step_size', 0.001)))
+                if slot == 'affine':
+                    holo_fused['pin'] = p.extras['pin']
+                holo_fused['opts'].append(o_)
+        self.state.finish_update()
+        return holo_fused
 
-        for i_batch in range(starting_batch, n_batch):
-            starting_batch = 0
-            # ---- checkpoint (ptychography.py:879-895): device -> host copy here, file writes on a helper thread ----
-            if store_checkpoint and i_batch % n_batch_per_checkpoint == 0:
-                import threading
-                if _ckpt_thread[0] is not None:
-                    _ckpt_thread[0].join()
-                state.finish_update()
-                host_obj = obj.arr.get() if rank == 0 else None
-                host_mom = [m_.get() for m_ in state.moments] if (rank == 0 or n_ranks > 1) else []
-                pk = params_to_host()       # the reference pickles the whole optimizable_params dict (misc.py:179-194)
-                _ckpt_thread[0] = threading.Thread(target=save_checkpoint, args=(i_epoch, i_batch, output_folder, host_obj, host_mom),
-                                                   kwargs=dict(rank=rank, n_ranks=n_ranks, params=pk))
-                _ckpt_thread[0].start()
-            t_elapsed = (time.time() - t_zero) / 60
-            if t_max_min is not None and n_ranks > 1:
-                t_elapsed = comm.bcast_object(t_elapsed, root=0)     # one decision for all ranks: nobody is left in a collective
-            if t_max_min is not None and t_elapsed >= t_max_min:
-                print_flush('Terminating program because maximum time limit is reached.', sto_rank, rank, **stdout_options)
-                sys.exit()
-            print_flush('Epoch {}, batch {} of {} started.'.format(i_epoch, i_batch, n_batch), sto_rank, rank, **stdout_options)
-            t00 = time.time()
-            this_i_theta, this_ind_batch = rank_batch(ind_list_rand, i_batch, rank, minibatch_size, n_ranks)
-            this_pos_batch = probe_pos_int[this_ind_batch]
-            # ONE decision for all ranks, taken on the angle the global batch starts with (rank 0's share).  The reference
-            # compares with each rank's own angle (adorym/ptychography.py:910): when a global batch straddles two angles its
-            # ranks then disagree, their optimiser counters i_opt_batch drift apart (:1266-1271) and the replicated objects
-            # stop being identical (golden F14 'immediate' records it; oracle.reconstruct(rank_local_counters=True) restates
-            # it).  Here the object is ONE sharded copy, so the step counter must be the same on every shard; the two rules
-            # coincide whenever no global batch straddles angles (always in 'per angle' mode).
-            is_last_batch_of_this_theta = i_batch == n_batch - 1 or ind_list_rand[i_batch + 1][0, 0] != ind_list_rand[i_batch][0, 0]
-            if n_ranks > 1 and rank == 0 and i_epoch == starting_epoch and not straddle_warned[0] and \
-                    len(np.unique(ind_list_rand[i_batch][:, 0])) > 1:
-                straddle_warned[0] = True
-                print_flush('  Note: this global batch holds positions of two angles.  adorym_amd keeps ONE optimiser step counter '
-                            'for the sharded object (decided on the angle the batch starts with); the reference keeps one per rank and '
-                            'its replicas drift apart in this case (INTEGRATION.md, "Deviations").  Use a position count that is a '
-                            'multiple of n_ranks * minibatch_size, or update_scheme="per angle", to reproduce a reference mpirun.',
-                            sto_rank, rank, **stdout_options)
-            print_flush('  Current rank is processing angle ID {}.'.format(this_i_theta), sto_rank, rank, **stdout_options)
+    def _update_object(self, i_batch, holo_fused):
+        """Exchange + update + constraints + mask (ptychography.py:1113-1158, 1210-1215).  Returns True when the object's update is
+        left to the small parameters' launch instead."""
+        state, opt, n_ranks, obj_size = self.state, self.opt, self.n_ranks, self.obj_size
+        obj_with_small = self.obj_with_small and holo_fused is None
+        if not self.optimize_object or obj_with_small or holo_fused is not None:
+            return obj_with_small
+        mask = self.mask.mask if self.mask is not None else None
+        if not self.fused:
+            opt.apply_gradient(self.obj.arr, self.gradient, self.i_opt_batch, flags=self.flags, mask=mask, **opt.options_dict)
+            return False
+        o = dict(opt.options_dict)
+        if self.opt_kind == 'gd':
+            o['step_size'] = GDOptimizer.scheduled_step(self.i_opt_batch, o.get('step_size', 0.001), o.get('dynamic_rate', True),
+                                                        o.get('first_downrate_iteration', 92))
+        first = None
+        plane = obj_size[1] * obj_size[2] * 2
+        if (n_ranks == 1 or state.overlap_gather) and self.builtin_model and not self.is_multi_dist and i_batch + 1 < self.n_batch \
+                and not self.rool:
+            # one rank: update the y-planes the next minibatch reads first; several ranks: gather the planes the
+            # next minibatches of ALL ranks read first (the same range on every rank: it shapes a collective).
+            # The rest -- of the element-wise update, or of the all-gather -- is queued by that minibatch on the
+            # side stream (DataParallelObject.finish_update), beside its multislice kernel
+            rank_batch(self.ind_list_rand, i_batch + 1, 0, self.minibatch_size, n_ranks)    # tops up a short last batch now
+            nxt = self.ind_list_rand[i_batch + 1]
+            ny0, ny1 = self.engine.y_footprint(self.probe_pos_int[nxt[:n_ranks * self.minibatch_size, 1]])
+            if self.update_scheme == 'per angle' and self.fuse_per_angle:
+                ny0, ny1 = 0, obj_size[0]
+            first = (ny0 * plane, ny1 * plane)
+        xkw = {}
+        if self.touched_planes is not None:
+            ad_, ab_, gm_ = combined_weights(self.forward_model.reg_list)
+            mult_ = float(n_ranks * self.forward_model.batch_group)     # every rank adds the term once per fused minibatch
 
-            # 'per angle': the minibatches of one angle see the same object, so they are fused into ONE launch
-            # (identical sums; all CUs busy instead of `minibatch_size` of them).  The reference evaluates them
-            # one by one and only logs the last (ptychography.py:1095-1099 `continue`).
-            # ---- rotate_out_of_loop (ptychography.py:917-947): the object is rotated to the angle OUTSIDE the differentiated
-            # block, once per change of angle -- the minibatches of the same angle that follow an 'immediate' update keep seeing
-            # the object as it was rotated when the angle began, exactly like the reference ----
-            if rool and this_i_theta != current_i_theta:
-                state.finish_update()           # the whole object is read
-                forward_model.rotate_outside(obj.arr, this_i_theta)
-            current_i_theta = this_i_theta
+            def _reg_shard(lo_, hi_, alo_, ahi_):
+                _lib.check(self.ctx.lib.adm_reg_grad_range(self.engine.plan.handle, self.obj.arr.ptr, ad_ * mult_, ab_ * mult_, gm_ * mult_,
+                                                           self.gradient.arr.ptr, lo_, hi_, alo_, ahi_))
+            xkw = dict(touched=(self.touched_planes[0] * plane, self.touched_planes[1] * plane), reg_shard=_reg_shard)
+        state.exchange_and_update(self.opt_kind, self.i_opt_batch, o, flags=self.flags, mask=mask, first=first, **xkw)
+        return False
 
-            if update_scheme == 'per angle' and fuse_per_angle:
-                pending_ind.append(this_ind_batch)
-                if not is_last_batch_of_this_theta:
-                    continue
-                forward_model.batch_group = len(pending_ind)
-                this_ind_batch = np.concatenate(pending_ind)
-                this_pos_batch = probe_pos_int[this_ind_batch]
-                pending_ind = []
+    def _update_small_params(self, i_batch, obj_with_small, holo_fused):
+        """The small parameters (optimizers.py:1022-1083): probe, sub-pixel positions, propagation distances, affine registration.
+        Gradients are summed over the ranks on the device, then ONE launch updates them all (per-array Adam, the drift guard of the
+        positions, the identity pin of affine matrix 0, and the zero fill of the accumulators for the next minibatch); custom
+        optimiser objects fall back to their own apply_gradient."""
+        items = []
+        if obj_with_small:
+            self.state.finish_update()
+            items.append(dict(opt=self.opt, x=self.state.obj.view(0, (self.state.n,)), g=self.state.grad.view(0, (self.state.n,))))
+        i_global = i_batch + self.i_epoch * self.n_batch
+        due = []
+        for p in self.small if holo_fused is None else ():     # (the fused holography launch has updated them already)
+            if p.due(i_global):
+                due.append(p)
+            elif p.key == 'probe_real':
+                print_flush('  Probe is not updated because current batch is out of the specified range ({}, {}).'.format(p.delay, p.limit),
+                            0, self.rank, **self.stdout_options)
+        items += [dict(opt=p.opt, x=p.x, g=p.g, zero_grad=True, **p.extras) for p in due]      # (accumulators zero-filled once used)
+        if self.n_ranks > 1:
+            for it_ in items:
+                self.comm.all_reduce_device(it_['g'])
+        apply_small_params(self.ctx, items, self.i_opt_batch)
+        self.zeroed_by_update = {p.key for p in due}
 
-            # ---- reweighted-L1 weights, refreshed every 10 minibatches (ptychography.py:995-1000) ----
-            if reg_rwl1 is not None:
-                if i_batch % 10 == 0:
-                    state.finish_update()
-                    _lib.check(ctx.lib.adm_rwl1_update(engine.plan.handle, obj.arr.ptr, rwl1_weight.ptr, rwl1_scratch.ptr))
-                reg_rwl1.update_l1_weight(rwl1_weight)
-
-            # ---- footprint-restricted exchange: the planes the GLOBAL batch (all ranks) touches, the same on every rank ----
-            touched_planes = None
-            if restricted_exchange:
-                if update_scheme == 'per angle':
-                    touched_planes = (0, this_obj_size[0])      # every position of the angle: the whole object
-                else:
-                    gb_ = ind_list_rand[i_batch]
-                    if len(gb_) < n_ranks * minibatch_size:     # (a short last batch was topped up from batch 0 by rank_batch)
-                        gb_ = np.concatenate([gb_, ind_list_rand[0][:n_ranks * minibatch_size - len(gb_)]])
-                    touched_planes = engine.y_footprint(probe_pos_int[gb_[:, 1]])
-            forward_model.restricted_planes = touched_planes
-
-            # ---- the next angle's rotation data, one minibatch ahead: when the NEXT global batch starts a new angle, its lookup table
-            # is computed and uploaded now (host work while the GPU still runs the previous minibatch) and its adjoint CSR is built on
-            # the side stream beside this minibatch's multislice kernel.  Met cold, the first launch of an angle waited 2 - 2.5 ms for
-            # the host (table: NumPy + allocation; CSR: ~25 launches); the tables are kept for the whole reconstruction either way.
-            # (The table is computed TWO minibatches ahead, the CSR and -- for datasets small enough to live on the device -- the angle's
-            # measured data ONE ahead: the host is at most a minibatch ahead of the GPU and each of these costs it 1 - 2 ms.)
-            if builtin_model and not two_d_mode and not is_multi_dist and not rool:
-                def _angle_of(i_b):
-                    nb_ = ind_list_rand[i_b]
-                    return int(nb_[min(rank * minibatch_size, len(nb_) - 1), 0])
-                if i_batch + 2 < n_batch and _angle_of(i_batch + 2) != this_i_theta:
-                    rotation_tables(_angle_of(i_batch + 2))
-                if i_batch + 1 < n_batch and _angle_of(i_batch + 1) != this_i_theta:
-                    forward_model.prefetch_table = rotation_tables(_angle_of(i_batch + 1))
-                    forward_model.prefetch_data(_angle_of(i_batch + 1))
-
-            # ---- gradients (ptychography.py:1017-1066) ----
-            t_grad_0 = time.time()
-            side_hook, init_grad = None, False
-            if initialize_gradients:
-                if builtin_model:
-                    # queued by the model on the side stream after the rotation: the deferred part of the previous update,
-                    # then the regulariser kernel in 'set' mode (or a zero fill) initialises the gradient buffer
-                    side_hook, init_grad = state.finish_update, True
-                else:
-                    state.zero_grad()
-                # (an accumulator that the last small-parameter update consumed was zero-filled by that launch)
-                if optimize_probe and id(probe_grad_dev) not in zeroed_by_update:
-                    probe_grad_dev.zero_()
-                if optimize_all_probe_pos and id(pos_grad_dev) not in zeroed_by_update:
-                    pos_grad_dev.zero_()
-                if opt_free_prop is not None and id(free_prop_grad_dev) not in zeroed_by_update:
-                    free_prop_grad_dev.zero_()
-                if opt_prj_affine is not None and id(affine_grad_dev) not in zeroed_by_update:
-                    affine_grad_dev.zero_()
-                zeroed_by_update = set()
-            grad_func_args = {}
-            for arg in forward_model.argument_ls:
-                if arg == 'obj':
-                    grad_func_args[arg] = forward_model.arr_rot if rool else obj.arr     # (:1009-1013)
-                elif arg == 'this_i_theta':
-                    grad_func_args[arg] = this_i_theta
-                elif arg == 'this_pos_batch':
-                    grad_func_args[arg] = this_pos_batch
-                elif arg == 'this_ind_batch':
-                    grad_func_args[arg] = this_ind_batch
-                elif arg == 'prj':
-                    grad_func_args[arg] = prj
-                else:
-                    grad_func_args[arg] = optimizable_params[arg]
-            forward_model.update_loss_args(grad_func_args)
-            # Multi-distance holography whose update is exactly "Adam on what this minibatch's gradients say" -- one rank, an update per
-            # minibatch, no regulariser, constraint or mask on the object, plain Adam with common (b1, b2, eps) on the object and on
-            # whichever of free_prop_cm / prj_affine_ls are optimised: the steps run INSIDE the gradient launch group's last kernel
-            # (adm_holo_fwd_adj_adam; same arithmetic, same bits), no gradient is stored and no optimiser launch follows.
-            holo_fused = None
-            if is_multi_dist and not holo_tiled and builtin_model and init_grad and update_scheme == 'immediate' and optimize_object and fused \
-                    and opt_kind == 'adam' and n_ranks == 1 and flags == 0 and mask is None and not optimize_probe \
-                    and not optimize_all_probe_pos and not forward_model.reg_list and os.environ.get('ADM_HOLO_FUSED_ADAM', '1') == '1':
-                small_opts = [o_ for o_ in (opt_free_prop, opt_prj_affine) if o_ is not None]
-                okeys = {(float(o_.options_dict.get('b1', 0.9)), float(o_.options_dict.get('b2', 0.999)), float(o_.options_dict.get('eps', 1e-7)))
-                         for o_ in [opt] + small_opts}
-                if len(okeys) == 1 and all(type(o_) is AdamOptimizer and set(o_.options_dict) <= {'step_size', 'b1', 'b2', 'eps'}
-                                           for o_ in [opt] + small_opts):
-                    upd_small = (i_batch + i_epoch * n_batch) >= other_params_update_delay
-                    b1_, b2_, eps_ = next(iter(okeys))
-                    holo_fused = dict(obj_mv=(state.moments[0], state.moments[1]), step_obj=float(opt.options_dict.get('step_size', 0.001)),
-                                      i_batch=i_opt_batch, b1=b1_, b2=b2_, eps=eps_, dists=None, affine=None, pin=None, opts=[opt])
-                    if upd_small and opt_free_prop is not None:
-                        holo_fused['dists'] = (opt_free_prop.params_whole_array_dict['m'], opt_free_prop.params_whole_array_dict['v'],
-                                               float(opt_free_prop.options_dict.get('step_size', 0.001)))
-                        holo_fused['opts'].append(opt_free_prop)
-                    if upd_small and opt_prj_affine is not None:
-                        holo_fused['affine'] = (opt_prj_affine.params_whole_array_dict['m'], opt_prj_affine.params_whole_array_dict['v'],
-                                                float(opt_prj_affine.options_dict.get('step_size', 0.001)))
-                        holo_fused['pin'] = affine_identity_dev
-                        holo_fused['opts'].append(opt_prj_affine)
-                    state.finish_update()
-            if is_multi_dist and builtin_model:
-                forward_model.fused_adam = holo_fused
-            # which measured data the NEXT evaluation needs, so that the model can send them to the device beside this one's launch
-            # (streamed datasets; resident ones are views of device arrays already)
-            if builtin_model and not is_multi_dist and stage_next_targets:
-                forward_model.next_batch = _next_evaluation(i_batch)
-            grads = diff.get_gradients(_accumulate_into=gradient.arr, _side_hook=side_hook, _init_grad=init_grad, **grad_func_args)
-            print_flush('  Gradient calculation done in {} s.'.format(time.time() - t_grad_0), sto_rank, rank, **stdout_options)
-            if initialize_gradients:
-                initialize_gradients = False
-            if rool:
-                # (:1066-1078) the gradient buffer is in the rotated frame: resample it with the -theta table, after EVERY
-                # minibatch and on everything accumulated so far.  In 'per angle' mode earlier contributions are therefore
-                # resampled again (the reference's TODO at :1075 says they should not be); kept literally -- golden F15
-                # pins it -- and the minibatches of an angle are not fused into one launch in this mode for that reason.
-                forward_model.resample_gradient(gradient.arr, this_i_theta)
-            if holo_fused is not None:
-                for o_ in holo_fused['opts']:
-                    o_.i_batch += 1
-                grads = None
-            if optimize_probe and holo_fused is None:
-                gpd = grads[opt_probe.index_in_grad_returns]       # interleaved (real, imag) device array
-                _lib.check(ctx.lib.adm_axpy(ctx.handle, probe_grad_dev.ptr, gpd.ptr, 1.0, gpd.size))
-            if optimize_all_probe_pos:
-                gcd = grads[opt_args_ls.index(forward_model.get_argument_index('probe_pos_correction'))]
-                _lib.check(ctx.lib.adm_axpy(ctx.handle, pos_grad_dev.ptr, gcd.ptr, 1.0, gcd.size))
-            if opt_free_prop is not None and holo_fused is None:
-                gfd = grads[opt_free_prop.index_in_grad_returns]
-                _lib.check(ctx.lib.adm_axpy(ctx.handle, free_prop_grad_dev.ptr, gfd.ptr, 1.0, gfd.size))
-            if opt_prj_affine is not None and holo_fused is None:
-                gad = grads[opt_prj_affine.index_in_grad_returns]
-                _lib.check(ctx.lib.adm_axpy(ctx.handle, affine_grad_dev.ptr, gad.ptr, 1.0, gad.size))
-
-            if update_scheme == 'per angle' and not is_last_batch_of_this_theta:
-                flush_log()     # keeps at most one evaluation between a loss read-back and its use (two pinned slots)
+    def _write_intermediate(self, i_batch):
+        """output_object(full_output=False) + output_intermediate_parameters of the reference: object TIFFs under
+        intermediate/object (named by (epoch, batch) when save_history, else overwritten), and one file set per optimised
+        parameter under intermediate/<what>."""
+        i_epoch, params, folder = self.i_epoch, self.optimizable_params, os.path.join(self.output_folder, 'intermediate')
+        tag = '_{}_{}'.format(i_epoch, i_batch) if self.save_history else ''
+        probe = self.probe_dev.get() if self.optimize_probe else None
+        _write_images(os.path.join(folder, 'object'), os.path.join(folder, 'probe'), tag, self.obj.arr.get(), self.unknown_type, probe)
+        for p in self.small:
+            if p.key == 'probe_real':
                 continue
-            initialize_gradients = True
+            d_ = os.path.join(folder, {'probe_pos_correction': 'probe_pos', 'prj_affine_ls': 'prj_affine'}.get(p.key, p.key))
+            os.makedirs(d_, exist_ok=True)
+            v_ = np.asarray(_host(params[p.key]))
+            if p.key == 'probe_pos_correction' and self.is_multi_dist:
+                np.savetxt(os.path.join(d_, 'probe_pos_correction_{}_{}.txt'.format(i_epoch, i_batch)), v_)
+            elif p.key == 'probe_pos_correction':
+                for i_t in range(self.n_theta):
+                    np.savetxt(os.path.join(d_, 'probe_pos_correction_{}_{}_{}.txt'.format(i_epoch, i_batch, i_t)), v_[i_t])
+            elif p.key == 'prj_affine_ls':
+                np.savetxt(os.path.join(d_, 'prj_affine_{}.txt'.format(i_epoch)), np.concatenate(v_, 0))
+            else:
+                np.savetxt(os.path.join(d_, '{}_{}.txt'.format(p.key, i_epoch)), np.atleast_1d(v_))
 
-            # ---- exchange + update + constraints + mask (ptychography.py:1113-1158, 1210-1215) ----
-            # A small object (2-D ptychography, holography: a few hundred thousand unknowns) on one rank, plain Adam, no constraint
-            # and no mask: its update is one more array of the ONE launch that updates the small parameters below (same
-            # arithmetic -- adam_value in adm_optim.h -- and same step counter); these paths are chains of 5-20 us kernels, where
-            # a launch saved is 5 % of a minibatch.
-            obj_with_small = (optimize_object and fused and opt_kind == 'adam' and n_ranks == 1 and flags == 0 and mask is None
-                              and state.n <= (1 << 22) and not restricted_exchange and holo_fused is None
-                              and set(opt.options_dict) <= {'step_size', 'b1', 'b2', 'eps'})
-            if optimize_object and not obj_with_small and holo_fused is None:
-                if fused:
-                    o = dict(opt.options_dict)
-                    if opt_kind == 'gd':
-                        o['step_size'] = GDOptimizer.scheduled_step(i_opt_batch, o.get('step_size', 0.001), o.get('dynamic_rate', True),
-                                                                    o.get('first_downrate_iteration', 92))
-                    first = None
-                    if (n_ranks == 1 or state.overlap_gather) and builtin_model and not is_multi_dist and i_batch + 1 < n_batch and not rool:
-                        # one rank: update the y-planes the next minibatch reads first; several ranks: gather the planes the
-                        # next minibatches of ALL ranks read first (the same range on every rank: it shapes a collective).
-                        # The rest -- of the element-wise update, or of the all-gather -- is queued by that minibatch on the
-                        # side stream (DataParallelObject.finish_update), beside its multislice kernel
-                        rank_batch(ind_list_rand, i_batch + 1, 0, minibatch_size, n_ranks)    # tops up a short last batch now
-                        nxt = ind_list_rand[i_batch + 1]
-                        ny0, ny1 = engine.y_footprint(probe_pos_int[nxt[:n_ranks * minibatch_size, 1]])
-                        if update_scheme == 'per angle' and fuse_per_angle:
-                            ny0, ny1 = 0, this_obj_size[0]
-                        plane = this_obj_size[1] * this_obj_size[2] * 2
-                        first = (ny0 * plane, ny1 * plane)
-                    xkw = {}
-                    if touched_planes is not None:
-                        plane_ = this_obj_size[1] * this_obj_size[2] * 2
-                        ad_, ab_, gm_ = _cw(forward_model.reg_list)
-                        mult_ = float(n_ranks * forward_model.batch_group)     # every rank adds the term once per fused minibatch
+    def _flush_log(self):
+        if self.pending_log is None:
+            return
+        e_, b_, thunk, t_start = self.pending_log
+        self.pending_log = None
+        current_loss = thunk()
+        self.loss_history.append(current_loss)
+        self.log('Minibatch/angle done in {} s; loss (rank 0) is {}.'.format(time.time() - t_start, current_loss))
+        self.log('Throughput: {} angles/sec'.format(self.minibatch_size / (time.time() - t_start)))
+        self.f_conv.write('{},{},{},{}\n'.format(e_, b_, current_loss, time.time() - self.t_zero))
+        self.f_conv.flush()
 
-                        def _reg_shard(lo_, hi_, alo_, ahi_):
-                            _lib.check(ctx.lib.adm_reg_grad_range(engine.plan.handle, obj.arr.ptr, ad_ * mult_, ab_ * mult_, gm_ * mult_,
-                                                                  gradient.arr.ptr, lo_, hi_, alo_, ahi_))
-                        xkw = dict(touched=(touched_planes[0] * plane_, touched_planes[1] * plane_), reg_shard=_reg_shard)
-                    state.exchange_and_update(opt_kind, i_opt_batch, o, flags=flags, mask=mask.mask if mask is not None else None,
-                                              first=first, **xkw)
-                else:
-                    opt.apply_gradient(obj.arr, gradient, i_opt_batch, flags=flags, mask=mask.mask if mask is not None else None,
-                                       **opt.options_dict)
-
-            # ---- the small parameters (optimizers.py:1022-1083): probe, sub-pixel positions, propagation distances, affine
-            # registration.  Gradients are summed over the ranks on the device, then ONE launch updates them all (per-array
-            # Adam, the drift guard of the positions, the identity pin of affine matrix 0, and the zero fill of the accumulators
-            # for the next minibatch); custom optimiser objects fall back to their own apply_gradient ----
-            small = []
-            if obj_with_small:
-                state.finish_update()
-                small.append(dict(opt=opt, x=state.obj.view(0, (state.n,)), g=state.grad.view(0, (state.n,))))
-            i_global = i_batch + i_epoch * n_batch
-            if optimize_probe:
-                if probe_update_delay <= i_global < probe_update_limit:
-                    small.append(dict(opt=opt_probe, x=probe_dev, g=probe_grad_dev, zero_grad=True))
-                else:
-                    print_flush('  Probe is not updated because current batch is out of the specified range ({}, {}).'.format(
-                        probe_update_delay, probe_update_limit), 0, rank, **stdout_options)
-            if i_global >= other_params_update_delay and holo_fused is None:
-                if optimize_all_probe_pos:
-                    # (+ "prevent position drifting": subtract the mean over (theta, position))
-                    small.append(dict(opt=opt_probe_pos, x=optimizable_params['probe_pos_correction'], g=pos_grad_dev, center_cols=2, zero_grad=True))
-                if opt_free_prop is not None:
-                    small.append(dict(opt=opt_free_prop, x=optimizable_params['free_prop_cm'], g=free_prop_grad_dev, zero_grad=True))
-                if opt_prj_affine is not None:
-                    # (+ "regularize transformation of image 0": matrix 0 is pinned to the identity)
-                    small.append(dict(opt=opt_prj_affine, x=optimizable_params['prj_affine_ls'], g=affine_grad_dev, pin=affine_identity_dev,
-                                      zero_grad=True))
-            if n_ranks > 1:
-                for it_ in small:
-                    comm.all_reduce_device(it_['g'])
-            apply_small_params(ctx, small, i_opt_batch)
-            zeroed_by_update = {id(it_['g']) for it_ in small}
-
-            # ---- intermediate output (ptychography.py:1231-1246; util.py:1958-2028, optimizers.py:1111-1160) ----
-            if save_intermediate and ((save_intermediate_level == 'epoch' and i_batch == n_batch - 1) or save_intermediate_level == 'batch'):
-                # finish_update() may hold a deferred collective (the rest of the all-gather): every rank calls it (the
-                # condition is the same on all ranks)
-                if is_last_batch_of_this_theta:
-                    state.finish_update()
-                if rank == 0 and is_last_batch_of_this_theta:
-                    _write_intermediate(output_folder, obj.arr.get(), unknown_type, i_epoch, i_batch, save_history, opt_ls,
-                                        probe_dev, optimizable_params, n_theta, is_multi_dist)
-                comm.barrier()
-
-            # ---- finishing a batch (ptychography.py:1231-1271) ----
-            this_log = (i_epoch, i_batch, forward_model.take_loss_thunk() if builtin_model else (lambda v=forward_model.current_loss: v), t00)
-            flush_log()                     # the PREVIOUS minibatch: its loss is read after this one has been queued
-            pending_log[0] = this_log
-            if optimizer_batch_number_increment == 'angle':
-                if is_last_batch_of_this_theta:
-                    i_opt_batch += 1
-            elif optimizer_batch_number_increment == 'batch':
-                i_opt_batch += 1
-
-        flush_log()
-        state.finish_update()
-        if n_epochs != 'auto' and i_epoch == n_epochs - 1:
-            cont = False
-        print_flush('Epoch {} (rank {}); Delta-t = {} s; current time = {} s,'.format(i_epoch, rank, time.time() - t0,
-                                                                                       time.time() - t_zero), sto_rank, rank, **stdout_options)
-        i_epoch = i_epoch + 1
-
-        # ---- outputs after an epoch (ptychography.py:1290-1294; util.py:1958-2028) ----
-        if rank == 0:
-            arr = obj.arr.get()
-            if unknown_type == 'delta_beta':
-                write_tiff(arr[..., 0], os.path.join(output_folder, 'delta_ds_{}'.format(ds_level)), dtype='float32')
-                write_tiff(arr[..., 1], os.path.join(output_folder, 'beta_ds_{}'.format(ds_level)), dtype='float32')
-            else:   # util.py:1990-2005
-                write_tiff(np.sqrt(arr[..., 0] ** 2 + arr[..., 1] ** 2), os.path.join(output_folder, 'obj_mag_ds_{}'.format(ds_level)), dtype='float32')
-                write_tiff(np.arctan2(arr[..., 1], arr[..., 0]), os.path.join(output_folder, 'obj_phase_ds_{}'.format(ds_level)), dtype='float32')
-            pa = probe_dev.get()
-            pc = pa[..., 0] + 1j * pa[..., 1]
-            write_tiff(np.abs(pc), os.path.join(output_folder, 'probe_mag_ds_{}'.format(ds_level)), dtype='float32')
-            write_tiff(np.angle(pc), os.path.join(output_folder, 'probe_phase_ds_{}'.format(ds_level)), dtype='float32')
-        print_flush('Current iteration finished.', sto_rank, rank, **stdout_options)
-    if _ckpt_thread[0] is not None:
-        _ckpt_thread[0].join()
-    comm.barrier()
-    f_conv.close()
-    f.close()
-    if return_state:
-        arr = obj.arr.get()
-        pa = probe_dev.get()
-        pc = optimizable_params['probe_pos_correction']
+    def finish(self):
+        """Outputs: the checkpoint writer is waited for, the files are closed, and with return_state the final arrays returned."""
+        if self.ckpt_thread is not None:
+            self.ckpt_thread.join()
+        self.comm.barrier()
+        self.f_conv.close()
+        self.f.close()
+        if not self.return_state:
+            return None
+        arr, pa, params = self.obj.arr.get(), self.probe_dev.get(), self.optimizable_params
         return {'delta': arr[..., 0], 'beta': arr[..., 1], 'probe_real': pa[..., 0], 'probe_imag': pa[..., 1],
-                'probe_pos_correction': pc.get() if hasattr(pc, 'get') else np.asarray(pc),
-                'free_prop_cm': (lambda v: v.get() if hasattr(v, 'get') else v)(optimizable_params.get('free_prop_cm', free_prop_cm)),
-                'prj_affine_ls': (lambda v: v.get() if hasattr(v, 'get') else v)(optimizable_params.get('prj_affine_ls')),
-                'losses': loss_history, 'output_folder': output_folder}
-    return None
+                'probe_pos_correction': np.asarray(_host(params['probe_pos_correction'])),
+                'free_prop_cm': _host(params.get('free_prop_cm', self.free_prop_cm)), 'prj_affine_ls': _host(params.get('prj_affine_ls')),
+                'losses': self.loss_history, 'output_folder': self.output_folder}

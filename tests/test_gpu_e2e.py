@@ -262,3 +262,30 @@ def test_streamed_data_staged_ahead_equals_upload_on_demand_bitwise(tmp_path, mo
     a, b = out
     assert a['losses'] == b['losses']
     assert np.array_equal(a['delta'], b['delta']) and np.array_equal(a['beta'], b['beta'])
+
+
+@pytest.mark.parametrize('extra', [dict(), dict(optimize_probe=True, probe_learning_rate=1e-3, save_intermediate=True, store_checkpoint=True,
+                                               update_scheme='per angle'), dict(rotate_out_of_loop=True)], ids=['plain', 'probe_ckpt_perangle', 'rool'])
+def test_driver_frees_its_run_by_reference_counting(tmp_path, extra):
+    """Everything one driver call allocates on the device -- object, gradient, moments, engines, probe, accumulators -- is released
+    when it returns, by reference counting: no reference cycle keeps the run until Python's cycle collector gets to it (a process
+    that calls the driver several times would hold several runs' device memory)."""
+    import gc
+    from adorym_amd import ptychography as P
+    from adorym_amd.device import DeviceArray
+    from adorym_amd.dp import DataParallelObject
+    from adorym_amd.forward_model import PtychographyModel
+    from adorym_amd.propagate import MultisliceEngine
+    kinds = (P._Run, DeviceArray, DataParallelObject, PtychographyModel, MultisliceEngine)
+
+    def census():
+        return [sum(type(o) is k for o in gc.get_objects()) for k in kinds]
+    gc.collect()
+    gc.disable()
+    try:
+        before = census()
+        run(tmp_path, n_epochs=1, optimizer='adam', learning_rate=1e-6, **extra)
+        after = census()
+    finally:
+        gc.enable()
+    assert all(a <= b for a, b in zip(after, before)), list(zip([k.__name__ for k in kinds], before, after))
