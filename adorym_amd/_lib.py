@@ -106,6 +106,7 @@ SIGNATURES = {
     'adm_p2p_status': (_I, [_VP]),
     'adm_p2p_destroy': (_I, [_VP]),
     'adm_plan_create': (_I, [_VP, C.POINTER(PlanDesc), C.POINTER(_VP)]),
+    'adm_plan_create_streamed': (_I, [_VP, C.POINTER(PlanDesc), C.POINTER(_VP)]),
     'adm_plan_destroy': (_I, [_VP]),
     'adm_plan_set_detector_mask': (_I, [_VP, _VP]),
     'adm_plan_set_detector_kernels': (_I, [_VP, C.c_int, _VP, _VP]),

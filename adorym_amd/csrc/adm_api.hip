@@ -271,27 +271,33 @@ static int upload_c(adm_ctx* ctx, const float* re, const float* im, size_t n, fl
     return ADM_OK;
 }
 
-extern "C" int adm_plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out) {
-    if (!ctx || !desc || !out) return fail(ADM_ERR_INVALID, "adm_plan_create: null argument");
+// adm_plan_create and adm_plan_create_streamed: the same descriptor and checks; `who` names the entry point in the messages
+static int plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out, bool streamed) {
+    const std::string who = streamed ? "adm_plan_create_streamed" : "adm_plan_create";
+    if (!ctx || !desc || !out) return fail(ADM_ERR_INVALID, who + ": null argument");
     const adm_plan_desc& d = *desc;
     if (d.obj_y <= 0 || d.obj_x <= 0 || d.obj_z <= 0 || d.probe_y <= 0 || d.probe_x <= 0)
-        return fail(ADM_ERR_INVALID, "adm_plan_create: non-positive dimension");
-    if (d.pad_y0 < 0 || d.pad_y1 < 0 || d.pad_x0 < 0 || d.pad_x1 < 0) return fail(ADM_ERR_INVALID, "adm_plan_create: negative pad");
-    if (d.binning < 1) return fail(ADM_ERR_INVALID, "adm_plan_create: binning must be >= 1");
-    if (d.sign_convention != 1 && d.sign_convention != -1) return fail(ADM_ERR_INVALID, "adm_plan_create: sign_convention must be +-1");
-    if (d.det_mode < 0 || d.det_mode > 2) return fail(ADM_ERR_INVALID, "adm_plan_create: bad det_mode");
-    if (d.loss_type != ADM_LOSS_LSQ && d.loss_type != ADM_LOSS_POISSON) return fail(ADM_ERR_INVALID, "adm_plan_create: bad loss_type");
-    if (d.unknown_type != 0 && d.unknown_type != 1) return fail(ADM_ERR_INVALID, "adm_plan_create: bad unknown_type");
-    if (d.unknown_type == 1 && d.binning != 1) return fail(ADM_ERR_UNSUPPORTED, "adm_plan_create: binning > 1 with unknown_type real_imag is not implemented");
-    if (!d.h_re || !d.h_im) return fail(ADM_ERR_INVALID, "adm_plan_create: transfer function missing");
+        return fail(ADM_ERR_INVALID, who + ": non-positive dimension");
+    if (d.pad_y0 < 0 || d.pad_y1 < 0 || d.pad_x0 < 0 || d.pad_x1 < 0) return fail(ADM_ERR_INVALID, who + ": negative pad");
+    if (d.binning < 1) return fail(ADM_ERR_INVALID, who + ": binning must be >= 1");
+    if (d.sign_convention != 1 && d.sign_convention != -1) return fail(ADM_ERR_INVALID, who + ": sign_convention must be +-1");
+    if (d.det_mode < 0 || d.det_mode > 2) return fail(ADM_ERR_INVALID, who + ": bad det_mode");
+    if (d.loss_type != ADM_LOSS_LSQ && d.loss_type != ADM_LOSS_POISSON) return fail(ADM_ERR_INVALID, who + ": bad loss_type");
+    if (d.unknown_type != 0 && d.unknown_type != 1) return fail(ADM_ERR_INVALID, who + ": bad unknown_type");
+    if (d.unknown_type == 1 && d.binning != 1) return fail(ADM_ERR_UNSUPPORTED, who + ": binning > 1 with unknown_type real_imag is not implemented");
+    if (!d.h_re || !d.h_im) return fail(ADM_ERR_INVALID, who + ": transfer function missing");
     if (d.det_mode == ADM_DET_FRESNEL && (!d.hfree_re || !d.hfree_im))
-        return fail(ADM_ERR_INVALID, "adm_plan_create: det_mode fresnel needs hfree");
-    const bool tuned = (d.probe_y == d.probe_x) && ms_threads_for(d.probe_x) != 0;
-    if (!tuned && !ms_generic_supported(d.probe_y, d.probe_x))
+        return fail(ADM_ERR_INVALID, who + ": det_mode fresnel needs hfree");
+    const bool tuned = !streamed && (d.probe_y == d.probe_x) && ms_threads_for(d.probe_x) != 0;
+    if (streamed) {
+        if (!ms_streamed_supported(d.probe_y, d.probe_x))
+            return fail(ADM_ERR_UNSUPPORTED, who + ": probe sides must be at most 2048");
+    } else if (!tuned && !ms_generic_supported(d.probe_y, d.probe_x)) {
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_create: probe too large for one workgroup (Py*Px <= 16384 and the field must fit 160 KB of LDS)");
-    if (d.n_modes < 1 || d.n_modes > 64) return fail(ADM_ERR_INVALID, "adm_plan_create: n_modes must be in [1, 64]");
+    }
+    if (d.n_modes < 1 || d.n_modes > 64) return fail(ADM_ERR_INVALID, who + ": n_modes must be in [1, 64]");
     if (d.pad_y0 + d.obj_y + d.pad_y1 < d.probe_y || d.pad_x0 + d.obj_x + d.pad_x1 < d.probe_x)
-        return fail(ADM_ERR_INVALID, "adm_plan_create: padded object smaller than the probe");
+        return fail(ADM_ERR_INVALID, who + ": padded object smaller than the probe");
     ADM_HIP(hipSetDevice(ctx->device));
     adm_plan* p = new adm_plan();
     p->ctx = ctx;
@@ -307,6 +313,7 @@ extern "C" int adm_plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan
     p->trans_only = false;
     std::memset(p->cover_keys, 0, sizeof(p->cover_keys));
     p->generic = !tuned;
+    p->streamed = streamed;
     {   // radix lists of the generic kernel's transforms: 8, 4, 2, 9, 3, 5, 7, then whatever primes remain
         auto factor = [](int n, int* r) {
             int cnt = 0;
@@ -319,7 +326,7 @@ extern "C" int adm_plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan
         p->gen_nry = factor(d.probe_y, p->gen_ry);
         if (p->gen_nrx < 0 || p->gen_nry < 0) {
             delete p;
-            return fail(ADM_ERR_UNSUPPORTED, "adm_plan_create: probe size with more than 8 prime-power factors");
+            return fail(ADM_ERR_UNSUPPORTED, who + ": probe size with more than 8 prime-power factors");
         }
     }
     p->reg_stats = nullptr;
@@ -356,6 +363,9 @@ extern "C" int adm_plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan
     return ADM_OK;
 }
 
+extern "C" int adm_plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out) { return plan_create(ctx, desc, out, false); }
+extern "C" int adm_plan_create_streamed(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out) { return plan_create(ctx, desc, out, true); }
+
 extern "C" int adm_plan_destroy(adm_plan* plan) {
     if (!plan) return ADM_OK;
     if (plan->h_dev) adm_free(plan->ctx, plan->h_dev);
@@ -391,6 +401,9 @@ extern "C" int adm_plan_set_detector_mask(adm_plan* plan, const float* mask_host
 extern "C" int adm_plan_set_detector_kernels(adm_plan* plan, int n, const float* hfree_re, const float* hfree_im) {
     if (!plan || !hfree_re || !hfree_im) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_kernels: null argument");
     if (n < 1) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_kernels: n must be >= 1");
+    if (n > 1 && plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_kernels: several detector kernels need one probe set per position "
+                                         "(adm_multislice_fwd_adj_pp), which streamed plans do not run");
     if (plan->d.det_mode != ADM_DET_FRESNEL) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_kernels: the plan's det_mode is not ADM_DET_FRESNEL");
     const size_t npx = (size_t)plan->d.probe_y * plan->d.probe_x, tot = npx * (size_t)n;
     float2 *a = nullptr, *b = nullptr;
@@ -422,11 +435,12 @@ extern "C" size_t adm_plan_rot_elems(const adm_plan* plan) {
 extern "C" size_t adm_plan_workspace_bytes(const adm_plan* plan, int batch) {
     if (!plan || batch <= 0) return 0;
     // [stash: B*M*per | tile gradients: B*per | cover lists (Yp*Xp*(1+64) u32) + overflow flag | detector fields: B*M*G*NT |
-    //  per-position probe gradients: B*M*Py*Px]
+    //  per-position probe gradients: B*M*Py*Px | streamed plans: fields B*M*Py*Px, loss partials B*column groups floats]
     const size_t per = adm::ms_ws_per_pos(plan) * sizeof(float2);
     const size_t det = adm::ws_det_bytes(plan, batch);
     const size_t gpp = (size_t)batch * plan->d.n_modes * plan->d.probe_y * plan->d.probe_x * sizeof(float2);
-    return (size_t)batch * (plan->d.n_modes + 1) * per + (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64 + det + gpp;
+    const size_t streamed = plan->streamed ? gpp + (size_t)batch * adm::ms_streamed_col_groups(plan->d.probe_y, plan->d.probe_x) * sizeof(float) : 0;
+    return (size_t)batch * (plan->d.n_modes + 1) * per + (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64 + det + gpp + streamed;
 }
 
 namespace adm {
@@ -447,6 +461,9 @@ size_t ws_off_gtile(const adm_plan* plan, int batch) { return (size_t)batch * pl
 size_t ws_off_cover(const adm_plan* plan, int batch) { return ws_off_gtile(plan, batch) + (size_t)batch * ms_ws_per_pos(plan) * sizeof(float2); }
 size_t ws_off_det(const adm_plan* plan, int batch) { return ws_off_cover(plan, batch) + (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64; }
 size_t ws_off_gprobe(const adm_plan* plan, int batch) { return ws_off_det(plan, batch) + ws_det_bytes(plan, batch); }
+size_t ws_off_field(const adm_plan* plan, int batch) {      // streamed plans: [B][M][Py][Px] fields, then the loss partials
+    return ws_off_gprobe(plan, batch) + (size_t)batch * plan->d.n_modes * plan->d.probe_y * plan->d.probe_x * sizeof(float2);
+}
 }  // namespace adm
 
 int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
@@ -456,7 +473,10 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: null argument");
     if (batch <= 0) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: batch must be positive");
     const adm_plan_desc& d = plan->d;
-    if (want_grad) {
+    if (plan->streamed && per_position)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_multislice_fwd_adj_pp: a streamed plan runs one probe set shared by all positions "
+                                         "(per-position probes are not implemented on the streamed path)");
+    if (want_grad || plan->streamed) {      // (a streamed plan keeps its fields in the workspace even for want_grad = 0)
         if (!workspace || workspace_bytes < adm_plan_workspace_bytes(plan, batch))
             return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: workspace too small");
     }
@@ -523,7 +543,13 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         p.gen_nrx = plan->gen_nrx; p.gen_nry = plan->gen_nry;
         for (int i = 0; i < 8; ++i) { p.gen_rx[i] = plan->gen_rx[i]; p.gen_ry[i] = plan->gen_ry[i]; }
         p.gen_twid_y = plan->twid_y_dev; p.gen_hs = plan->hs_dev; p.gen_hfree_s = plan->hfree_s_dev;
-        ADM_HIP(ms_generic_launch(p, batch, plan->ctx->stream));
+        if (plan->streamed) {
+            char* f = (char*)workspace + ws_off_field(plan, batch);
+            const size_t fbytes = (size_t)batch * probe_elems * sizeof(float2);
+            ADM_HIP(ms_streamed_launch(p, batch, (float2*)f, (float*)(f + fbytes), plan->ctx->stream));
+        } else {
+            ADM_HIP(ms_generic_launch(p, batch, plan->ctx->stream));
+        }
         if (grad_probe && want_grad)
             ADM_HIP(probe_grad_reduce(p.grad_probe, batch, probe_elems, (float2*)grad_probe, plan->ctx->stream));
         return ADM_OK;
@@ -537,6 +563,7 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
 
 extern "C" int adm_plan_set_generic(adm_plan* plan, int on) {
     if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_generic: null plan");
+    if (plan->streamed) return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_generic: a streamed plan always runs the streamed kernels (adm_ms_streamed.hip)");
     const bool tuned = (plan->d.probe_y == plan->d.probe_x) && ms_threads_for(plan->d.probe_x) != 0;
     if (!on && !tuned) return fail(ADM_ERR_INVALID, "adm_plan_set_generic: this probe size has no tuned kernel");
     plan->generic = on != 0;
@@ -561,6 +588,7 @@ extern "C" int adm_probe_shift(adm_plan* plan, const float* probe, const float* 
                                float* probes_out) {
     if (!plan || !probe || !shifts || !probes_out) return fail(ADM_ERR_INVALID, "adm_probe_shift: null argument");
     if (batch <= 0) return fail(ADM_ERR_INVALID, "adm_probe_shift: batch must be positive");
+    if (plan->streamed) return fail(ADM_ERR_UNSUPPORTED, "adm_probe_shift: sub-pixel probe shifts are not implemented on streamed plans");
     if (plan->generic) return fail(ADM_ERR_UNSUPPORTED, "adm_probe_shift: sub-pixel probe shifts need one of the tuned probe sizes {8,12,16,18,24,27,32,36,64,72}");
     ShiftParams q;
     std::memset(&q, 0, sizeof(q));
@@ -578,6 +606,7 @@ extern "C" int adm_probe_shift_adj(adm_plan* plan, const float* probe, const flo
                                    float* grad_probes, float* grad_probe, float* grad_shifts) {
     if (!plan || !probe || !shifts || !grad_probes || !grad_shifts) return fail(ADM_ERR_INVALID, "adm_probe_shift_adj: null argument");
     if (batch <= 0) return fail(ADM_ERR_INVALID, "adm_probe_shift_adj: batch must be positive");
+    if (plan->streamed) return fail(ADM_ERR_UNSUPPORTED, "adm_probe_shift_adj: sub-pixel probe shifts are not implemented on streamed plans");
     if (plan->generic) return fail(ADM_ERR_UNSUPPORTED, "adm_probe_shift_adj: sub-pixel probe shifts need one of the tuned probe sizes {8,12,16,18,24,27,32,36,64,72}");
     ShiftParams q;
     std::memset(&q, 0, sizeof(q));

@@ -36,6 +36,7 @@ struct adm_plan {
     float* reg_stats;      // 2 floats of scratch for the real_imag L1 regulariser (lazily allocated)
     float* reg_partial;    // [obj_y*obj_x] per-row partial sums of the regulariser value (lazily allocated)
     bool generic;          // probe size outside the tuned kernels' set (or forced): adm_ms_generic.hip, pixel-major workspace rows
+    bool streamed;         // adm_plan_create_streamed: adm_ms_streamed.hip (fields in the workspace, row / column launches); generic is set too
     int gen_nrx, gen_nry, gen_rx[8], gen_ry[8];   // radix lists of the x / y transforms of the generic kernel
     float2* hs_dev;        // [Py*Px] H / (Py*Px), one rounding per element (generic kernel)
     float2* hfree_s_dev;   // same for the detector-plane Fresnel kernel, or nullptr
@@ -124,6 +125,11 @@ int multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, co
 bool ms_generic_supported(int py, int px);
 int ms_generic_threads(int py, int px);
 hipError_t ms_generic_launch(const MsParams& p, int batch, hipStream_t st);
+bool ms_streamed_supported(int py, int px);
+int ms_streamed_col_groups(int py, int px);
+size_t ws_off_field(const adm_plan* plan, int batch);
+// the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials
+hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st);
 hipError_t shift_launch(int n, const ShiftParams& q, int batch, bool adjoint, hipStream_t st);
 }  // namespace adm
 

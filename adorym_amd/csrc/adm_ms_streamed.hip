@@ -1,0 +1,360 @@
+// Multislice forward + loss + adjoint for probes of any size up to 2048 x 2048: the fields of all (position, mode) pairs live
+// in global memory ([B][M][Py][Px] complex, a section of the workspace) and every 2-D transform is a ROW launch and a COLUMN
+// launch over all of them, with the element-wise work fused into those launches.  Spread over the chip like that, a minibatch of
+// 32 positions of 256 x 256 fills every CU, where the one-workgroup-per-position kernels (adm_multislice.hip,
+// adm_ms_generic.hip) stop at 128 x 128 (the field must fit one workgroup's LDS).
+//
+// Mathematics: exactly ms_generic_kernel's (adm_ms_generic.hip), which is the specification -- the stash conventions, H / (Py*Px)
+// rounded once per element, det_scale / det_inverse, the fftshift-ed detector indexing, loss_term / loss_term_nz, det_weight,
+// pre_t, binning with a partial last bin, the three detector modes, tile gradients summed over the modes in ascending order, one
+// probe-gradient slot per position.  A 2-D transform here is the row transform and then the column transform (the inverse:
+// columns, then rows); the same line passes (gen_pass, run-time radix lists) as the generic kernel, so the roundings differ from
+// it only in the order of the two axes.
+//
+// Launch sequence of one minibatch, S = n_steps (4 S launches, + 2 each way for a Fresnel detector; far field, S = 1: four):
+//   forward   row(s):  [row IFFT of the previous convolution] * t_s -> stash, [row FFT of the next convolution / detector]
+//             col:     column FFT, * H / (Py*Px), column IFFT                        (between the steps)
+//             Fresnel detector: one more col (H_free) and a row launch with the row IFFT only
+//   detector  det:     per (b, column group), all modes: column transform, intensity over the modes, loss terms, pred,
+//                      dL/dPsi, per-group loss partials; then per mode the adjoint's first column transform
+//             reduce:  loss_sum[b] = the group partials of b in a fixed order
+//   adjoint   [Fresnel: a row launch with the row FFT, col with conj(H_free)]
+//             row(s), s descending: [pending row transform], tile gradient of step s (+= over the modes, in the workgroup),
+//                      * conj(t_s), then the row FFT of the next convolution -- or, at s = 0, the probe-gradient slot
+//             col:     the conj(H) convolution between the steps
+//   then probe_grad_reduce sums the slots (adm_api.hip).
+//
+// Row launches: one workgroup per (position, group of whole rows), all modes in turn (the slice factors are loaded once and the
+// tile gradient of the modes is summed in registers).  Column launches: one workgroup per (position, mode, 8 adjacent columns;
+// 4 beyond Py = 1024): every row of the group is a 64-byte (32-byte) run.  Workspace rows (stash, tile gradients) are pixel-major [Py][Px] like the generic
+// kernel's, so the cover lists and the overlap-add (TileGeom::pixel_major) serve both.
+#include <hip/hip_runtime.h>
+#include "adm_common.h"
+#include "adm_fft.h"
+#include "adm_ms_math.h"
+#include "adm_ms_gen.h"
+
+namespace adm {
+
+constexpr int ST_ROW_NT = 256;                 // threads of a row workgroup
+constexpr int ST_ROW_E = 8;                    // elements per thread in a row workgroup
+constexpr int ST_ROW_ELEMS = ST_ROW_NT * ST_ROW_E;   // whole rows, at most this many elements (one row of 2048 at the largest)
+constexpr int ST_MAX_SIDE = 2048;
+constexpr int ST_COL_NT = 512;                 // most threads of a column workgroup (GEN_E elements each)
+// adjacent columns of a column workgroup: 8 (64-byte runs per row) up to Py = 1024, 4 at larger Py (the group is at most
+// ST_COL_NT * GEN_E elements: with more threads the detector kernel's per-element state no longer fits the registers)
+__host__ __device__ __forceinline__ int st_cw(int py) { return py <= ST_COL_NT * GEN_E / 8 ? 8 : 4; }
+
+// row transform passes of the line group in LDS (INV: conjugate twiddles)
+template <bool INV, int E> __device__ __forceinline__ void st_row_fft(const GenCtx& g, const MsParams& p, cf (&v)[E]) {
+    int Ns = 1;
+    for (int s = 0; s < p.gen_nrx; ++s) { gen_pass<false, INV, E>(g, p.gen_rx[s], Ns, v); Ns *= p.gen_rx[s]; }
+}
+template <bool INV> __device__ __forceinline__ void st_col_fft(const GenCtx& g, const MsParams& p, cf (&v)[GEN_E]) {
+    int Ns = 1;
+    for (int s = 0; s < p.gen_nry; ++s) { gen_pass<true, INV>(g, p.gen_ry[s], Ns, v); Ns *= p.gen_ry[s]; }
+}
+// dir: 0 none, 1 forward, 2 inverse
+template <int E> __device__ __forceinline__ void st_row_dir(const GenCtx& g, const MsParams& p, int dir, cf (&v)[E]) {
+    if (dir == 1) st_row_fft<false>(g, p, v);
+    else if (dir == 2) st_row_fft<true>(g, p, v);
+}
+__device__ __forceinline__ void st_col_dir(const GenCtx& g, const MsParams& p, int dir, cf (&v)[GEN_E]) {
+    if (dir == 1) st_col_fft<false>(g, p, v);
+    else if (dir == 2) st_col_fft<true>(g, p, v);
+}
+
+struct StRow {
+    int rows;          // rows per workgroup
+    int step;          // modulation step (mode 1, 2)
+    int mode;          // 0 transforms only, 1 forward (modulation, stash), 2 adjoint (tile gradient, conjugate modulation)
+    int pre, post;     // row transform before / after the element-wise work: 0 none, 1 forward, 2 inverse
+    int from_probe;    // read the probe modes instead of the field buffer (first forward step)
+    int to_gprobe;     // write the position's probe-gradient slots instead of the field buffer (last adjoint step)
+};
+
+__global__ __launch_bounds__(ST_ROW_NT) void st_row_kernel(MsParams p, StRow r, float2* __restrict__ fld) {
+    __shared__ cf lds[ST_ROW_ELEMS + ST_MAX_SIDE];
+    const int Py = p.gen_py, Px = p.gen_px;
+    const int ngr = (Py + r.rows - 1) / r.rows;
+    const int b = blockIdx.x / ngr, r0 = (blockIdx.x - b * ngr) * r.rows;
+    GenCtx g;
+    g.Py = min(r.rows, Py - r0); g.Px = Px; g.n = g.Py * Px;
+    g.tid = threadIdx.x; g.nt = ST_ROW_NT;
+    g.ne = (g.n + g.nt - 1) / g.nt;
+    g.fld = lds;
+    cf* twx = lds + ST_ROW_ELEMS;
+    for (int i = g.tid; i < Px; i += g.nt) twx[i] = p.twid[i];
+    g.twx = twx; g.twy = nullptr;
+    const int M = p.n_modes;
+    const bool RI = p.real_imag != 0;
+    const size_t row = (size_t)Py * Px, per = (size_t)p.n_steps * row, off0 = (size_t)r0 * Px;
+    const int2 ps = p.pos[b];
+    const size_t slice_stride = (size_t)p.Yp * p.Xp;
+    const float2* tile = p.obj_rot + (size_t)(ps.x + p.pad_y0 + r0) * p.Xp + (ps.y + p.pad_x0);
+    cf v[ST_ROW_E], tv[ST_ROW_E];
+    float2 gacc[ST_ROW_E];
+    const float sk1 = p.sigma * p.k1;
+    for (int m = 0; m < M; ++m) {
+        const float2* src = r.from_probe ? p.probe + (size_t)m * row : fld + ((size_t)b * M + m) * row;
+        for (int i = g.tid; i < g.n; i += g.nt) lds[i] = src[off0 + i];
+        __syncthreads();
+        st_row_dir(g, p, r.pre, v);
+        if (r.mode != 0) {
+            float2* stash = p.stash + ((size_t)b * M + m) * per + (size_t)r.step * row + off0;
+#pragma unroll
+            for (int j = 0; j < ST_ROW_E; ++j) {
+                const int i = g.tid + j * g.nt;
+                if (j < g.ne && i < g.n) {
+                    if (m == 0) {       // the slice factor of this pixel, kept for the other modes
+                        const int y = i / Px;
+                        const float2 db = gen_slice(p, tile, slice_stride, r.step, (size_t)y * p.Xp + (i - y * Px));
+                        tv[j] = (RI || p.pre_t) ? db : gen_modulator(db, p.k1, p.sigma);
+                    }
+                    cf a = lds[i];
+                    if (r.mode == 1) {
+                        if (RI) {
+                            if (p.want_grad) stash[i] = a;      // pre-modulation field
+                            a = cmul(a, tv[j]);
+                        } else {
+                            a = cmul(a, tv[j]);
+                            if (p.want_grad) stash[i] = a;      // post-modulation field
+                        }
+                    } else {
+                        const cf psi = stash[i];
+                        const float zr = a.x * psi.x + a.y * psi.y;
+                        const float zi = a.x * psi.y - a.y * psi.x;
+                        float2 gr = make_float2(RI ? zr : sk1 * zi, RI ? -zi : -p.k1 * zr);
+                        if (m > 0) { gr.x += gacc[j].x; gr.y += gacc[j].y; }
+                        gacc[j] = gr;
+                        a = cmulc(a, tv[j]);
+                    }
+                    lds[i] = a;
+                }
+            }
+            __syncthreads();
+        }
+        st_row_dir(g, p, r.post, v);
+        float2* dst = fld + ((size_t)b * M + m) * row;
+        if (r.to_gprobe) dst = p.grad_probe ? p.grad_probe + (size_t)b * p.gprobe_bstride + (size_t)m * row : nullptr;
+        if (dst)
+            for (int i = g.tid; i < g.n; i += g.nt) dst[off0 + i] = lds[i];
+        __syncthreads();
+    }
+    if (r.mode == 2) {
+        float2* gtile = p.gtile + (size_t)b * per + (size_t)r.step * row + off0;
+#pragma unroll
+        for (int j = 0; j < ST_ROW_E; ++j) {
+            const int i = g.tid + j * g.nt;
+            if (j < g.ne && i < g.n) gtile[i] = gacc[j];
+        }
+    }
+}
+
+// LDS of a column workgroup: the [Py][cw] group, then W_Py^j
+__device__ __forceinline__ void st_col_ctx(GenCtx& g, cf* lds, const MsParams& p, int c0, int cw) {
+    g.Py = p.gen_py; g.Px = min(cw, p.gen_px - c0); g.n = g.Py * g.Px;
+    g.tid = threadIdx.x; g.nt = blockDim.x;
+    g.ne = (g.n + g.nt - 1) / g.nt;
+    g.fld = lds;
+    cf* twy = lds + (size_t)g.Py * cw;
+    for (int i = g.tid; i < g.Py; i += g.nt) twy[i] = p.gen_twid_y[i];
+    g.twx = nullptr; g.twy = twy;
+}
+__device__ __forceinline__ void st_col_load(const GenCtx& g, const float2* f, int Px, int c0) {
+    for (int i = g.tid; i < g.n; i += g.nt) {
+        const int y = i / g.Px;
+        g.fld[i] = f[(size_t)y * Px + c0 + (i - y * g.Px)];
+    }
+}
+__device__ __forceinline__ void st_col_store(const GenCtx& g, float2* f, int Px, int c0) {
+    for (int i = g.tid; i < g.n; i += g.nt) {
+        const int y = i / g.Px;
+        f[(size_t)y * Px + c0 + (i - y * g.Px)] = g.fld[i];
+    }
+}
+
+// field <- column IFFT( H * column FFT(field) ) for one (position, mode, column group); hs = H / (Py*Px) (CONJ: conj)
+template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_kernel(MsParams p, float2* __restrict__ fld, const float2* __restrict__ hs) {
+    extern __shared__ cf st_lds[];
+    const int Px = p.gen_px, cw = st_cw(p.gen_py), ncg = (Px + cw - 1) / cw;
+    const int bm = blockIdx.x / ncg, c0 = (blockIdx.x - bm * ncg) * cw;
+    GenCtx g;
+    st_col_ctx(g, st_lds, p, c0, cw);
+    float2* f = fld + (size_t)bm * p.gen_py * Px;
+    st_col_load(g, f, Px, c0);
+    __syncthreads();
+    cf v[GEN_E];
+    st_col_fft<false>(g, p, v);
+#pragma unroll
+    for (int j = 0; j < GEN_E; ++j) {
+        const int i = g.tid + j * g.nt;
+        if (j < g.ne && i < g.n) {
+            const int y = i / g.Px;
+            g.fld[i] = cmul_t<CONJ>(g.fld[i], hs[(size_t)y * Px + c0 + (i - y * g.Px)]);
+        }
+    }
+    __syncthreads();
+    st_col_fft<true>(g, p, v);
+    st_col_store(g, f, Px, c0);
+}
+
+// detector plane of one (position, column group), all modes: column transform, loss, pred, dL/dPsi, adjoint column transform
+__global__ __launch_bounds__(ST_COL_NT) void st_det_kernel(MsParams p, float2* __restrict__ fld, float* __restrict__ part) {
+    extern __shared__ cf st_lds[];
+    __shared__ float red[ST_COL_NT / 64];
+    const int Py = p.gen_py, Px = p.gen_px, cw = st_cw(Py), ncg = (Px + cw - 1) / cw;
+    const int b = blockIdx.x / ncg, cg = blockIdx.x - b * ncg, c0 = cg * cw;
+    GenCtx g;
+    st_col_ctx(g, st_lds, p, c0, cw);
+    const int M = p.n_modes;
+    const bool far = p.det_mode == ADM_DET_FARFIELD_;
+    const int fwd_dir = far ? (p.det_inverse ? 2 : 1) : 0, adj_dir = far ? (p.det_inverse ? 1 : 2) : 0;
+    const size_t row = (size_t)Py * Px;
+    cf v[GEN_E];
+    // per element: the intensity summed over the modes, then the factor g of dL/dPsi = g * Psi (LDS, behind the twiddles: in
+    // registers the detector state spills)
+    float* gf = reinterpret_cast<float*>(st_lds + (size_t)Py * cw + Py);
+    auto gidx = [&](int i) { const int y = i / g.Px; return (size_t)y * Px + c0 + (i - y * g.Px); };
+    for (int m = 0; m < M; ++m) {
+        if (m > 0) __syncthreads();
+        st_col_load(g, fld + ((size_t)b * M + m) * row, Px, c0);
+        __syncthreads();
+        st_col_dir(g, p, fwd_dir, v);
+        if (M > 1) {
+            float2* dq = p.det + ((size_t)b * M + m) * row;
+#pragma unroll
+            for (int j = 0; j < GEN_E; ++j) {
+                const int i = g.tid + j * g.nt;
+                if (j < g.ne && i < g.n) {
+                    const cf psi = far ? cscale(g.fld[i], p.det_scale) : g.fld[i];
+                    const float q = psi.x * psi.x + psi.y * psi.y;
+                    gf[i] = m > 0 ? gf[i] + q : q;
+                    dq[gidx(i)] = psi;
+                }
+            }
+        }
+    }
+    float lsum = 0.f;
+#pragma unroll
+    for (int j = 0; j < GEN_E; ++j) {
+        const int i = g.tid + j * g.nt;
+        if (j < g.ne && i < g.n) {
+            const int ky = i / g.Px, kx = c0 + (i - ky * g.Px);
+            // far field: natural-order spectrum element (ky, kx) is the fftshifted detector pixel ((ky + Py/2) % Py, ...)
+            const int my = far ? (ky + Py / 2) % Py : ky, mx = far ? (kx + Px / 2) % Px : kx;
+            const size_t di = ((size_t)b * Py + my) * Px + mx;
+            const float wq = p.det_weight ? p.det_weight[my * Px + mx] : 1.f;
+            float mag;
+            if (M > 1) mag = sqrtf(gf[i]);
+            else {
+                const cf psi = far ? cscale(g.fld[i], p.det_scale) : g.fld[i];
+                mag = sqrtf(psi.x * psi.x + psi.y * psi.y);
+            }
+            float gg;
+            lsum += wq * (M > 1 ? loss_term_nz(mag, p.target[di], p, gg) : loss_term(mag, p.target[di], p, gg));
+            if (p.pred) p.pred[di] = mag;
+            gf[i] = wq * gg;
+        }
+    }
+    {
+        const float s = gen_block_sum(lsum, red, g.tid, g.nt);
+        if (g.tid == 0) part[blockIdx.x] = s;
+    }
+    if (!p.want_grad) return;
+    for (int m = 0; m < M; ++m) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < GEN_E; ++j) {
+            const int i = g.tid + j * g.nt;
+            if (j < g.ne && i < g.n) {
+                // Psi = scale * F(psi): the adjoint of (scale * F) applied to g * Psi is scale * F^H (g * scale * F psi)
+                const cf psi = (M > 1) ? p.det[((size_t)b * M + m) * row + gidx(i)] : (far ? cscale(g.fld[i], p.det_scale) : g.fld[i]);
+                g.fld[i] = cscale(psi, gf[i] * (far ? p.det_scale : 1.f));
+            }
+        }
+        __syncthreads();
+        st_col_dir(g, p, adj_dir, v);
+        st_col_store(g, fld + ((size_t)b * M + m) * row, Px, c0);
+    }
+}
+
+// loss_sum[b] = the column-group partials of position b, ascending (loss_sum may be host-mapped memory)
+__global__ __launch_bounds__(256) void st_loss_reduce_kernel(const float* __restrict__ part, int ncg, int batch, float* loss_sum) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= batch) return;
+    float s = 0.f;
+    for (int c = 0; c < ncg; ++c) s += part[(size_t)b * ncg + c];
+    loss_sum[b] = s;
+}
+
+bool ms_streamed_supported(int py, int px) { return py >= 1 && px >= 1 && py <= ST_MAX_SIDE && px <= ST_MAX_SIDE; }
+int ms_streamed_col_groups(int py, int px) { return (px + st_cw(py) - 1) / st_cw(py); }
+static int st_col_threads(int py) {
+    const int n = py * st_cw(py);
+    int nt = ((n + GEN_E - 1) / GEN_E + 63) / 64 * 64;
+    if (nt < 256) nt = 256;
+    return nt;
+}
+
+hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st) {
+    const int Py = p.gen_py, Px = p.gen_px, S = p.n_steps, M = p.n_modes;
+    if (!ms_streamed_supported(Py, Px)) return hipErrorInvalidValue;
+    const bool far = p.det_mode == ADM_DET_FARFIELD_, fresnel = p.det_mode == ADM_DET_FRESNEL_;
+    int rows = ST_ROW_ELEMS / Px;
+    if (rows < 1) rows = 1;
+    if (rows > Py) rows = Py;
+    const int ngr = (Py + rows - 1) / rows, ncg = ms_streamed_col_groups(Py, Px);
+    const int cnt = st_col_threads(Py);
+    const size_t clds = ((size_t)Py * st_cw(Py) + Py) * sizeof(float2);
+    static bool attr_set = false;
+    if (!attr_set) {
+        const int lim = 160 * 1024 - 256;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_det_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    auto row = [&](int step, int mode, int pre, int post, int from_probe, int to_gprobe) {
+        StRow r;
+        r.rows = rows; r.step = step; r.mode = mode; r.pre = pre; r.post = post; r.from_probe = from_probe; r.to_gprobe = to_gprobe;
+        hipLaunchKernelGGL(st_row_kernel, dim3(batch * ngr), dim3(ST_ROW_NT), 0, st, p, r, fld);
+        return hipGetLastError();
+    };
+    auto col = [&](const float2* h, bool conj) {
+        if (conj) hipLaunchKernelGGL(st_col_conv_kernel<true>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h);
+        else hipLaunchKernelGGL(st_col_conv_kernel<false>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h);
+        return hipGetLastError();
+    };
+    hipError_t e = hipSuccess;
+    // ---------------- forward ----------------
+    const int det_row = far ? (p.det_inverse ? 2 : 1) : (fresnel ? 1 : 0);     // the row transform that starts the detector propagation
+    for (int s = 0; s < S && e == hipSuccess; ++s) {
+        e = row(s, 1, s > 0 ? 2 : 0, s < S - 1 ? 1 : det_row, s == 0, 0);
+        if (e == hipSuccess && s < S - 1) e = col(p.gen_hs, false);
+    }
+    if (e == hipSuccess && fresnel) {
+        e = col(p.gen_hfree_s, false);
+        if (e == hipSuccess) e = row(0, 0, 2, 0, 0, 0);
+    }
+    if (e != hipSuccess) return e;
+    // ---------------- detector, loss ----------------
+    hipLaunchKernelGGL(st_det_kernel, dim3(batch * ncg), dim3(cnt), clds + (size_t)Py * st_cw(Py) * sizeof(float), st, p, fld, part);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(st_loss_reduce_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, part, ncg, batch, p.loss_sum);
+    if ((e = hipGetLastError()) != hipSuccess || !p.want_grad) return e;
+    // ---------------- adjoint ----------------
+    if (fresnel) {
+        e = row(0, 0, 1, 0, 0, 0);
+        if (e == hipSuccess) e = col(p.gen_hfree_s, true);
+    }
+    const int adj_row = far ? (p.det_inverse ? 1 : 2) : (fresnel ? 2 : 0);
+    for (int s = S - 1; s >= 0 && e == hipSuccess; --s) {
+        e = row(s, 2, s == S - 1 ? adj_row : 2, s > 0 ? 1 : 0, 0, s == 0);
+        if (e == hipSuccess && s > 0) e = col(p.gen_hs, true);
+    }
+    return e;
+}
+
+}  // namespace adm

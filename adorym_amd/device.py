@@ -303,7 +303,10 @@ class Plan(object):
     """adm_plan: object/probe geometry, padding, physics constants and transfer functions."""
 
     def __init__(self, ctx, obj_size, probe_size, pads, k1, h, binning=1, n_modes=1, sign_convention=1,
-                 det_mode=_lib.DET_FARFIELD, normalize_fft=False, h_free=None, loss_type=_lib.LOSS_LSQ, poisson_multiplier=1.0, unknown_type='delta_beta'):
+                 det_mode=_lib.DET_FARFIELD, normalize_fft=False, h_free=None, loss_type=_lib.LOSS_LSQ, poisson_multiplier=1.0, unknown_type='delta_beta',
+                 streamed=False):
+        """``streamed``: adm_plan_create_streamed (adm_ms_streamed.hip: fields in the workspace, row / column launches over the
+        minibatch; sides up to 2048) instead of adm_plan_create (one workgroup per position, the field in LDS)."""
         self.ctx = ctx
         d = _lib.PlanDesc()
         d.obj_y, d.obj_x, d.obj_z = [int(v) for v in obj_size]
@@ -322,8 +325,10 @@ class Plan(object):
             self._hf = (np.ascontiguousarray(hf.real, dtype=np.float32), np.ascontiguousarray(hf.imag, dtype=np.float32))
             d.hfree_re, d.hfree_im = _fptr(self._hf[0]), _fptr(self._hf[1])
         p = C.c_void_p()
-        check(ctx.lib.adm_plan_create(ctx.handle, C.byref(d), C.byref(p)))
+        create = ctx.lib.adm_plan_create_streamed if streamed else ctx.lib.adm_plan_create
+        check(create(ctx.handle, C.byref(d), C.byref(p)))
         self.handle = p
+        self.streamed = bool(streamed)
         self.desc = d
         self.obj_size = (d.obj_y, d.obj_x, d.obj_z)
         self.probe_size = (d.probe_y, d.probe_x)

@@ -122,10 +122,18 @@ class MultisliceEngine(object):
     def __init__(self, ctx, obj_size, probe_size, probe_pos, energy_ev, psize_cm, free_prop_cm='inf', binning=1,
                  fresnel_approx=True, sign_convention=1, normalize_fft=False, kernel=None, scale_ri_by_k=True,
                  n_probe_modes=1, max_batch=None, loss_function_type='lsq', poisson_multiplier=1., unknown_type='delta_beta',
-                 beamstop=None, generic=False, transmission_cache=True, transmissions_only=False):
+                 beamstop=None, generic=False, transmission_cache=True, transmissions_only=False, streamed=False,
+                 workspace_budget=4 << 30):
         """``free_prop_cm``: 0 / None (exit wave), 'inf' (far field), a distance in cm (Fresnel propagation to the detector), or
         a SEQUENCE of n distances: position b of every launch is propagated to distance b % n (multi-distance data divided into
-        sub-tiles, adorym/forward_model.py:999-1018 -- the caller lists every tile n times in a row, ``n_dists`` = n)."""
+        sub-tiles, adorym/forward_model.py:999-1018 -- the caller lists every tile n times in a row, ``n_dists`` = n).
+
+        ``streamed``: False -- the one-workgroup-per-position kernels (probes up to 128 x 128); True -- the streamed kernels
+        (adm_ms_streamed.hip: sides up to 2048, fields in the workspace); 'auto' -- the former where adm_plan_create accepts the
+        probe size, else the latter.  ``self.streamed`` tells which.  A streamed engine runs a batch in rounds whose workspace
+        fits ``workspace_budget`` bytes (a position keeps n_steps * Py * Px complex numbers per mode: 134 MB at 256 x 256 and
+        256 slices); each round is overlap-added before the next reuses the workspace.  Streamed engines take one probe set
+        shared by all positions: no ``shifts`` / ``probes_b`` and no multi-distance sequence."""
         self.ctx = ctx
         self.obj_size = tuple(int(v) for v in obj_size)
         self.probe_size = tuple(int(v) for v in probe_size)
@@ -156,15 +164,25 @@ class MultisliceEngine(object):
             # fresnel_propagate always builds the Fresnel-approx kernel (adorym/propagate.py:537-546)
             h_free = get_kernel(float(free_prop_cm) * 1e7, lmbda_nm, voxel_nm, self.probe_size,
                                 sign_convention=sign_convention)
-        self.plan = Plan(ctx, self.obj_size, self.probe_size, pads, self.k1, kernel, binning=binning,
-                         n_modes=n_probe_modes, sign_convention=sign_convention, det_mode=det,
-                         normalize_fft=normalize_fft, h_free=h_free,
-                         loss_type={'lsq': _lib.LOSS_LSQ, 'poisson': _lib.LOSS_POISSON}[loss_function_type],
-                         poisson_multiplier=poisson_multiplier, unknown_type=unknown_type)
+        if streamed not in (False, True, 'auto'):
+            raise ValueError("streamed must be False, True or 'auto', got %r" % (streamed,))
+        plan_kw = dict(binning=binning, n_modes=n_probe_modes, sign_convention=sign_convention, det_mode=det, normalize_fft=normalize_fft,
+                       h_free=h_free, loss_type={'lsq': _lib.LOSS_LSQ, 'poisson': _lib.LOSS_POISSON}[loss_function_type],
+                       poisson_multiplier=poisson_multiplier, unknown_type=unknown_type)
+        self.plan = None
+        if streamed == 'auto':
+            try:
+                self.plan = Plan(ctx, self.obj_size, self.probe_size, pads, self.k1, kernel, **plan_kw)
+            except NotImplementedError:
+                pass                          # (too large for one workgroup's LDS: the streamed plan below)
+        if self.plan is None:
+            self.plan = Plan(ctx, self.obj_size, self.probe_size, pads, self.k1, kernel, streamed=bool(streamed), **plan_kw)
+        self.streamed = self.plan.streamed
+        self.workspace_budget = int(workspace_budget)
         if dists and len(dists) > 1:
             self.plan.set_detector_kernels([get_kernel(d_ * 1e7, lmbda_nm, voxel_nm, self.probe_size, sign_convention=sign_convention)
                                             for d_ in dists])
-        if generic:
+        if generic and not self.streamed:
             self.plan.set_generic(True)       # the any-size kernel even where a tuned one exists (tests, A/B timing)
         # slice transmissions cached per rotated-frame voxel by rotate() (include/adm.h: adm_plan_set_transmission_cache)
         self.transmission_cache = bool(transmission_cache) and unknown_type == 'delta_beta' and binning == 1
@@ -201,11 +219,28 @@ class MultisliceEngine(object):
             self._reserve(max_batch)
 
     # -------------------------------------------------------------------------------- buffers
+    def round_cap(self):
+        """Streamed engines: the most positions one launch takes within ``workspace_budget`` (at least one)."""
+        one, two = self.plan.workspace_bytes(1), self.plan.workspace_bytes(2)
+        per = two - one                       # (the workspace is a fixed part -- the cover lists -- plus a part per position)
+        return max(1, (self.workspace_budget - (one - per)) // per)
+
+    def rounds(self, B):
+        """(offset, count) of the launches a batch of B positions takes: one, or for a streamed engine as many equal rounds as
+        the workspace budget asks for."""
+        n_rounds = -(-B // self.round_cap()) if self.streamed else 1
+        if n_rounds == 1:
+            return [(0, B)]
+        sizes = [B // n_rounds + (1 if i < B % n_rounds else 0) for i in range(n_rounds)]
+        bounds = [0] + [int(v) for v in np.cumsum(sizes)]
+        return [(bounds[i], bounds[i + 1] - bounds[i]) for i in range(n_rounds)]
+
     def _reserve(self, batch):
         if batch <= self.max_batch:
             return
         Py, Px = self.probe_size
-        self._ws = DeviceArray(self.ctx, (self.plan.workspace_bytes(batch),), np.uint8)
+        ws_batch = min(batch, self.round_cap()) if self.streamed else batch      # streamed: one round's workspace
+        self._ws = DeviceArray(self.ctx, (self.plan.workspace_bytes(ws_batch),), np.uint8)
         self._pos = DeviceArray(self.ctx, (batch, 2), np.int32)
         self._target = DeviceArray(self.ctx, (batch, Py, Px), np.float32)
         self._pred = DeviceArray(self.ctx, (batch, Py, Px), np.float32)
@@ -338,7 +373,14 @@ class MultisliceEngine(object):
         if grad_scale is None:
             grad_scale = 2.0 / (B * self.n_det)       # d mean((pred-target)^2) / d pred
         lib = self.ctx.lib
+        if self.streamed and (shifts is not None or probes_b is not None):
+            raise NotImplementedError('streamed multislice (probe %dx%d): sub-pixel probe shifts and per-position probes are not '
+                                      'implemented on the streamed path' % (Py, Px))
+        self._acc_done = False
         self._next_loss_buffer()
+        if self.streamed and len(self.rounds(B)) > 1:
+            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale)
+            return
         if probes_b is not None:
             if shifts is not None or grad_probe is not None:
                 raise ValueError('probes_b excludes shifts and grad_probe')
@@ -375,6 +417,37 @@ class MultisliceEngine(object):
         if want_grad and accumulate:
             self.accumulate_tiles()
 
+    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale):
+        """A streamed engine's batch that does not fit the workspace budget: one launch per round into the same workspace, each
+        round's tile gradients overlap-added into grad_rot (zeroed first) before the next round overwrites them.  Losses,
+        predictions and the probe gradient are those of one launch; the object gradient too, up to the order of the additions."""
+        lib, h, B = self.ctx.lib, self.plan.handle, self._B
+        Py, Px = self.probe_size
+        ws = self._ws
+        gp = grad_probe.ptr if grad_probe is not None else None
+        pr = self._pred.ptr if want_pred else None
+        if want_grad:
+            check(lib.adm_memset(self.ctx.handle, self.grad_rot.ptr, 0, self.grad_rot.nbytes))
+        for o, n in self.rounds(B):
+            check(lib.adm_multislice_fwd_adj(h, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr + 8 * o, n,
+                                             self._cur_target.ptr + 4 * o * Py * Px, 1 if want_grad else 0, gp,
+                                             (pr + 4 * o * Py * Px) if pr else None, self._loss.ptr + 4 * o, float(grad_scale),
+                                             ws.ptr, ws.nbytes))
+            if not want_grad:
+                continue
+            pos_host = np.ascontiguousarray(self._pos_host[o:o + n])
+            if self._check_cover(pos_host) > self.MAX_COVER:
+                for lo in range(0, n, self.MAX_COVER):
+                    check(lib.adm_tile_grad_accumulate_range(h, ws.ptr, ws.nbytes, self._cur_pos.ptr + 8 * o, n, pos_host.ctypes.data,
+                                                             self.grad_rot.ptr, lo, min(lo + self.MAX_COVER, n), 1))
+            else:
+                check(lib.adm_tile_grad_accumulate_part(h, ws.ptr, ws.nbytes, self._cur_pos.ptr + 8 * o, n, pos_host.ctypes.data,
+                                                        self.grad_rot.ptr, 0, 0, 1))
+        # (every overlap-add above saw at most MAX_COVER tiles per pixel: nothing to check afterwards)
+        self._acc_done = want_grad
+        self._accumulated = want_grad
+        self._acc_parts = []
+
     MAX_COVER = 64        # ADM_MAXCOVER of adm_object.hip: cover-list entries per rotated-frame pixel
 
     def _check_cover(self, pos):
@@ -406,8 +479,8 @@ class MultisliceEngine(object):
         """Queue the cover lists of the overlap-add of the batch given to set_batch() NOW (they depend on the positions only):
         called inside Context.fork()/end_fork(), they are built beside the multislice launch and accumulate_tiles() -- after
         Context.join() -- skips its own build: one launch and one dependency gap less behind the kernel."""
-        if self._check_cover(self._pos_host) > self.MAX_COVER:
-            return                  # (the multi-pass overlap-add builds a list per pass)
+        if self._check_cover(self._pos_host) > self.MAX_COVER or (self.streamed and len(self.rounds(self._B)) > 1):
+            return                  # (the multi-pass overlap-add and the rounds of a streamed batch build a list per pass)
         check(self.ctx.lib.adm_tile_cover_build(self.plan.handle, self._ws.ptr, self._ws.nbytes, self._cur_pos.ptr, self._B,
                                                 self._pos_host.ctypes.data, 0, 0, 0))
 
@@ -415,6 +488,8 @@ class MultisliceEngine(object):
         """Overlap-add the per-position tile gradients into the batch's rows of grad_rot.  A batch in which some pixel is covered
         by more than MAX_COVER tiles (a dense 2-D scan taken as one minibatch) is added in passes of MAX_COVER positions each."""
         lib, B = self.ctx.lib, self._B
+        if getattr(self, '_acc_done', False):
+            return                  # (a streamed batch launched in rounds was overlap-added round by round)
         if self._check_cover(self._pos_host) > self.MAX_COVER:
             for k, lo in enumerate(range(0, B, self.MAX_COVER)):
                 check(lib.adm_tile_grad_accumulate_range(self.plan.handle, self._ws.ptr, self._ws.nbytes, self._cur_pos.ptr, B,
@@ -436,7 +511,8 @@ class MultisliceEngine(object):
         i runs on the side stream BESIDE the launch of round i+1 -- in particular beside a short last round that leaves most
         CUs idle.  Same sums as one launch + one overlap-add, up to the order of the additions per pixel."""
         B = self._B
-        if B <= self.N_CU or self._check_cover(self._pos_host) > self.MAX_COVER:
+        if B <= self.N_CU or self._check_cover(self._pos_host) > self.MAX_COVER or self.streamed:
+            # (a streamed engine spreads every launch over the chip already; its rounds are sized by memory, in multislice)
             # (a batch denser than the cover lists hold is one launch followed by the multi-pass overlap-add)
             self.multislice(probe, grad_probe=grad_probe, want_grad=True, want_pred=want_pred, grad_scale=grad_scale)
             self.ctx.join()                   # side-stream work the caller queued before the launch (no-op if none)

@@ -495,7 +495,13 @@ class _Run(object):
                 n_probe_modes=self.n_probe_modes, max_batch=self.minibatch_size, loss_function_type=self.loss_function_type,
                 poisson_multiplier=self.poisson_multiplier, beamstop=self.beamstop,
                 # the rotation stores slice transmissions only; rotate_out_of_loop and plugin models read obj_rot
-                transmissions_only=(self.forward_model == 'auto' and not self.rotate_out_of_loop), **common)
+                transmissions_only=(self.forward_model == 'auto' and not self.rotate_out_of_loop),
+                # probes too large for one workgroup's LDS (beyond 128 x 128) take the streamed kernels
+                streamed='auto', **common)
+            # the rule of _shift_args (forward_model.py): sub-pixel shifts when the corrections are optimised or one exceeds 1e-3
+            _not_implemented(self.engine.streamed and (self.optimize_all_probe_pos or bool(np.any(self.probe_pos - self.probe_pos_int > 1e-3))),
+                             'sub-pixel probe positions (optimize_all_probe_pos or fractional probe_pos) with a %d x %d probe '
+                             '(streamed multislice)' % tuple(probe_size))
         tables, theta_ls = {}, self.theta_ls
 
         def rotation_tables(i_theta):

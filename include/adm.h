@@ -206,6 +206,12 @@ typedef struct {
 } adm_plan_desc;
 
 int adm_plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out);
+/* A STREAMED plan (adm_ms_streamed.hip): the same descriptor and checks as adm_plan_create, for probes with sides up to 2048
+ * (under the generic kernel's factoriser rule: at most 8 prime-power factors per side) whatever LDS they would take.
+ * The fields of all (position, mode) pairs live in the workspace and every transform is a row launch and a column launch
+ * over the whole minibatch (4 * n_steps launches, 4 more with a Fresnel detector).  Small sizes are accepted too (tests force this path where the
+ * one-workgroup kernels exist).  See "Probe sizes" below for what a streamed plan runs. */
+int adm_plan_create_streamed(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out);
 int adm_plan_destroy(adm_plan* plan);
 /* Beamstop (adorym/forward_model.py:128-136): host float [Py][Px] in the detector layout of the data; pixels with
  * mask >= 1e-5 take part in the loss, the others are dropped.  The per-position loss sums then run over the kept pixels only
@@ -319,12 +325,17 @@ int adm_multislice_fwd_adj(adm_plan* plan, const float* obj_rot, const float* pr
  * image the cache holds; adm_multislice_fwd_adj then refuses an obj_rot the cache was not filled from. */
 int adm_plan_set_transmission_cache(adm_plan* plan, int on);
 int adm_transmission_refresh(adm_plan* plan, const float* obj_rot, int y_lo, int y_hi);
-/* Probe sizes.  Any Py x Px with Py*Px <= 16384 whose field fits the LDS is accepted (the reference takes whatever
+/* Probe sizes.  adm_plan_create accepts any Py x Px with Py*Px <= 16384 whose field fits the LDS (the reference takes whatever
  * prj.shape[-2:] is, adorym/ptychography.py:313-317).  Square sizes in {8,12,16,18,24,27,32,36,64,72} run the tuned
  * register-resident kernels; every other size -- and every size after adm_plan_set_generic(plan, 1) -- runs the generic
  * kernel (adm_ms_generic.hip: run-time radix lists, any prime factors, non-square).  Call it before the first workspace is
  * sized: the two kernels lay their workspace rows out differently.  Per-position probes (adm_multislice_fwd_adj_pp,
- * adm_probe_shift*) exist for the tuned sizes only. */
+ * adm_probe_shift*) exist for the tuned sizes only.
+ * Larger probes (sides up to 2048) take a plan of adm_plan_create_streamed.  It keeps the contracts of adm_multislice_fwd_adj
+ * (whose workspace it always needs, want_grad = 0 included: the fields live there), adm_plan_workspace_bytes, the cover build
+ * and the overlap-add (pixel-major rows, like the generic kernel's), rotation, the transmission cache and the detector mask.
+ * It refuses with ADM_ERR_UNSUPPORTED: adm_multislice_fwd_adj_pp and adm_probe_shift* (per-position and sub-pixel shifted
+ * probes), adm_plan_set_detector_kernels with n > 1 (which needs per-position probes) and adm_plan_set_generic. */
 int adm_plan_set_generic(adm_plan* plan, int on);
 
 /* Same as adm_multislice_fwd_adj with ONE PROBE SET PER POSITION (sub-pixel probe positions, adorym/forward_model.py:
