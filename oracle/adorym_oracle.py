@@ -142,6 +142,19 @@ def _sample_setup(coords_fp16, X, Z, dtype):
     return ix0, ix1, iz0, iz1, w00, w01, w10, w11, v_x1, v_z1
 
 
+def rotation_weights(coords_fp16, X, Z, dtype='float32'):
+    """The sampling operator of one angle as numbers: ``idx`` int64 [4, X*Z] (object-plane voxel x*Z + z of the four corners
+    of rotated-frame voxel p = x'*Z + z', clamped to the plane) and ``w`` [4, X*Z] in ``dtype`` (the weights of
+    _sample_setup, zero where the corner lies outside the plane): what rotate_fwd gathers with and rotate_adj scatters with.
+    For checkers that redo the sums themselves (in another precision or order)."""
+    ix0, ix1, iz0, iz1, w00, w01, w10, w11, vx1, vz1 = _sample_setup(coords_fp16, X, Z, dtype)
+    ix1c = np.minimum(ix1, X - 1)
+    iz1c = np.minimum(iz1, Z - 1)
+    idx = np.stack([ix0 * Z + iz0, ix0 * Z + iz1c, ix1c * Z + iz0, ix1c * Z + iz1c])
+    w = np.stack([w00, np.where(vz1, w01, 0), np.where(vx1, w10, 0), np.where(vx1 & vz1, w11, 0)]).astype(dtype)
+    return idx, w
+
+
 def rotate_fwd(obj, coords_fp16, dtype=None):
     """R2: apply_rotation (util.py:536-552).  obj [Y,X,Z,C] -> rotated [Y,X,Z,C]."""
     dtype = obj.dtype if dtype is None else dtype
