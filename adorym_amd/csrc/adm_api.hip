@@ -311,6 +311,11 @@ static int plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out, 
     p->trans_dev = nullptr;
     p->trans_src = nullptr;
     p->trans_only = false;
+    p->zpos_dev = nullptr;
+    p->n_zpos = 0;
+    p->zpos_dirty = false;
+    p->sp_hs_dev = nullptr;
+    p->sp_a_dev = nullptr;
     std::memset(p->cover_keys, 0, sizeof(p->cover_keys));
     p->generic = !tuned;
     p->streamed = streamed;
@@ -378,6 +383,8 @@ extern "C" int adm_plan_destroy(adm_plan* plan) {
     if (plan->reg_partial) (void)hipFree(plan->reg_partial);
     if (plan->trans_dev) (void)hipFree(plan->trans_dev);
     if (plan->det_weight_dev) adm_free(plan->ctx, plan->det_weight_dev);
+    if (plan->sp_hs_dev) adm_free(plan->ctx, plan->sp_hs_dev);
+    if (plan->sp_a_dev) adm_free(plan->ctx, plan->sp_a_dev);
     delete plan;
     return ADM_OK;
 }
@@ -435,12 +442,17 @@ extern "C" size_t adm_plan_rot_elems(const adm_plan* plan) {
 extern "C" size_t adm_plan_workspace_bytes(const adm_plan* plan, int batch) {
     if (!plan || batch <= 0) return 0;
     // [stash: B*M*per | tile gradients: B*per | cover lists (Yp*Xp*(1+64) u32) + overflow flag | detector fields: B*M*G*NT |
-    //  per-position probe gradients: B*M*Py*Px | streamed plans: fields B*M*Py*Px, loss partials B*column groups floats]
+    //  per-position probe gradients: B*M*Py*Px | streamed plans: fields B*M*Py*Px, loss partials B*column groups floats |
+    //  streamed plans with slice positions: kept spectra B*M*(S-1)*Py*Px, dL/dd partials (S-1)*B*M*column groups doubles]
     const size_t per = adm::ms_ws_per_pos(plan) * sizeof(float2);
     const size_t det = adm::ws_det_bytes(plan, batch);
     const size_t gpp = (size_t)batch * plan->d.n_modes * plan->d.probe_y * plan->d.probe_x * sizeof(float2);
     const size_t streamed = plan->streamed ? gpp + (size_t)batch * adm::ms_streamed_col_groups(plan->d.probe_y, plan->d.probe_x) * sizeof(float) : 0;
-    return (size_t)batch * (plan->d.n_modes + 1) * per + (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64 + det + gpp + streamed;
+    const size_t base = (size_t)batch * (plan->d.n_modes + 1) * per + (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64 + det + gpp + streamed;
+    if (!plan->streamed || plan->n_zpos < 2) return base;
+    const size_t n_conv = (size_t)plan->n_zpos - 1;
+    return adm::ws_off_sparse(plan, batch) + n_conv * gpp
+           + n_conv * batch * plan->d.n_modes * adm::ms_streamed_col_groups(plan->d.probe_y, plan->d.probe_x) * sizeof(double);
 }
 
 namespace adm {
@@ -464,11 +476,63 @@ size_t ws_off_gprobe(const adm_plan* plan, int batch) { return ws_off_det(plan, 
 size_t ws_off_field(const adm_plan* plan, int batch) {      // streamed plans: [B][M][Py][Px] fields, then the loss partials
     return ws_off_gprobe(plan, batch) + (size_t)batch * plan->d.n_modes * plan->d.probe_y * plan->d.probe_x * sizeof(float2);
 }
+size_t ws_off_sparse(const adm_plan* plan, int batch) {
+    // sparse plans: kept spectra, then the dL/dd partials (doubles), behind the loss partials.  8-byte aligned by a pad that does
+    // not depend on the batch (every section in front is a multiple of 8 bytes per position except the loss partials, rounded up
+    // here, and the cover lists, a fixed 0 or 4 mod 8): the workspace stays linear in the batch, which MultisliceEngine.round_cap
+    // relies on
+    const size_t part = (size_t)batch * ((ms_streamed_col_groups(plan->d.probe_y, plan->d.probe_x) * sizeof(float) + 7) & ~(size_t)7);
+    const size_t fld = (size_t)batch * plan->d.n_modes * plan->d.probe_y * plan->d.probe_x * sizeof(float2);
+    const size_t cover = (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64;
+    return ws_off_field(plan, batch) + fld + part + (cover % 8 ? 4 : 0);
+}
 }  // namespace adm
+
+extern "C" int adm_plan_set_slice_positions(adm_plan* plan, const float* z_cm_dev, int n, double lambda_nm, double voxel_nm_y,
+                                            double voxel_nm_x) {
+    if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_slice_positions: null plan");
+    if (!plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions (sparse multislice) need a streamed plan "
+                                         "(adm_plan_create_streamed); the one-workgroup kernels keep one transfer function");
+    if (n == 0) {
+        plan->zpos_dev = nullptr;
+        plan->n_zpos = 0;
+        plan->zpos_dirty = false;
+        return ADM_OK;
+    }
+    if (!z_cm_dev) return fail(ADM_ERR_INVALID, "adm_plan_set_slice_positions: null positions");
+    if (plan->d.binning != 1) return fail(ADM_ERR_INVALID, "adm_plan_set_slice_positions: slice positions need binning = 1");
+    if (n != plan->d.obj_z)
+        return fail(ADM_ERR_INVALID, "adm_plan_set_slice_positions: " + std::to_string(n) + " positions for a plan of " +
+                                         std::to_string(plan->d.obj_z) + " slices");
+    if (n > ms_sparse_max_slices()) return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: more than 1024 slice positions");
+    if (!(lambda_nm > 0) || !(voxel_nm_y > 0) || !(voxel_nm_x > 0))
+        return fail(ADM_ERR_INVALID, "adm_plan_set_slice_positions: wavelength and voxel sizes must be positive");
+    const size_t npx = (size_t)plan->d.probe_y * plan->d.probe_x;
+    if (n > 1 && !plan->sp_hs_dev) {
+        int rc = adm_malloc(plan->ctx, (size_t)(n - 1) * npx * sizeof(float2), (void**)&plan->sp_hs_dev);
+        if (!rc) rc = adm_malloc(plan->ctx, (size_t)(plan->d.probe_y + plan->d.probe_x) * sizeof(float), (void**)&plan->sp_a_dev);
+        if (rc) return rc;
+    }
+    plan->zpos_dev = z_cm_dev;
+    plan->n_zpos = n;
+    plan->sp_lambda_nm = lambda_nm;
+    plan->sp_voxel_nm_y = voxel_nm_y;
+    plan->sp_voxel_nm_x = voxel_nm_x;
+    plan->zpos_dirty = true;
+    return ADM_OK;
+}
+
+extern "C" int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n) {
+    if (!ctx || !z_cm_dev) return fail(ADM_ERR_INVALID, "adm_slice_positions_anchor: null argument");
+    if (n < 1) return fail(ADM_ERR_INVALID, "adm_slice_positions_anchor: n must be positive");
+    ADM_HIP(ms_sparse_anchor_launch(z_cm_dev, n, ctx->stream));
+    return ADM_OK;
+}
 
 int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
                          const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
-                         float grad_scale, void* workspace, size_t workspace_bytes, bool per_position) {
+                         float grad_scale, void* workspace, size_t workspace_bytes, bool per_position, float* grad_slice_pos) {
     if (!plan || !obj_rot || !probe || !pos || !target || !loss_sum)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: null argument");
     if (batch <= 0) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: batch must be positive");
@@ -546,7 +610,26 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         if (plan->streamed) {
             char* f = (char*)workspace + ws_off_field(plan, batch);
             const size_t fbytes = (size_t)batch * probe_elems * sizeof(float2);
-            ADM_HIP(ms_streamed_launch(p, batch, (float2*)f, (float*)(f + fbytes), plan->ctx->stream));
+            StSparseLaunch sp;
+            const bool sparse = plan->n_zpos > 0;
+            if (sparse) {
+                const int Py = d.probe_y, Px = d.probe_x;
+                if (plan->zpos_dirty && plan->n_zpos > 1) {
+                    StSparseGeom q;
+                    q.py = Py; q.px = Px; q.n_slices = plan->n_zpos; q.sigma = (double)d.sign_convention;
+                    q.lambda_nm = plan->sp_lambda_nm; q.voxel_nm_y = plan->sp_voxel_nm_y; q.voxel_nm_x = plan->sp_voxel_nm_x;
+                    ADM_HIP(ms_sparse_table_launch(q, plan->zpos_dev, plan->sp_hs_dev, plan->sp_a_dev, plan->sp_a_dev + Py, plan->ctx->stream));
+                }
+                plan->zpos_dirty = false;
+                char* k = (char*)workspace + ws_off_sparse(plan, batch);
+                sp.hs = plan->sp_hs_dev;
+                sp.keep = (float2*)k;
+                sp.part = (double*)(k + (size_t)(plan->n_zpos - 1) * fbytes);
+                sp.ay = plan->sp_a_dev;
+                sp.ax = plan->sp_a_dev ? plan->sp_a_dev + Py : nullptr;
+                sp.grad_z = grad_slice_pos;
+            }
+            ADM_HIP(ms_streamed_launch(p, batch, (float2*)f, (float*)(f + fbytes), plan->ctx->stream, sparse ? &sp : nullptr));
         } else {
             ADM_HIP(ms_generic_launch(p, batch, plan->ctx->stream));
         }
@@ -575,6 +658,18 @@ extern "C" int adm_multislice_fwd_adj(adm_plan* plan, const float* obj_rot, cons
                                       float grad_scale, void* workspace, size_t workspace_bytes) {
     return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
                            workspace_bytes, false);
+}
+
+extern "C" int adm_multislice_fwd_adj_sparse(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
+                                             const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
+                                             float grad_scale, void* workspace, size_t workspace_bytes, float* grad_slice_pos) {
+    if (plan && !plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_multislice_fwd_adj_sparse: slice positions (sparse multislice) need a streamed plan "
+                                         "(adm_plan_create_streamed)");
+    if (plan && plan->n_zpos == 0)
+        return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_sparse: the plan has no slice positions (adm_plan_set_slice_positions)");
+    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
+                           workspace_bytes, false, grad_slice_pos);
 }
 
 extern "C" int adm_multislice_fwd_adj_pp(adm_plan* plan, const float* obj_rot, const float* probes, const int32_t* pos, int batch,

@@ -46,6 +46,13 @@ struct adm_plan {
     bool trans_only;       // adm_plan_set_transmission_cache(plan, 2): adm_rotate_fwd writes ONLY the transmissions (obj_rot is an identity, not data)
     // adm_tile_cover_build: the cover lists in workspace `ws` are current for (pos, batch, window); a few entries, so that every
     // round of a batch launched in parts can have its lists built ahead
+    // adm_plan_set_slice_positions (streamed plans): sparse multislice
+    const float* zpos_dev; // [n_zpos] slice positions in cm, the CALLER's device buffer; nullptr = equidistant slices (h_dev)
+    int n_zpos;
+    bool zpos_dirty;       // the table below has to be rebuilt from zpos_dev before the next launch
+    double sp_lambda_nm, sp_voxel_nm_y, sp_voxel_nm_x;
+    float2* sp_hs_dev;     // [n_zpos-1][Py*Px] H_s / (Py*Px)
+    float* sp_a_dev;       // [Py] then [Px]: a_yx = sp_a[y] + sp_a[Py + x], the phase of H per nm
     struct CoverKey { const void* ws; const void* pos; int batch, row0, nrows; unsigned long long fp; } cover_keys[4];
 };
 
@@ -121,15 +128,34 @@ hipError_t ms_launch(int n, const MsParams& p, int batch, hipStream_t st);
 // adm_multislice_fwd_adj's body (per_position: one probe set per position)
 int multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch, const float* target,
                     int want_grad, float* grad_probe, float* pred, float* loss_sum, float grad_scale, void* workspace,
-                    size_t workspace_bytes, bool per_position);
+                    size_t workspace_bytes, bool per_position, float* grad_slice_pos = nullptr);
 bool ms_generic_supported(int py, int px);
 int ms_generic_threads(int py, int px);
 hipError_t ms_generic_launch(const MsParams& p, int batch, hipStream_t st);
 bool ms_streamed_supported(int py, int px);
 int ms_streamed_col_groups(int py, int px);
 size_t ws_off_field(const adm_plan* plan, int batch);
-// the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials
-hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st);
+// sparse multislice on streamed plans (adm_ms_streamed.hip)
+struct StSparseGeom { int py, px, n_slices; double sigma, lambda_nm, voxel_nm_y, voxel_nm_x; };
+struct StSparse {              // kernel argument of the column launches that serve the slice-position gradient
+    float2* keep;              // [B][M][S-1][Py][Px] H_s * spectrum / (Py*Px) of the forward sweep
+    double* part;              // [S-1][B*M*column groups] dL/dd partials
+    const float* ay;           // [Py], [Px]: a_yx = ay[y] + ax[x]
+    const float* ax;
+    int step, n_conv;
+};
+struct StSparseLaunch {
+    const float2* hs;          // [S-1][Py][Px]
+    float2* keep; double* part; const float* ay; const float* ax;
+    float* grad_z;             // [S] += dL/dz (cm), or nullptr
+};
+hipError_t ms_sparse_table_launch(const StSparseGeom& q, const float* z, float2* hs, float* ay, float* ax, hipStream_t st);
+hipError_t ms_sparse_anchor_launch(float* z, int n, hipStream_t st);
+int ms_sparse_max_slices();
+size_t ws_off_sparse(const adm_plan* plan, int batch);
+// the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials;
+// sp: the tables of a sparse plan, or nullptr
+hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp = nullptr);
 hipError_t shift_launch(int n, const ShiftParams& q, int batch, bool adjoint, hipStream_t st);
 }  // namespace adm
 

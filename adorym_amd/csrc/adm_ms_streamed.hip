@@ -40,6 +40,7 @@ constexpr int ST_ROW_NT = 256;                 // threads of a row workgroup
 constexpr int ST_ROW_E = 8;                    // elements per thread in a row workgroup
 constexpr int ST_ROW_ELEMS = ST_ROW_NT * ST_ROW_E;   // whole rows, at most this many elements (one row of 2048 at the largest)
 constexpr int ST_MAX_SIDE = 2048;
+constexpr int ST_MAX_SLICES = 1024;         // most slices of a sparse plan (st_sparse_reduce_kernel keeps one sum per gap in LDS)
 constexpr int ST_COL_NT = 512;                 // most threads of a column workgroup (GEN_E elements each)
 // adjacent columns of a column workgroup: 8 (64-byte runs per row) up to Py = 1024, 4 at larger Py (the group is at most
 // ST_COL_NT * GEN_E elements: with more threads the detector kernel's per-element state no longer fits the registers)
@@ -279,6 +280,122 @@ __global__ __launch_bounds__(ST_COL_NT) void st_det_kernel(MsParams p, float2* _
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Sparse multislice (adm_plan_set_slice_positions): the slices sit at arbitrary depths z_s, so convolution s has a transfer
+// function of its own, H_s = exp(i a d_s) with d_s = (z_{s+1} - z_s) * 1e7 nm and a = -sigma PI lambda (u^2 + v^2) per nm.  The
+// table hs[S-1][Py][Px] = H_s / (Py*Px) is built on the device from z as it lives there; the forward and adjoint sweeps are the
+// launches above with hs + s*Py*Px.  When dL/dz is wanted, the column launches are the two kernels below instead: the forward
+// one keeps H_s Psihat'_s / (Py*Px) (in LDS after the multiply), the adjoint one holds Ghat after its column transform and sums
+//   dL/dd_s = - sum_k a_k Im( conj(Ghat_k) * kept_k )
+// over its elements (products in fp32, sums in fp64), ONE partial per workgroup; st_sparse_reduce_kernel adds the partials of a
+// step in a fixed order and accumulates dL/dz_j = 1e7 (dL/dd_{j-1} - dL/dd_j) into the caller's buffer.  No atomics.
+
+// fftfreq(n)[i] * n
+__device__ __forceinline__ int st_freq_index(int i, int n) { return i <= (n - 1) / 2 ? i : i - n; }
+
+// hs[s][y][x] = exp(i a_yx d_s) / (Py*Px): the phase (hundreds of radians at 10 um gaps) in fp64, reduced to one turn, then
+// sin / cos in fp32 and one rounding for the division.  ay[y] + ax[x] = a_yx for the gradient kernel (fp32).
+__global__ __launch_bounds__(256) void st_sparse_table_kernel(StSparseGeom q, const float* __restrict__ z, float2* __restrict__ hs,
+                                                               float* __restrict__ ay, float* __restrict__ ax) {
+    const size_t row = (size_t)q.py * q.px, n = (size_t)(q.n_slices - 1) * row;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const double c = -q.sigma * 3.14159265359 * q.lambda_nm;
+    if (i < (size_t)q.py) { const double u = (double)st_freq_index((int)i, q.py) / q.py / q.voxel_nm_y; ay[i] = (float)(c * u * u); }
+    if (i < (size_t)q.px) { const double v = (double)st_freq_index((int)i, q.px) / q.px / q.voxel_nm_x; ax[i] = (float)(c * v * v); }
+    if (i >= n) return;
+    const int s = (int)(i / row);
+    const int y = (int)((i - (size_t)s * row) / q.px), x = (int)(i - (size_t)s * row - (size_t)y * q.px);
+    const double u = (double)st_freq_index(y, q.py) / q.py / q.voxel_nm_y, v = (double)st_freq_index(x, q.px) / q.px / q.voxel_nm_x;
+    const double d = ((double)z[s + 1] - (double)z[s]) * 1e7;
+    double ph = c * (u * u + v * v) * d;
+    const double two_pi = 6.283185307179586476925287;
+    ph -= two_pi * rint(ph / two_pi);
+    float sn, cs;
+    sincosf((float)ph, &sn, &cs);
+    hs[i] = make_float2((float)((double)cs / (double)row), (float)((double)sn / (double)row));
+}
+
+// z <- z - z[0] (adorym/optimizers.py:1059)
+__global__ __launch_bounds__(256) void st_sparse_anchor_kernel(float* z, int n) {
+    const float z0 = z[0];
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256) z[i] -= z0;
+}
+
+// st_col_conv_kernel for the convolution `step` of a sparse plan when dL/dz is wanted.  Forward: keeps the multiplied spectrum.
+// Adjoint (CONJ): forms this workgroup's share of dL/dd_step before the multiply.
+template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_sparse_kernel(MsParams p, float2* __restrict__ fld,
+                                                                                             const float2* __restrict__ hs, StSparse q) {
+    extern __shared__ cf st_lds[];
+    __shared__ double redd[ST_COL_NT / 64];
+    const int Px = p.gen_px, cw = st_cw(p.gen_py), ncg = (Px + cw - 1) / cw;
+    const int bm = blockIdx.x / ncg, c0 = (blockIdx.x - bm * ncg) * cw;
+    GenCtx g;
+    st_col_ctx(g, st_lds, p, c0, cw);
+    const size_t row = (size_t)p.gen_py * Px;
+    float2* f = fld + (size_t)bm * row;
+    float2* keep = q.keep + ((size_t)bm * q.n_conv + q.step) * row;
+    st_col_load(g, f, Px, c0);
+    __syncthreads();
+    cf v[GEN_E];
+    st_col_fft<false>(g, p, v);
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < GEN_E; ++j) {
+        const int i = g.tid + j * g.nt;
+        if (j < g.ne && i < g.n) {
+            const int y = i / g.Px, x = c0 + (i - y * g.Px);
+            const size_t k = (size_t)y * Px + x;
+            const cf a = g.fld[i];
+            if (CONJ) {
+                const cf w = keep[k];
+                acc += (double)((q.ay[y] + q.ax[x]) * (a.x * w.y - a.y * w.x));
+                g.fld[i] = cmulc(a, hs[k]);
+            } else {
+                const cf w = cmul(a, hs[k]);
+                keep[k] = w;
+                g.fld[i] = w;
+            }
+        }
+    }
+    if (CONJ) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if ((g.tid & 63) == 0) redd[g.tid >> 6] = acc;
+    }
+    __syncthreads();
+    if (CONJ && g.tid == 0) {
+        double s = 0.0;
+        for (int w = 0; w < (g.nt >> 6); ++w) s += redd[w];
+        q.part[(size_t)q.step * gridDim.x + blockIdx.x] = -s;
+    }
+    st_col_fft<true>(g, p, v);
+    st_col_store(g, f, Px, c0);
+}
+
+// gz[j] += 1e7 * (dL/dd_{j-1} - dL/dd_j), dL/dd_s = the npart partials of step s added in a fixed order (one workgroup)
+__global__ __launch_bounds__(256) void st_sparse_reduce_kernel(const double* __restrict__ part, int npart, int n_conv, float* gz) {
+    __shared__ double red[256];
+    __shared__ double gd[ST_MAX_SLICES];
+    const int t = threadIdx.x;
+    for (int s = 0; s < n_conv; ++s) {
+        double a = 0.0;
+        for (int i = t; i < npart; i += 256) a += part[(size_t)s * npart + i];
+        red[t] = a;
+        __syncthreads();
+        for (int h = 128; h > 0; h >>= 1) {
+            if (t < h) red[t] += red[t + h];
+            __syncthreads();
+        }
+        if (t == 0) gd[s] = red[0];
+        __syncthreads();
+    }
+    for (int j = t; j <= n_conv; j += 256) {
+        const double d = (j > 0 ? gd[j - 1] : 0.0) - (j < n_conv ? gd[j] : 0.0);
+        gz[j] += (float)(1e7 * d);
+    }
+}
+
 // loss_sum[b] = the column-group partials of position b, ascending (loss_sum may be host-mapped memory)
 __global__ __launch_bounds__(256) void st_loss_reduce_kernel(const float* __restrict__ part, int ncg, int batch, float* loss_sum) {
     const int b = blockIdx.x * 256 + threadIdx.x;
@@ -297,7 +414,19 @@ static int st_col_threads(int py) {
     return nt;
 }
 
-hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st) {
+hipError_t ms_sparse_table_launch(const StSparseGeom& q, const float* z, float2* hs, float* ay, float* ax, hipStream_t st) {
+    size_t n = (size_t)(q.n_slices - 1) * q.py * q.px;
+    if (n < (size_t)(q.py > q.px ? q.py : q.px)) n = q.py > q.px ? q.py : q.px;
+    hipLaunchKernelGGL(st_sparse_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, z, hs, ay, ax);
+    return hipGetLastError();
+}
+hipError_t ms_sparse_anchor_launch(float* z, int n, hipStream_t st) {
+    hipLaunchKernelGGL(st_sparse_anchor_kernel, dim3(1), dim3(256), 0, st, z, n);
+    return hipGetLastError();
+}
+int ms_sparse_max_slices() { return ST_MAX_SLICES; }
+
+hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp) {
     const int Py = p.gen_py, Px = p.gen_px, S = p.n_steps, M = p.n_modes;
     if (!ms_streamed_supported(Py, Px)) return hipErrorInvalidValue;
     const bool far = p.det_mode == ADM_DET_FARFIELD_, fresnel = p.det_mode == ADM_DET_FRESNEL_;
@@ -313,6 +442,8 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_det_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_sparse_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_sparse_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
@@ -327,12 +458,26 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         else hipLaunchKernelGGL(st_col_conv_kernel<false>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h);
         return hipGetLastError();
     };
+    // convolution `step` of the slice loop: the plan's one H, or a sparse plan's H_step -- through the kernels that also keep the
+    // spectrum / form the dL/dd partials when the slice-position gradient is wanted
+    const size_t frow = (size_t)Py * Px;
+    const bool zgrad = sp && sp->grad_z && p.want_grad && S > 1;
+    auto conv = [&](int step, bool conj) {
+        if (!sp) return col(p.gen_hs, conj);
+        const float2* h = sp->hs + (size_t)step * frow;
+        if (!zgrad) return col(h, conj);
+        StSparse q;
+        q.keep = sp->keep; q.part = sp->part; q.ay = sp->ay; q.ax = sp->ax; q.step = step; q.n_conv = S - 1;
+        if (conj) hipLaunchKernelGGL(st_col_conv_sparse_kernel<true>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h, q);
+        else hipLaunchKernelGGL(st_col_conv_sparse_kernel<false>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h, q);
+        return hipGetLastError();
+    };
     hipError_t e = hipSuccess;
     // ---------------- forward ----------------
     const int det_row = far ? (p.det_inverse ? 2 : 1) : (fresnel ? 1 : 0);     // the row transform that starts the detector propagation
     for (int s = 0; s < S && e == hipSuccess; ++s) {
         e = row(s, 1, s > 0 ? 2 : 0, s < S - 1 ? 1 : det_row, s == 0, 0);
-        if (e == hipSuccess && s < S - 1) e = col(p.gen_hs, false);
+        if (e == hipSuccess && s < S - 1) e = conv(s, false);
     }
     if (e == hipSuccess && fresnel) {
         e = col(p.gen_hfree_s, false);
@@ -352,7 +497,11 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
     const int adj_row = far ? (p.det_inverse ? 1 : 2) : (fresnel ? 2 : 0);
     for (int s = S - 1; s >= 0 && e == hipSuccess; --s) {
         e = row(s, 2, s == S - 1 ? adj_row : 2, s > 0 ? 1 : 0, 0, s == 0);
-        if (e == hipSuccess && s > 0) e = col(p.gen_hs, true);
+        if (e == hipSuccess && s > 0) e = conv(s - 1, true);
+    }
+    if (e == hipSuccess && zgrad) {
+        hipLaunchKernelGGL(st_sparse_reduce_kernel, dim3(1), dim3(256), 0, st, sp->part, batch * M * ncg, S - 1, sp->grad_z);
+        e = hipGetLastError();
     }
     return e;
 }

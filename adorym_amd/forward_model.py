@@ -262,7 +262,7 @@ class PtychographyModel(ForwardModel):
 
     def _run(self, obj, probe_real, probe_imag, this_i_theta, this_pos_batch, target, want_grad, grad_obj=None,
              want_probe_grad=False, want_pred=False, probe_pos_correction=None, this_ind_batch=None, want_shift_grad=False,
-             side_hook=None, regularize=True, init_grad=False):
+             side_hook=None, regularize=True, init_grad=False, want_slice_pos_grad=False):
         """One evaluation.  Stream plan (same as bench.py): rotation on the main stream; then, on the context's side
         stream, ``side_hook()`` (the driver zeroes the gradient buffer / finishes the previous update there) and the
         regulariser gradient -- they only need the object -- while the multislice chain, which occupies `minibatch` of
@@ -334,15 +334,20 @@ class PtychographyModel(ForwardModel):
             if getattr(self, '_grad_shift_dev', None) is None or self._grad_shift_dev.shape != shifts.shape:
                 self._grad_shift_dev = self.device.empty(shifts.shape)
             gsh = self._grad_shift_dev.zero_()
+        gz = None
+        if want_slice_pos_grad:         # (SparseMultisliceModel: dL/d slice_pos_cm_ls, left in self._grad_slice_pos_dev)
+            if getattr(self, '_grad_slice_pos_dev', None) is None:
+                self._grad_slice_pos_dev = self.device.empty(eng.slice_pos.shape)
+            gz = self._grad_slice_pos_dev.zero_()
         mb = B // self.batch_group
         gs = 2.0 / (mb * eng.n_det)     # each reference minibatch is a mean over ITS positions (and the kept detector pixels)
-        if want_grad and shifts is None and B > eng.N_CU:
+        if want_grad and shifts is None and B > eng.N_CU and gz is None:
             # no join here: the overlapped launch forks again, and the side stream is in order, so its overlap-adds queue
             # behind the regulariser kernel while the first round of workgroups already runs beside it
             eng.multislice_overlapped(probe, grad_probe=gp, grad_scale=gs, want_pred=want_pred)
         else:
             eng.multislice(probe, grad_probe=gp, want_grad=want_grad, want_pred=want_pred, grad_scale=gs, shifts=shifts,
-                           shift_index=idx, grad_shifts=gsh, accumulate=False)
+                           shift_index=idx, grad_shifts=gsh, accumulate=False, grad_slice_pos=gz)
             ctx.join()              # (the side stream's work is a fraction of the kernel's time: the join does not wait)
             if want_grad:
                 eng.accumulate_tiles()
@@ -538,9 +543,88 @@ SingleBatchFullfieldModel = PtychographyModel
 SingleBatchPtychographyModel = PtychographyModel
 
 
-class SparseMultisliceModel(ForwardModel):
-    def __init__(self, *a, **k):
-        raise NotImplementedError('SparseMultisliceModel is outside the accelerated path (not in BASELINE configs)')
+class SparseMultisliceModel(PtychographyModel):
+    """
+    adorym/forward_model.py:589-806: a few thin slices at arbitrary depths ``slice_pos_cm_ls`` (cm), every gap propagated with
+    its own Fresnel-approximation kernel (sparse_multislice_propagate_batch, adorym/propagate.py:479-534).  The argument list is
+    PtychographyModel's with ``slice_pos_cm_ls`` where that has ``tilt_ls``; everything else -- rotation, resident data, staged
+    targets, regularisers, probe gradient -- is PtychographyModel's machinery.  ``common_vars_dict['engine']`` is a
+    MultisliceEngine built with ``slice_pos_cm`` (a streamed engine); its ``slice_pos`` device array IS the parameter: a
+    DeviceArray handed in must be that array (the driver's optimiser updates it in place and tells the engine), host values are
+    uploaded into it when they differ from the ones last seen.  Sub-pixel probe positions are refused (the streamed path takes one
+    probe set for all positions).
+    """
+
+    def __init__(self, loss_function_type='lsq', distribution_mode=None, device=None, common_vars_dict=None,
+                 raw_data_type='magnitude', simulation_mode=False, run_bfloat16=False, run_float64=False):
+        super(SparseMultisliceModel, self).__init__(loss_function_type, distribution_mode, device, common_vars_dict, raw_data_type,
+                                                    simulation_mode=simulation_mode, run_bfloat16=run_bfloat16, run_float64=run_float64)
+        if self.engine is not None and getattr(self.engine, 'slice_pos', None) is None:
+            raise ValueError('SparseMultisliceModel needs an engine built with slice_pos_cm (the slice positions in cm)')
+        self._slice_pos_host = None
+
+    def _set_slice_pos(self, slice_pos_cm_ls):
+        eng = self.engine
+        if isinstance(slice_pos_cm_ls, DeviceArray):
+            if slice_pos_cm_ls.ptr != eng.slice_pos.ptr:
+                raise ValueError('slice_pos_cm_ls on the device must be the engine\'s own slice_pos array')
+            return
+        host = np.ascontiguousarray(np.asarray(slice_pos_cm_ls, dtype=np.float32).reshape(-1))
+        if host.size != eng.slice_pos.size:
+            raise ValueError('slice_pos_cm_ls: %d slice positions for an object of %d slices' % (host.size, eng.slice_pos.size))
+        if self._slice_pos_host is None or not np.array_equal(self._slice_pos_host, host):
+            eng.slice_pos.set(host)
+            eng.slice_pos_changed()
+            self._slice_pos_host = host
+
+    def predict(self, obj, probe_real, probe_imag, probe_defocus_mm, probe_pos_offset, this_i_theta, this_pos_batch, prj,
+                probe_pos_correction, this_ind_batch, slice_pos_cm_ls, prj_pos_offset):
+        """Predicted detector magnitudes [minibatch, Py, Px] (host float32), adorym/forward_model.py:602-792."""
+        self._set_slice_pos(slice_pos_cm_ls)
+        return super(SparseMultisliceModel, self).predict(obj, probe_real, probe_imag, probe_defocus_mm, probe_pos_offset, this_i_theta,
+                                                          this_pos_batch, prj, probe_pos_correction, this_ind_batch, None, prj_pos_offset)
+
+    def get_loss_function(self):
+        dense = super(SparseMultisliceModel, self).get_loss_function()
+
+        def calculate_loss(obj, probe_real, probe_imag, probe_defocus_mm, probe_pos_offset, this_i_theta, this_pos_batch, prj,
+                           probe_pos_correction, this_ind_batch, slice_pos_cm_ls, prj_pos_offset):
+            self._set_slice_pos(slice_pos_cm_ls)
+            return dense(obj, probe_real, probe_imag, probe_defocus_mm, probe_pos_offset, this_i_theta, this_pos_batch, prj,
+                         probe_pos_correction, this_ind_batch, None, prj_pos_offset)
+        calculate_loss.forward_model = self
+        return calculate_loss
+
+    def loss_and_gradients(self, opt_args_ls, grad_obj, obj, probe_real, probe_imag, probe_defocus_mm, probe_pos_offset,
+                           this_i_theta, this_pos_batch, prj, probe_pos_correction, this_ind_batch, slice_pos_cm_ls, prj_pos_offset,
+                           _side_hook=None, _init_grad=False):
+        """PtychographyModel.loss_and_gradients with the index of ``slice_pos_cm_ls`` served too: its gradient is a DeviceArray
+        float32 [S], dL/dz in 1/cm."""
+        self._set_slice_pos(slice_pos_cm_ls)
+        self._check_static(probe_defocus_mm, probe_pos_offset, probe_pos_correction, prj_pos_offset)
+        staged = self.__dict__.pop('_staged', None)
+        if staged is not None and staged[0] == (int(this_i_theta), np.asarray(this_ind_batch).tobytes()):
+            target = staged[1]
+        else:
+            target = self._target(this_i_theta, this_ind_batch)
+        i_pr, i_pi = self.get_argument_index('probe_real'), self.get_argument_index('probe_imag')
+        i_z = self.get_argument_index('slice_pos_cm_ls')
+        want_probe = (i_pr in opt_args_ls) or (i_pi in opt_args_ls)
+        gp, _ = self._run(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, target, want_grad=True, grad_obj=grad_obj,
+                          want_probe_grad=want_probe, probe_pos_correction=probe_pos_correction, this_ind_batch=this_ind_batch,
+                          side_hook=_side_hook, init_grad=_init_grad, want_slice_pos_grad=i_z in opt_args_ls)
+        self._queue_loss()
+        out = []
+        for i in opt_args_ls:
+            if i == 0:
+                out.append(grad_obj)
+            elif i in (i_pr, i_pi):
+                out.append(gp)
+            elif i == i_z:
+                out.append(self._grad_slice_pos_dev)
+            else:
+                raise NotImplementedError("gradient w.r.t. '%s' is outside the accelerated path" % self.argument_ls[i])
+        return tuple(out)
 
 
 class MultiDistModel(PtychographyModel):

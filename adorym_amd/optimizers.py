@@ -139,7 +139,8 @@ def apply_small_params(ctx, items, i_batch):
     free_prop_cm, prj_affine_ls) in ONE launch (adm_adam_step_small) when every one of them is driven by a plain AdamOptimizer with
     the same (b1, b2, eps); otherwise one by one through the optimisers' own apply_gradient.  ``items``: dicts with
     opt, x, g (DeviceArrays), and optionally center_cols (drift guard, :1046-1048), pin (DeviceArray copied over the first
-    entries of x, :1067-1073), zero_grad (the gradient accumulator is zero-filled once used).  Same arithmetic either way."""
+    entries of x, :1067-1073), zero_grad (the gradient accumulator is zero-filled once used), anchor (x <- x - x[0] after the
+    update: the slice positions of sparse multislice, :1059; its own launch in both branches).  Same arithmetic either way."""
     from ._lib import SmallParam, SMALL_PARAMS_MAX
     if not items:
         return
@@ -167,6 +168,9 @@ def apply_small_params(ctx, items, i_batch):
             it['opt'].i_batch += 1
         b1, b2, eps = betas
         check(ctx.lib.adm_adam_step_small(ctx.handle, arr, len(items), int(i_batch), b1, b2, eps))
+        for it in items:
+            if it.get('anchor'):
+                check(ctx.lib.adm_slice_positions_anchor(ctx.handle, it['x'].ptr, it['x'].size))
         return
     for it in items:
         it['opt'].apply_gradient(it['x'], it['g'], i_batch, **it['opt'].options_dict)
@@ -174,6 +178,8 @@ def apply_small_params(ctx, items, i_batch):
             check(ctx.lib.adm_center_rows(ctx.handle, it['x'].ptr, it['x'].size // it['center_cols'], it['center_cols']))
         if it.get('pin') is not None:
             check(ctx.lib.adm_d2d(ctx.handle, it['x'].ptr, it['pin'].ptr, it['pin'].nbytes))
+        if it.get('anchor'):
+            check(ctx.lib.adm_slice_positions_anchor(ctx.handle, it['x'].ptr, it['x'].size))
         if it.get('zero_grad'):
             it['g'].zero_()
 

@@ -123,7 +123,7 @@ class MultisliceEngine(object):
                  fresnel_approx=True, sign_convention=1, normalize_fft=False, kernel=None, scale_ri_by_k=True,
                  n_probe_modes=1, max_batch=None, loss_function_type='lsq', poisson_multiplier=1., unknown_type='delta_beta',
                  beamstop=None, generic=False, transmission_cache=True, transmissions_only=False, streamed=False,
-                 workspace_budget=4 << 30):
+                 workspace_budget=4 << 30, slice_pos_cm=None):
         """``free_prop_cm``: 0 / None (exit wave), 'inf' (far field), a distance in cm (Fresnel propagation to the detector), or
         a SEQUENCE of n distances: position b of every launch is propagated to distance b % n (multi-distance data divided into
         sub-tiles, adorym/forward_model.py:999-1018 -- the caller lists every tile n times in a row, ``n_dists`` = n).
@@ -133,7 +133,12 @@ class MultisliceEngine(object):
         probe size, else the latter.  ``self.streamed`` tells which.  A streamed engine runs a batch in rounds whose workspace
         fits ``workspace_budget`` bytes (a position keeps n_steps * Py * Px complex numbers per mode: 134 MB at 256 x 256 and
         256 slices); each round is overlap-added before the next reuses the workspace.  Streamed engines take one probe set
-        shared by all positions: no ``shifts`` / ``probes_b`` and no multi-distance sequence."""
+        shared by all positions: no ``shifts`` / ``probes_b`` and no multi-distance sequence.
+
+        ``slice_pos_cm``: a sequence of obj_size[2] slice positions in cm -- SPARSE multislice (adorym/propagate.py:479-534): the
+        slices sit at these depths and every gap has its own Fresnel-approximation transfer function, built on the device from
+        ``self.slice_pos`` (DeviceArray float32 [S]; whoever changes it in place calls ``slice_pos_changed()``).  Always the
+        streamed plan, whatever the probe size; ``binning`` must be 1; ``kernel`` / ``fresnel_approx`` do not apply to the gaps."""
         self.ctx = ctx
         self.obj_size = tuple(int(v) for v in obj_size)
         self.probe_size = tuple(int(v) for v in probe_size)
@@ -166,6 +171,15 @@ class MultisliceEngine(object):
                                 sign_convention=sign_convention)
         if streamed not in (False, True, 'auto'):
             raise ValueError("streamed must be False, True or 'auto', got %r" % (streamed,))
+        if slice_pos_cm is not None:
+            slice_pos_cm = np.asarray(slice_pos_cm, dtype=np.float64).reshape(-1)
+            if len(slice_pos_cm) != self.obj_size[2]:
+                raise ValueError('slice_pos_cm: %d slice positions for an object of %d slices' % (len(slice_pos_cm), self.obj_size[2]))
+            if binning != 1:
+                raise ValueError('slice_pos_cm: sparse multislice needs binning = 1, got %r' % (binning,))
+            if dists and len(dists) > 1:
+                raise NotImplementedError('slice_pos_cm: sparse multislice with a sequence of detector distances is not implemented')
+            streamed = True                   # (the one path that applies a transfer function of its own per gap)
         plan_kw = dict(binning=binning, n_modes=n_probe_modes, sign_convention=sign_convention, det_mode=det, normalize_fft=normalize_fft,
                        h_free=h_free, loss_type={'lsq': _lib.LOSS_LSQ, 'poisson': _lib.LOSS_POISSON}[loss_function_type],
                        poisson_multiplier=poisson_multiplier, unknown_type=unknown_type)
@@ -179,6 +193,11 @@ class MultisliceEngine(object):
             self.plan = Plan(ctx, self.obj_size, self.probe_size, pads, self.k1, kernel, streamed=bool(streamed), **plan_kw)
         self.streamed = self.plan.streamed
         self.workspace_budget = int(workspace_budget)
+        self.slice_pos = None
+        if slice_pos_cm is not None:
+            self.slice_pos = ctx.array(slice_pos_cm.astype(np.float32))
+            self._sparse_args = (float(lmbda_nm), float(voxel_nm[0]), float(voxel_nm[1]))
+            self.slice_pos_changed()
         if dists and len(dists) > 1:
             self.plan.set_detector_kernels([get_kernel(d_ * 1e7, lmbda_nm, voxel_nm, self.probe_size, sign_convention=sign_convention)
                                             for d_ in dists])
@@ -217,6 +236,17 @@ class MultisliceEngine(object):
         self._ws = self._pos = self._target = self._pred = self._loss = None
         if max_batch:
             self._reserve(max_batch)
+
+    def slice_pos_changed(self):
+        """The values of ``slice_pos`` were changed on the device: the transfer functions of the gaps are rebuilt from them in
+        front of the next launch (and kept until the next call)."""
+        if self.slice_pos is None:
+            raise ValueError('slice_pos_changed: the engine has no slice positions')
+        check(self.ctx.lib.adm_plan_set_slice_positions(self.plan.handle, self.slice_pos.ptr, self.slice_pos.size, *self._sparse_args))
+
+    def anchor_slice_pos(self):
+        """slice_pos <- slice_pos - slice_pos[0] on the device (adorym/optimizers.py:1059); the gaps do not change."""
+        check(self.ctx.lib.adm_slice_positions_anchor(self.ctx.handle, self.slice_pos.ptr, self.slice_pos.size))
 
     # -------------------------------------------------------------------------------- buffers
     def round_cap(self):
@@ -356,7 +386,7 @@ class MultisliceEngine(object):
         return view
 
     def multislice(self, probe, grad_probe=None, want_grad=True, want_pred=False, grad_scale=None, accumulate=True,
-                   shifts=None, shift_index=None, grad_shifts=None, probes_b=None):
+                   shifts=None, shift_index=None, grad_shifts=None, probes_b=None, grad_slice_pos=None):
         """Launch the fused kernel on the batch given to set_batch().  Returns nothing; read
         results with loss() / pred().
 
@@ -367,7 +397,9 @@ class MultisliceEngine(object):
 
         ``probes_b`` (DeviceArray [B, n_modes, Py, Px, 2]): one probe set per position handed over as it is (the windows of a
         full-field probe that the sub-tiles of multi-distance data see, adorym/forward_model.py:944-994); ``probe`` is ignored
-        and no probe gradient is formed."""
+        and no probe gradient is formed.
+
+        ``grad_slice_pos`` (DeviceArray float32 [S], +=; engines with ``slice_pos_cm`` only): dL/d slice_pos in 1/cm."""
         B = self._B
         Py, Px = self.probe_size
         if grad_scale is None:
@@ -376,10 +408,15 @@ class MultisliceEngine(object):
         if self.streamed and (shifts is not None or probes_b is not None):
             raise NotImplementedError('streamed multislice (probe %dx%d): sub-pixel probe shifts and per-position probes are not '
                                       'implemented on the streamed path' % (Py, Px))
+        if grad_slice_pos is not None:
+            if self.slice_pos is None:
+                raise ValueError('grad_slice_pos: the engine was built without slice_pos_cm')
+            if grad_slice_pos.size != self.slice_pos.size or grad_slice_pos.dtype != np.float32:
+                raise ValueError('grad_slice_pos must be float32 [%d]' % self.slice_pos.size)
         self._acc_done = False
         self._next_loss_buffer()
         if self.streamed and len(self.rounds(B)) > 1:
-            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale)
+            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos)
             return
         if probes_b is not None:
             if shifts is not None or grad_probe is not None:
@@ -391,10 +428,13 @@ class MultisliceEngine(object):
                 1 if want_grad else 0, None, self._pred.ptr if want_pred else None, self._loss.ptr, float(grad_scale),
                 self._ws.ptr, self._ws.nbytes))
         elif shifts is None:
-            check(lib.adm_multislice_fwd_adj(
-                self.plan.handle, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr, B, self._cur_target.ptr,
-                1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
-                self._pred.ptr if want_pred else None, self._loss.ptr, float(grad_scale), self._ws.ptr, self._ws.nbytes))
+            args = (self.plan.handle, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr, B, self._cur_target.ptr,
+                    1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
+                    self._pred.ptr if want_pred else None, self._loss.ptr, float(grad_scale), self._ws.ptr, self._ws.nbytes)
+            if grad_slice_pos is not None:
+                check(lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
+            else:
+                check(lib.adm_multislice_fwd_adj(*args))
         else:
             M = self.n_probe_modes
             if getattr(self, '_probes_b', None) is None or self._probes_b.shape[0] < B:
@@ -417,10 +457,11 @@ class MultisliceEngine(object):
         if want_grad and accumulate:
             self.accumulate_tiles()
 
-    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale):
+    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None):
         """A streamed engine's batch that does not fit the workspace budget: one launch per round into the same workspace, each
         round's tile gradients overlap-added into grad_rot (zeroed first) before the next round overwrites them.  Losses,
-        predictions and the probe gradient are those of one launch; the object gradient too, up to the order of the additions."""
+        predictions and the probe gradient are those of one launch; the object gradient too, up to the order of the additions.
+        Every round adds its share to ``grad_slice_pos``."""
         lib, h, B = self.ctx.lib, self.plan.handle, self._B
         Py, Px = self.probe_size
         ws = self._ws
@@ -429,10 +470,13 @@ class MultisliceEngine(object):
         if want_grad:
             check(lib.adm_memset(self.ctx.handle, self.grad_rot.ptr, 0, self.grad_rot.nbytes))
         for o, n in self.rounds(B):
-            check(lib.adm_multislice_fwd_adj(h, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr + 8 * o, n,
-                                             self._cur_target.ptr + 4 * o * Py * Px, 1 if want_grad else 0, gp,
-                                             (pr + 4 * o * Py * Px) if pr else None, self._loss.ptr + 4 * o, float(grad_scale),
-                                             ws.ptr, ws.nbytes))
+            args = (h, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr + 8 * o, n, self._cur_target.ptr + 4 * o * Py * Px,
+                    1 if want_grad else 0, gp, (pr + 4 * o * Py * Px) if pr else None, self._loss.ptr + 4 * o, float(grad_scale),
+                    ws.ptr, ws.nbytes)
+            if grad_slice_pos is not None:
+                check(lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
+            else:
+                check(lib.adm_multislice_fwd_adj(*args))
             if not want_grad:
                 continue
             pos_host = np.ascontiguousarray(self._pos_host[o:o + n])

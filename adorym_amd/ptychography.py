@@ -32,7 +32,7 @@ from .constants import PI
 from .device import Context, DeviceArray
 from .differentiator import Differentiator
 from .dp import DataParallelObject, HipOps, constraint_flags
-from .forward_model import PtychographyModel, MultiDistModel
+from .forward_model import PtychographyModel, MultiDistModel, SparseMultisliceModel
 from .optimizers import Optimizer, AdamOptimizer, GDOptimizer, MomentumOptimizer, apply_small_params, plain_adam
 from .propagate import MultisliceEngine, RotationTable, get_kernel
 from .regularizers import L1Regularizer, TVRegularizer, ReweightedL1Regularizer, combined_weights
@@ -270,7 +270,8 @@ def reconstruct_ptychography(
     Same contract as the reference: returns None; results are files under ``save_path/output_folder``
     (delta_ds_1.tiff, beta_ds_1.tiff, probe_mag_ds_1.tiff, probe_phase_ds_1.tiff, convergence/loss_rank_*.txt).
     ``fname`` may also be a NumPy array / dict holding 'exchange/data' (no file needed), and ``kwargs`` may
-    carry ``comm=`` (an adorym_amd.comm object) and ``return_state=True`` (returns a dict of final arrays).
+    carry ``comm=`` (an adorym_amd.comm object) and ``return_state=True`` (returns a dict of final arrays; for sparse
+    multislice also 'slice_pos_cm_ls' and, when they are refined, 'slice_pos_history': the positions after every update).
     ``backend`` accepts 'hip' (and, for script compatibility, the reference's 'pytorch' / 'autograd' names,
     which are mapped to 'hip' with a warning).
     """
@@ -354,8 +355,8 @@ class _Run(object):
         _not_implemented(self.shrink_cycle is not None, 'shrink-wrap mask updates')
         _not_implemented(self.initial_tilt is not None, 'initial_tilt')
         _not_implemented(self.interpolation != 'bilinear', "interpolation='%s'" % self.interpolation)
-        for nm in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_prj_pos_offset', 'optimize_slice_pos',
-                   'optimize_tilt', 'optimize_ctf_lg_kappa'):
+        for nm in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_prj_pos_offset', 'optimize_tilt',
+                   'optimize_ctf_lg_kappa'):
             _not_implemented(getattr(self, nm), nm)
         if self.update_scheme not in ('immediate', 'per angle'):
             raise ValueError("update_scheme must be 'immediate' or 'per angle'")
@@ -403,10 +404,19 @@ class _Run(object):
             self.energy_ev = float(self.f.get('metadata/energy_ev'))
         if self.psize_cm is None:
             self.psize_cm = float(self.f.get('metadata/psize_cm'))
-        _not_implemented(self.slice_pos_cm_ls is not None and len(self.slice_pos_cm_ls) > 1, 'sparse multislice (slice_pos_cm_ls)')
+        # sparse multislice (ptychography.py:285-292): a few slices at the depths slice_pos_cm_ls
+        self.is_sparse_multislice = self.slice_pos_cm_ls is not None and len(self.slice_pos_cm_ls) > 1
+        if self.is_sparse_multislice:
+            if len(self.slice_pos_cm_ls) != obj_size[2]:
+                raise ValueError('slice_pos_cm_ls holds %d slice positions, the object has %d slices' % (len(self.slice_pos_cm_ls), obj_size[2]))
+            _not_implemented(self.binning != 1, 'sparse multislice (slice_pos_cm_ls) with binning = %r' % (self.binning,))
+            # the streamed kernels, the one path with a transfer function per gap, take one probe set for all positions
+            _not_implemented(self.optimize_all_probe_pos or bool(np.any(probe_pos - np.round(probe_pos) > 1e-3)),
+                             'sparse multislice (slice_pos_cm_ls) with sub-pixel probe positions (optimize_all_probe_pos or fractional probe_pos)')
         if self.free_prop_cm is None:
             self.free_prop_cm = self.f.get('metadata/free_prop_cm')
         self.is_multi_dist = np.array(self.free_prop_cm).size != 1          # ptychography.py:296-305
+        _not_implemented(self.is_sparse_multislice and self.is_multi_dist, 'sparse multislice (slice_pos_cm_ls) with multi-distance data')
         self.holo_tiled = False
         if self.is_multi_dist:
             # one object slice; config 5 is one undivided field of view (n_blocks == 1) without a safe zone
@@ -496,8 +506,8 @@ class _Run(object):
                 poisson_multiplier=self.poisson_multiplier, beamstop=self.beamstop,
                 # the rotation stores slice transmissions only; rotate_out_of_loop and plugin models read obj_rot
                 transmissions_only=(self.forward_model == 'auto' and not self.rotate_out_of_loop),
-                # probes too large for one workgroup's LDS (beyond 128 x 128) take the streamed kernels
-                streamed='auto', **common)
+                # probes too large for one workgroup's LDS (beyond 128 x 128) take the streamed kernels; so does sparse multislice
+                streamed='auto', slice_pos_cm=self.slice_pos_cm_ls if self.is_sparse_multislice else None, **common)
             # the rule of _shift_args (forward_model.py): sub-pixel shifts when the corrections are optimised or one exceeds 1e-3
             _not_implemented(self.engine.streamed and (self.optimize_all_probe_pos or bool(np.any(self.probe_pos - self.probe_pos_int > 1e-3))),
                              'sub-pixel probe positions (optimize_all_probe_pos or fractional probe_pos) with a %d x %d probe '
@@ -610,11 +620,12 @@ class _Run(object):
                        common_vars_dict=common_vars, raw_data_type=self.raw_data_type, run_bfloat16=self.run_bfloat16,
                        run_float64=self.run_float64)
         if self.forward_model == 'auto':
-            self.forward_model = MultiDistModel(**fm_args) if self.is_multi_dist else PtychographyModel(**fm_args)
+            cls = MultiDistModel if self.is_multi_dist else (SparseMultisliceModel if self.is_sparse_multislice else PtychographyModel)
+            self.forward_model = cls(**fm_args)
         else:
             self.forward_model = self.forward_model(**fm_args)
         fm = self.forward_model
-        self.builtin_model = type(fm) in (PtychographyModel, MultiDistModel)
+        self.builtin_model = type(fm) in (PtychographyModel, MultiDistModel, SparseMultisliceModel)
         self.rool = bool(self.rotate_out_of_loop) and not self.two_d_mode and not self.is_multi_dist
         if self.rool:
             _not_implemented(not isinstance(fm, PtychographyModel), 'rotate_out_of_loop with a user-defined forward model')
@@ -693,6 +704,9 @@ class _Run(object):
             params.update(probe_pos_correction=np.zeros([self.n_dists, 2]), free_prop_cm=self.free_prop_cm,
                           safe_zone_width=self.safe_zone_width, ctf_lg_kappa=self.ctf_lg_kappa,
                           prj_affine_ls=np.tile(np.array([[1., 0, 0], [0, 1., 0]]).reshape([1, 2, 3]), [self.n_dists, 1, 1]))
+        if self.is_sparse_multislice:
+            # ptychography.py:718-719.  The engine's device array IS the parameter: the optimiser updates it in place
+            params['slice_pos_cm_ls'] = self.engine.slice_pos
         # The optimised ones, in the order of the gradient tuple; one entry each (+ its gradient in the forward model)
         self.small, self.opt_args_ls = [], [0]
         if self.optimize_probe:
@@ -708,6 +722,10 @@ class _Run(object):
             # optimizers.py:877-889: Adam on probe_pos_correction [n_theta, n_pos, 2] (+ "prevent position drifting": subtract the
             # mean over (theta, position))
             self._add_small('probe_pos_correction', self.optimizer_all_probe_pos, self.all_probe_pos_learning_rate, center_cols=2)
+        if self.is_sparse_multislice and self.optimize_slice_pos:
+            # optimizers.py:891-903, 1051-1060: Adam on the slice positions (+ "prevent position drifting": subtract the first)
+            self._add_small('slice_pos_cm_ls', self.optimizer_slice_pos, self.slice_pos_learning_rate, anchor=True)
+        self.slice_pos_history = None         # (return_state: the positions after every update, copied on the device)
 
         restored = self.restored_params
         if restored is not None:
@@ -717,12 +735,14 @@ class _Run(object):
                     raise ValueError('checkpointed probe has shape %s, this run uses %s' % (pr_.shape[:-1], self.probe_dev.shape[:-1]))
                 self.probe_dev.set(pr_.astype(np.float32))
             for k_ in ('probe_pos_correction', 'free_prop_cm', 'prj_affine_ls', 'probe_defocus_mm', 'probe_pos_offset', 'prj_pos_offset',
-                       'tilt_ls'):
+                       'tilt_ls', 'slice_pos_cm_ls'):
                 if k_ in restored and k_ in params:
                     if hasattr(params[k_], 'set'):
                         params[k_].set(np.asarray(restored[k_], dtype=np.float32).reshape(params[k_].shape))
                     else:
                         params[k_] = restored[k_]
+            if self.is_sparse_multislice:
+                self.engine.slice_pos_changed()
 
         self.diff = Differentiator()
         self.diff.create_loss_node(self.forward_model.get_loss_function(), self.opt_args_ls)
@@ -1100,6 +1120,16 @@ class _Run(object):
                 self.comm.all_reduce_device(it_['g'])
         apply_small_params(self.ctx, items, self.i_opt_batch)
         self.zeroed_by_update = {p.key for p in due}
+        if any(p.key == 'slice_pos_cm_ls' for p in due):
+            self.engine.slice_pos_changed()       # the gaps' transfer functions are rebuilt in front of the next launch
+            if self.return_state and self.n_epochs != 'auto':
+                z = self.engine.slice_pos
+                if self.slice_pos_history is None:
+                    self.slice_pos_history = [self.ctx.zeros((int(self.n_epochs) * self.n_batch, z.size)), 0]
+                hist, k = self.slice_pos_history
+                if k < hist.shape[0]:
+                    _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * z.size * k, z.ptr, z.nbytes))
+                    self.slice_pos_history[1] = k + 1
 
     def _write_intermediate(self, i_batch):
         """output_object(full_output=False) + output_intermediate_parameters of the reference: object TIFFs under
@@ -1150,4 +1180,6 @@ class _Run(object):
         return {'delta': arr[..., 0], 'beta': arr[..., 1], 'probe_real': pa[..., 0], 'probe_imag': pa[..., 1],
                 'probe_pos_correction': np.asarray(_host(params['probe_pos_correction'])),
                 'free_prop_cm': _host(params.get('free_prop_cm', self.free_prop_cm)), 'prj_affine_ls': _host(params.get('prj_affine_ls')),
+                'slice_pos_cm_ls': _host(params.get('slice_pos_cm_ls')),
+                'slice_pos_history': None if self.slice_pos_history is None else self.slice_pos_history[0].get()[:self.slice_pos_history[1]],
                 'losses': self.loss_history, 'output_folder': self.output_folder}

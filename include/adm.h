@@ -345,6 +345,29 @@ int adm_multislice_fwd_adj_pp(adm_plan* plan, const float* obj_rot, const float*
                               const float* target, int want_grad, float* grad_probes, float* pred, float* loss_sum,
                               float grad_scale, void* workspace, size_t workspace_bytes);
 
+/* ---- sparse multislice (streamed plans) ------------------------------------------------
+ * A few thin slices at arbitrary, unequal depths (adorym/propagate.py:479-534, forward_model.py:589-806): slice s of the
+ * plan's obj_z slices sits at z_s cm and convolution s uses its own Fresnel-approximation transfer function
+ *   H_s = exp(i a d_s),  d_s = (z_{s+1} - z_s) * 1e7 nm,  a = -sign_convention * PI * lambda_nm * (u^2 + v^2),  PI = 3.14159265359,
+ * (u, v) = fftfreq / voxel_nm, in place of adm_plan_desc.h_* (which the plan still takes and then does not use).
+ * adm_plan_set_slice_positions hands the plan z_cm_dev: DEVICE float [n], n = obj_z, binning = 1 (ADM_ERR_INVALID otherwise);
+ * the buffer stays the caller's and must outlive its use.  The table of the H_s is built on the device, on the context's stream,
+ * in front of the next launch (phase in fp64, reduced to one turn, sin / cos in fp32).  Whoever changes the values afterwards
+ * -- an optimiser step, adm_slice_positions_anchor -- calls adm_plan_set_slice_positions again (same arguments) so that the
+ * table is rebuilt; without that call it is kept.  n = 0 removes the positions (the plan is equidistant again).  Call it before
+ * the workspace is sized: adm_plan_workspace_bytes grows by the spectra kept for the slice-position gradient.
+ * Plans of adm_plan_create answer ADM_ERR_UNSUPPORTED: only a streamed plan applies H in a launch of its own.
+ * On such a plan adm_multislice_fwd_adj runs the sparse model; adm_multislice_fwd_adj_sparse is the same call with
+ * grad_slice_pos: device float [n], dL/dz_s in 1/cm ACCUMULATED into it (want_grad = 1; may be NULL).  The terms are summed in a
+ * fixed order (no atomics): two calls give the same bits.
+ * adm_slice_positions_anchor: z <- z - z[0] on the device (adorym/optimizers.py:1059), asynchronous. */
+int adm_plan_set_slice_positions(adm_plan* plan, const float* z_cm_dev, int n, double lambda_nm, double voxel_nm_y,
+                                 double voxel_nm_x);
+int adm_multislice_fwd_adj_sparse(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
+                                  const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
+                                  float grad_scale, void* workspace, size_t workspace_bytes, float* grad_slice_pos);
+int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n);
+
 /* ---- f2  sub-pixel probe positions -----------------------------------------------------
  * realign_image_fourier (adorym/util.py:380-397) applied to every probe mode for every position of a minibatch:
  *   probes_out[b][m] = IFFT2( exp(-2 PI i (fx*sx_b + fy*sy_b)) * FFT2(probe[m]) ),  PI = 3.14159265359, f = fftfreq.
