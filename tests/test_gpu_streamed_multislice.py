@@ -28,9 +28,11 @@ def ctx(A):
     c.close()
 
 
-def run_streamed(A, ctx, case, streamed=True, **engine_kw):
+def run_streamed(A, ctx, case, streamed=True, want_grad=True, **engine_kw):
     """ms_matrix.run_engine with the engine's ``streamed`` choice (and further engine keywords): rotate -> multislice ->
-    rotate_adjoint on one shared probe set.  Returns the case with the engine's results added, and the engine's streamed flag."""
+    rotate_adjoint on one shared probe set.  Returns the case with the engine's results added, and the engine's streamed flag.
+    ``want_grad`` False: the forward-only launch; 'gprobe_raw' and 'grad_rot' are then the probe-gradient buffer (handed over
+    filled with 3) and the engine's rotated-frame gradient (filled with 5) as the launch left them."""
     out, k = dict(case), case['kw']
     obj, pos, probes, target, bs = [case[n] for n in ('obj', 'pos', 'probes', 'target', 'beamstop')]
     (Py, Px), S, B, M = k['shape'], k['S'], k['B'], k['n_modes']
@@ -45,12 +47,18 @@ def run_streamed(A, ctx, case, streamed=True, **engine_kw):
     d_gp = ctx.zeros((M, Py, Px, 2))
     eng.set_batch(pos, target)
     eng.rotate(ctx.array(obj, np.float32), None)
-    eng.multislice(d_probe, grad_probe=d_gp, want_pred=True)
-    eng.rotate_adjoint(d_grad, None)
+    if want_grad:
+        eng.multislice(d_probe, grad_probe=d_gp, want_pred=True)
+        eng.rotate_adjoint(d_grad, None)
+        out['grad'] = d_grad.get()
+        out['gprobe'] = MM.cplx(d_gp.get())
+    else:
+        d_gp = ctx.array(np.full((M, Py, Px, 2), 3, np.float32))
+        eng.grad_rot.set(np.full(eng.grad_rot.shape, 5, np.float32))
+        eng.multislice(d_probe, grad_probe=d_gp, want_grad=False, want_pred=True)
+        out['gprobe_raw'], out['grad_rot'] = d_gp.get(), eng.grad_rot.get()
     out['pred'] = eng.pred()
     out['loss'] = eng.loss()
-    out['grad'] = d_grad.get()
-    out['gprobe'] = MM.cplx(d_gp.get())
     out['streamed'] = eng.streamed
     out['n_rounds'] = len(eng.rounds(B))
     eng.plan.close()
@@ -71,8 +79,10 @@ ORACLE_CASES = {
 
 @pytest.mark.parametrize('name', list(ORACLE_CASES))
 def test_streamed_vs_oracle(A, ctx, name):
-    """Probe sizes beyond the LDS kernels (and 135 = 3^3 * 5, 200 x 240) on the streamed plan: prediction, loss, object gradient,
-    probe gradient against the fp64 oracle."""
+    """Probe sizes beyond the LDS kernels, up to 512 (and 135 = 3^3 * 5, 200 x 240) on the streamed plan: prediction, loss, object
+    gradient, probe gradient against the fp64 oracle.  Every one of these runs column workgroups of 256 threads over 8 columns
+    and several rows per row workgroup; the launch geometries beyond (sides up to 2048, large prime sides) are swept by
+    tests/st_matrix.py and tests/test_gpu_streamed_matrix.py."""
     kw = dict(ORACLE_CASES[name])
     res = run_streamed(A, ctx, MM.oracle_case(kw.pop('P'), **kw))
     assert res['streamed']
