@@ -5,7 +5,7 @@
 #include <cstring>
 #include <csignal>
 #include <unistd.h>
-#include "adm_common.h"
+#include "adm_host.h"
 
 namespace adm {
 static thread_local std::string g_err;
@@ -306,17 +306,6 @@ static int plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out, 
     p->Yp = d.pad_y0 + d.obj_y + d.pad_y1;
     p->Xp = d.pad_x0 + d.obj_x + d.pad_x1;
     p->n_steps = (d.obj_z + d.binning - 1) / d.binning;
-    p->h_dev = p->hfree_dev = p->twid_dev = nullptr;
-    p->hs_dev = p->hfree_s_dev = p->twid_y_dev = nullptr;
-    p->trans_dev = nullptr;
-    p->trans_src = nullptr;
-    p->trans_only = false;
-    p->zpos_dev = nullptr;
-    p->n_zpos = 0;
-    p->zpos_dirty = false;
-    p->sp_hs_dev = nullptr;
-    p->sp_a_dev = nullptr;
-    std::memset(p->cover_keys, 0, sizeof(p->cover_keys));
     p->generic = !tuned;
     p->streamed = streamed;
     {   // radix lists of the generic kernel's transforms: 8, 4, 2, 9, 3, 5, 7, then whatever primes remain
@@ -334,10 +323,6 @@ static int plan_create(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan** out, 
             return fail(ADM_ERR_UNSUPPORTED, who + ": probe size with more than 8 prime-power factors");
         }
     }
-    p->reg_stats = nullptr;
-    p->reg_partial = nullptr;
-    p->det_weight_dev = nullptr;
-    p->n_hfree = 1;
     const size_t npx = (size_t)d.probe_y * d.probe_x;
     int rc = upload_c(ctx, d.h_re, d.h_im, npx, &p->h_dev);
     if (!rc && d.det_mode == ADM_DET_FRESNEL) rc = upload_c(ctx, d.hfree_re, d.hfree_im, npx, &p->hfree_dev);
@@ -441,18 +426,7 @@ extern "C" size_t adm_plan_rot_elems(const adm_plan* plan) {
 
 extern "C" size_t adm_plan_workspace_bytes(const adm_plan* plan, int batch) {
     if (!plan || batch <= 0) return 0;
-    // [stash: B*M*per | tile gradients: B*per | cover lists (Yp*Xp*(1+64) u32) + overflow flag | detector fields: B*M*G*NT |
-    //  per-position probe gradients: B*M*Py*Px | streamed plans: fields B*M*Py*Px, loss partials B*column groups floats |
-    //  streamed plans with slice positions: kept spectra B*M*(S-1)*Py*Px, dL/dd partials (S-1)*B*M*column groups doubles]
-    const size_t per = adm::ms_ws_per_pos(plan) * sizeof(float2);
-    const size_t det = adm::ws_det_bytes(plan, batch);
-    const size_t gpp = (size_t)batch * plan->d.n_modes * plan->d.probe_y * plan->d.probe_x * sizeof(float2);
-    const size_t streamed = plan->streamed ? gpp + (size_t)batch * adm::ms_streamed_col_groups(plan->d.probe_y, plan->d.probe_x) * sizeof(float) : 0;
-    const size_t base = (size_t)batch * (plan->d.n_modes + 1) * per + (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64 + det + gpp + streamed;
-    if (!plan->streamed || plan->n_zpos < 2) return base;
-    const size_t n_conv = (size_t)plan->n_zpos - 1;
-    return adm::ws_off_sparse(plan, batch) + n_conv * gpp
-           + n_conv * batch * plan->d.n_modes * adm::ms_streamed_col_groups(plan->d.probe_y, plan->d.probe_x) * sizeof(double);
+    return adm::ws_layout(plan, batch).total;
 }
 
 namespace adm {
@@ -460,31 +434,38 @@ size_t ms_row_elems(const adm_plan* plan) {      // float2 elements of one works
     if (plan->generic) return (size_t)plan->d.probe_y * plan->d.probe_x;
     return (size_t)ms_r1_for(plan->d.probe_x) * ms_threads_for(plan->d.probe_x);
 }
-size_t ms_ws_per_pos(const adm_plan* plan) { return (size_t)plan->n_steps * ms_row_elems(plan); }
-size_t ws_det_bytes(const adm_plan* plan, int batch) {   // parked detector-plane fields of the probe modes
-    if (plan->d.n_modes <= 1) return 0;
-    const int N = plan->d.probe_x;
-    const size_t per_mode = plan->generic ? (size_t)plan->d.probe_y * N
-                                          : (size_t)(ms_r1_for(N) > ms_r2_for(N) ? ms_r1_for(N) : ms_r2_for(N)) * ms_threads_for(N);
-    return (size_t)batch * plan->d.n_modes * per_mode * sizeof(float2);
-}
-// byte offsets of the workspace sections
-size_t ws_off_gtile(const adm_plan* plan, int batch) { return (size_t)batch * plan->d.n_modes * ms_ws_per_pos(plan) * sizeof(float2); }
-size_t ws_off_cover(const adm_plan* plan, int batch) { return ws_off_gtile(plan, batch) + (size_t)batch * ms_ws_per_pos(plan) * sizeof(float2); }
-size_t ws_off_det(const adm_plan* plan, int batch) { return ws_off_cover(plan, batch) + (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64; }
-size_t ws_off_gprobe(const adm_plan* plan, int batch) { return ws_off_det(plan, batch) + ws_det_bytes(plan, batch); }
-size_t ws_off_field(const adm_plan* plan, int batch) {      // streamed plans: [B][M][Py][Px] fields, then the loss partials
-    return ws_off_gprobe(plan, batch) + (size_t)batch * plan->d.n_modes * plan->d.probe_y * plan->d.probe_x * sizeof(float2);
-}
-size_t ws_off_sparse(const adm_plan* plan, int batch) {
-    // sparse plans: kept spectra, then the dL/dd partials (doubles), behind the loss partials.  8-byte aligned by a pad that does
-    // not depend on the batch (every section in front is a multiple of 8 bytes per position except the loss partials, rounded up
-    // here, and the cover lists, a fixed 0 or 4 mod 8): the workspace stays linear in the batch, which MultisliceEngine.round_cap
-    // relies on
-    const size_t part = (size_t)batch * ((ms_streamed_col_groups(plan->d.probe_y, plan->d.probe_x) * sizeof(float) + 7) & ~(size_t)7);
-    const size_t fld = (size_t)batch * plan->d.n_modes * plan->d.probe_y * plan->d.probe_x * sizeof(float2);
-    const size_t cover = (size_t)plan->Yp * plan->Xp * 65 * sizeof(unsigned) + 64;
-    return ws_off_field(plan, batch) + fld + part + (cover % 8 ? 4 : 0);
+
+WsLayout ws_layout(const adm_plan* plan, int batch) {
+    const adm_plan_desc& d = plan->d;
+    const int N = d.probe_x;
+    const size_t B = (size_t)batch, M = (size_t)d.n_modes;
+    const size_t pos = (size_t)plan->n_steps * ms_row_elems(plan) * sizeof(float2);    // the rows of one position, one mode
+    const size_t fld = (size_t)d.probe_y * d.probe_x * sizeof(float2);                  // one field
+    const size_t lists = (size_t)plan->Yp * plan->Xp * (ADM_MAXCOVER + 1) * sizeof(unsigned);
+    size_t det = 0;                         // one parked detector-plane field: only several modes park theirs
+    if (M > 1) det = plan->generic ? fld : (size_t)(ms_r1_for(N) > ms_r2_for(N) ? ms_r1_for(N) : ms_r2_for(N)) * ms_threads_for(N) * sizeof(float2);
+    const size_t cg = plan->streamed ? (size_t)ms_streamed_col_groups(d.probe_y, d.probe_x) : 0;
+    const bool sparse = plan->streamed && plan->n_zpos >= 2;
+    const size_t n_conv = sparse ? (size_t)plan->n_zpos - 1 : 0;
+    WsLayout w;
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t off = at; at += bytes; return off; };
+    w.stash = take(B * M * pos);
+    w.gtile = take(B * pos);
+    w.cover = take(lists);
+    w.overflow = take(64);
+    w.det = take(B * M * det);
+    w.gprobe = take(B * M * fld);
+    w.field = take(plan->streamed ? B * M * fld : 0);
+    // The doubles of dd_part need 8-byte alignment, and MultisliceEngine.round_cap needs a total that is linear in the batch.
+    // Every section is a multiple of 8 bytes per position except the loss partials, rounded up here on sparse plans, and the
+    // cover lists, 0 or 4 mod 8 whatever the batch, made up for by a pad that does not depend on the batch either.
+    w.loss_part = take(B * (sparse ? (cg * sizeof(float) + 7) & ~(size_t)7 : cg * sizeof(float)));
+    if (sparse && lists % 8) at += 4;
+    w.keep = take(n_conv * B * M * fld);
+    w.dd_part = take(n_conv * B * M * cg * sizeof(double));
+    w.total = at;
+    return w;
 }
 }  // namespace adm
 
@@ -530,6 +511,31 @@ extern "C" int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n) 
     return ADM_OK;
 }
 
+// The launch of a streamed plan: fields and loss partials from the layout; on a sparse plan also the tables of the gaps (rebuilt
+// first if the slice positions changed), the kept spectra and the dL/dd partials.
+static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* ws, const WsLayout& w, float* grad_slice_pos) {
+    StSparseLaunch sp;
+    const bool sparse = plan->n_zpos > 0;
+    if (sparse) {
+        const int Py = plan->d.probe_y, Px = plan->d.probe_x;
+        if (plan->zpos_dirty && plan->n_zpos > 1) {
+            StSparseGeom q;
+            q.py = Py; q.px = Px; q.n_slices = plan->n_zpos; q.sigma = (double)plan->d.sign_convention;
+            q.lambda_nm = plan->sp_lambda_nm; q.voxel_nm_y = plan->sp_voxel_nm_y; q.voxel_nm_x = plan->sp_voxel_nm_x;
+            ADM_HIP(ms_sparse_table_launch(q, plan->zpos_dev, plan->sp_hs_dev, plan->sp_a_dev, plan->sp_a_dev + Py, plan->ctx->stream));
+        }
+        plan->zpos_dirty = false;
+        sp.hs = plan->sp_hs_dev;
+        sp.keep = (float2*)(ws + w.keep);
+        sp.part = (double*)(ws + w.dd_part);
+        sp.ay = plan->sp_a_dev;
+        sp.ax = plan->sp_a_dev ? plan->sp_a_dev + Py : nullptr;
+        sp.grad_z = grad_slice_pos;
+    }
+    ADM_HIP(ms_streamed_launch(p, batch, (float2*)(ws + w.field), (float*)(ws + w.loss_part), plan->ctx->stream, sparse ? &sp : nullptr));
+    return ADM_OK;
+}
+
 int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
                          const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
                          float grad_scale, void* workspace, size_t workspace_bytes, bool per_position, float* grad_slice_pos) {
@@ -540,8 +546,10 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
     if (plan->streamed && per_position)
         return fail(ADM_ERR_UNSUPPORTED, "adm_multislice_fwd_adj_pp: a streamed plan runs one probe set shared by all positions "
                                          "(per-position probes are not implemented on the streamed path)");
+    const WsLayout w = ws_layout(plan, batch);
+    char* ws = (char*)workspace;
     if (want_grad || plan->streamed) {      // (a streamed plan keeps its fields in the workspace even for want_grad = 0)
-        if (!workspace || workspace_bytes < adm_plan_workspace_bytes(plan, batch))
+        if (!workspace || workspace_bytes < w.total)
             return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: workspace too small");
     }
     MsParams p;
@@ -554,11 +562,11 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
     p.target = target;
     p.pred = pred;
     p.loss_sum = loss_sum;
-    p.stash = (float2*)workspace;
-    p.gtile = workspace ? (float2*)((char*)workspace + ws_off_gtile(plan, batch)) : nullptr;
-    p.det = workspace ? (float2*)((char*)workspace + ws_off_det(plan, batch)) : nullptr;
+    p.stash = ws ? (float2*)(ws + w.stash) : nullptr;
+    p.gtile = ws ? (float2*)(ws + w.gtile) : nullptr;
+    p.det = ws ? (float2*)(ws + w.det) : nullptr;
     p.n_modes = d.n_modes;
-    if (d.n_modes > 1 && (!workspace || workspace_bytes < adm_plan_workspace_bytes(plan, batch)))
+    if (d.n_modes > 1 && (!workspace || workspace_bytes < w.total))
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: several probe modes need the workspace even for want_grad = 0");
     p.h = plan->h_dev;
     p.hfree = plan->hfree_dev;
@@ -593,7 +601,7 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         p.probe_bstride = p.gprobe_bstride = probe_elems;       // every position stores its own gradient slot
     } else if (grad_probe && want_grad) {
         // shared probe: per-position slots in the workspace, summed in a fixed order into grad_probe after the launch
-        p.grad_probe = (float2*)((char*)workspace + ws_off_gprobe(plan, batch));
+        p.grad_probe = (float2*)(ws + w.gprobe);
         p.gprobe_bstride = probe_elems;
     }
     // cached slice transmissions: only for the buffer they were computed from
@@ -601,44 +609,22 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
     if (plan->trans_only && !use_t)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: the plan keeps slice transmissions only (cache mode 2) and this obj_rot was not "
                                      "produced by adm_rotate_fwd on it");
+    if (use_t) { p.obj_rot = plan->trans_dev; p.pre_t = 1; }
     if (plan->generic) {
-        if (use_t) { p.obj_rot = plan->trans_dev; p.pre_t = 1; }
         p.gen_py = d.probe_y; p.gen_px = d.probe_x;
         p.gen_nrx = plan->gen_nrx; p.gen_nry = plan->gen_nry;
         for (int i = 0; i < 8; ++i) { p.gen_rx[i] = plan->gen_rx[i]; p.gen_ry[i] = plan->gen_ry[i]; }
         p.gen_twid_y = plan->twid_y_dev; p.gen_hs = plan->hs_dev; p.gen_hfree_s = plan->hfree_s_dev;
         if (plan->streamed) {
-            char* f = (char*)workspace + ws_off_field(plan, batch);
-            const size_t fbytes = (size_t)batch * probe_elems * sizeof(float2);
-            StSparseLaunch sp;
-            const bool sparse = plan->n_zpos > 0;
-            if (sparse) {
-                const int Py = d.probe_y, Px = d.probe_x;
-                if (plan->zpos_dirty && plan->n_zpos > 1) {
-                    StSparseGeom q;
-                    q.py = Py; q.px = Px; q.n_slices = plan->n_zpos; q.sigma = (double)d.sign_convention;
-                    q.lambda_nm = plan->sp_lambda_nm; q.voxel_nm_y = plan->sp_voxel_nm_y; q.voxel_nm_x = plan->sp_voxel_nm_x;
-                    ADM_HIP(ms_sparse_table_launch(q, plan->zpos_dev, plan->sp_hs_dev, plan->sp_a_dev, plan->sp_a_dev + Py, plan->ctx->stream));
-                }
-                plan->zpos_dirty = false;
-                char* k = (char*)workspace + ws_off_sparse(plan, batch);
-                sp.hs = plan->sp_hs_dev;
-                sp.keep = (float2*)k;
-                sp.part = (double*)(k + (size_t)(plan->n_zpos - 1) * fbytes);
-                sp.ay = plan->sp_a_dev;
-                sp.ax = plan->sp_a_dev ? plan->sp_a_dev + Py : nullptr;
-                sp.grad_z = grad_slice_pos;
-            }
-            ADM_HIP(ms_streamed_launch(p, batch, (float2*)f, (float*)(f + fbytes), plan->ctx->stream, sparse ? &sp : nullptr));
+            const int rc = streamed_launch(plan, p, batch, ws, w, grad_slice_pos);
+            if (rc) return rc;
         } else {
             ADM_HIP(ms_generic_launch(p, batch, plan->ctx->stream));
         }
-        if (grad_probe && want_grad)
-            ADM_HIP(probe_grad_reduce(p.grad_probe, batch, probe_elems, (float2*)grad_probe, plan->ctx->stream));
-        return ADM_OK;
+    } else {
+        ADM_HIP(ms_launch(d.probe_x, p, batch, plan->ctx->stream));
     }
-    if (use_t) { p.obj_rot = plan->trans_dev; p.pre_t = 1; }
-    ADM_HIP(ms_launch(d.probe_x, p, batch, plan->ctx->stream));
+    // (per-position probes: every slot IS the result, nothing to sum)
     if (!per_position && grad_probe && want_grad)
         ADM_HIP(probe_grad_reduce(p.grad_probe, batch, probe_elems, (float2*)grad_probe, plan->ctx->stream));
     return ADM_OK;

@@ -16,7 +16,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
-#include "adm_common.h"
+#include "adm_host.h"
 
 namespace {
 

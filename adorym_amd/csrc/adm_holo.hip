@@ -15,7 +15,7 @@
 #include <vector>
 #include <cmath>
 #include <cstring>
-#include "adm_common.h"
+#include "adm_host.h"
 #include "adm_optim.h"
 #include "adm_fft.h"
 #include "adm_ms_math.h"

@@ -17,7 +17,7 @@
 // variants, beamstop weights, one probe set per position (adm_multislice_fwd_adj_pp).  Not supported here: the Fourier
 // shift of the probes (adm_probe_shift: sub-pixel position refinement).
 #include <hip/hip_runtime.h>
-#include "adm_common.h"
+#include "adm_host.h"
 #include "adm_fft.h"
 #include "adm_ms_math.h"
 #include "adm_ms_gen.h"

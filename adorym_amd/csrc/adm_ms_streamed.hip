@@ -29,7 +29,7 @@
 // 4 beyond Py = 1024): every row of the group is a 64-byte (32-byte) run.  Workspace rows (stash, tile gradients) are pixel-major [Py][Px] like the generic
 // kernel's, so the cover lists and the overlap-add (TileGeom::pixel_major) serve both.
 #include <hip/hip_runtime.h>
-#include "adm_common.h"
+#include "adm_host.h"
 #include "adm_fft.h"
 #include "adm_ms_math.h"
 #include "adm_ms_gen.h"

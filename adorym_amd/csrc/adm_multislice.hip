@@ -22,7 +22,7 @@
 //     tile gradients are stored per position in the same thread-native order and overlap-added by a
 //     separate streaming kernel (tile_accumulate_kernel): no atomics in the slice loop.
 #include <hip/hip_runtime.h>
-#include "adm_common.h"
+#include "adm_host.h"
 #include "adm_fft.h"
 #include "adm_ms_math.h"
 #include <type_traits>

@@ -4,7 +4,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <hip/hip_fp16.h>
-#include "adm_common.h"
+#include "adm_host.h"
 #include "adm_optim.h"
 #include "adm_ms_math.h"
 
@@ -480,7 +480,6 @@ __global__ __launch_bounds__(256) void rotate_adj_staged_stack_kernel(const floa
 // pixel (row, col) -> k = col / R2, tid = (row / LPW) * 64 + (row % LPW) * G + col % R2 (the multislice kernel's
 // thread-native order).
 // --------------------------------------------------------------------------------------------
-#define ADM_MAXCOVER 64
 
 struct TileGeom {
     int Yp, Xp, pad_y0, pad_x0, Py, Px, R1, R2, G, LPW, NT, n_steps, binning, Z;
@@ -1446,13 +1445,26 @@ static bool cover_key_take(adm_plan* plan, const void* ws, const void* pos, cons
 static int cover_build(adm_plan* plan, void* workspace, const int32_t* pos, int batch, const TileGeom& g, int b_lo = 0, int b_hi = -1) {
     if (b_hi < 0) b_hi = batch;
     char* ws = (char*)workspace;
-    unsigned* cover = (unsigned*)(ws + ws_off_cover(plan, batch));
-    int* overflow = (int*)(cover + (size_t)g.Yp * g.Xp * (ADM_MAXCOVER + 1));
+    const WsLayout w = ws_layout(plan, batch);
+    unsigned* cover = (unsigned*)(ws + w.cover);
+    int* overflow = (int*)(ws + w.overflow);
     hipStream_t st = plan->ctx->stream;
     // (a batch of at most ADM_MAXCOVER positions cannot overflow a cover list: no flag to reset, one launch less per minibatch)
     if (b_hi - b_lo > ADM_MAXCOVER) ADM_HIP(hipMemsetAsync(overflow, 0, sizeof(int), st));
     dim3 grid((g.Xp + 31) / 32, (g.nrows + 7) / 8, 1);
     hipLaunchKernelGGL(cover_build_kernel, grid, dim3(256), 0, st, (const int2*)pos, b_lo, b_hi, g, cover, overflow);
+    ADM_HIP(hipGetLastError());
+    return ADM_OK;
+}
+
+// grad_rot rows of g (+)= the tile gradients in the workspace, gathered through its cover lists
+static int tile_accumulate(adm_plan* plan, void* workspace, int batch, const TileGeom& g, float* grad_rot) {
+    char* ws = (char*)workspace;
+    const WsLayout w = ws_layout(plan, batch);
+    dim3 grid((g.Xp + 31) / 32, (g.nrows + 7) / 8, 1);
+    const unsigned nz8 = ((plan->n_steps + TA_STEPS - 1) / TA_STEPS + 7) / 8;      // step chunks per XCD
+    hipLaunchKernelGGL(tile_accumulate_kernel, dim3(8u * nz8 * grid.x * grid.y), dim3(256), 0, plan->ctx->stream,
+                       (const float2*)(ws + w.gtile), (const unsigned*)(ws + w.cover), (float2*)grad_rot, g);
     ADM_HIP(hipGetLastError());
     return ADM_OK;
 }
@@ -1488,16 +1500,7 @@ extern "C" int adm_tile_grad_accumulate_part(adm_plan* plan, void* workspace, si
         rc = cover_build(plan, workspace, pos, batch, g);
         if (rc) return rc;
     }
-    char* ws = (char*)workspace;
-    const float2* gtile = (const float2*)(ws + ws_off_gtile(plan, batch));
-    unsigned* cover = (unsigned*)(ws + ws_off_cover(plan, batch));
-    hipStream_t st = plan->ctx->stream;
-    dim3 grid((g.Xp + 31) / 32, (g.nrows + 7) / 8, 1);
-    const unsigned nz8 = ((plan->n_steps + TA_STEPS - 1) / TA_STEPS + 7) / 8;      // step chunks per XCD
-    hipLaunchKernelGGL(tile_accumulate_kernel, dim3(8u * nz8 * grid.x * grid.y), dim3(256), 0, st, gtile, (const unsigned*)cover,
-                       (float2*)grad_rot, g);
-    ADM_HIP(hipGetLastError());
-    return ADM_OK;
+    return tile_accumulate(plan, workspace, batch, g, grad_rot);
 }
 
 // A batch in which a pixel is covered by more than ADM_MAXCOVER tiles (dense 2-D scans taken as ONE minibatch,
@@ -1528,16 +1531,7 @@ extern "C" int adm_tile_grad_accumulate_range(adm_plan* plan, void* workspace, s
         return fail(ADM_ERR_UNSUPPORTED, "adm_tile_grad_accumulate_range: batch too large for 32-bit tile offsets");
     rc = cover_build(plan, workspace, pos, batch, g, b_lo, b_hi);
     if (rc) return rc;
-    char* ws = (char*)workspace;
-    const float2* gtile = (const float2*)(ws + ws_off_gtile(plan, batch));
-    unsigned* cover = (unsigned*)(ws + ws_off_cover(plan, batch));
-    hipStream_t st = plan->ctx->stream;
-    dim3 grid((g.Xp + 31) / 32, (g.nrows + 7) / 8, 1);
-    const unsigned nz8 = ((plan->n_steps + TA_STEPS - 1) / TA_STEPS + 7) / 8;
-    hipLaunchKernelGGL(tile_accumulate_kernel, dim3(8u * nz8 * grid.x * grid.y), dim3(256), 0, st, gtile, (const unsigned*)cover,
-                       (float2*)grad_rot, g);
-    ADM_HIP(hipGetLastError());
-    return ADM_OK;
+    return tile_accumulate(plan, workspace, batch, g, grad_rot);
 }
 
 extern "C" int adm_tile_grad_status(adm_plan* plan, void* workspace, size_t workspace_bytes, int batch, int* overflow_host) {
@@ -1547,10 +1541,7 @@ extern "C" int adm_tile_grad_status(adm_plan* plan, void* workspace, size_t work
         *overflow_host = 0;
         return ADM_OK;
     }
-    char* ws = (char*)workspace;
-    unsigned* cover = (unsigned*)(ws + ws_off_cover(plan, batch));
-    int* overflow = (int*)(cover + (size_t)plan->Yp * plan->Xp * (ADM_MAXCOVER + 1));
-    return adm_d2h(plan->ctx, overflow_host, overflow, sizeof(int));
+    return adm_d2h(plan->ctx, overflow_host, (char*)workspace + ws_layout(plan, batch).overflow, sizeof(int));
 }
 
 static int reg_grad_impl(adm_plan* plan, const float* obj, float alpha_d, float alpha_b, float gamma, float* grad_obj,

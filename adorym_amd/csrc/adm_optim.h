@@ -8,6 +8,7 @@
 //   constraints / support mask        adorym/ptychography.py:1135-1158, adorym/array_ops.py:239-251
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/adm.h"     // ADM_FLAG_*
 #include "adm_common.h"
 
 namespace adm {

@@ -26,7 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include "adm_common.h"
+#include "adm_host.h"
 #include "adm_optim.h"
 
 namespace {

@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <hipcub/hipcub.hpp>
-#include "adm_common.h"
+#include "adm_host.h"
 
 namespace adm {
 

@@ -5,6 +5,7 @@ kernels for one minibatch: rotate -> multislice forward + loss + adjoint -> rota
 Reference: adorym/propagate.py (get_kernel :62-81, gen_freq_mesh :54-60,
 multislice_propagate_batch :131-288).
 """
+import collections
 import ctypes as C
 import os
 import numpy as np
@@ -108,6 +109,12 @@ class RotationTable(object):
         return build_rotation_adjoint_csr(self.host, self.obj_size, Yp, Xp, plan.pads[1][0], staged=True)
 
 
+def equal_parts(B, cap):
+    """(offset, count) of the fewest equal parts of B items that hold at most ``cap`` each (544, 256 -> 182 + 181 + 181)."""
+    n = -(-B // cap)
+    return [(i * (B // n) + min(i, B % n), B // n + (1 if i < B % n else 0)) for i in range(n)]
+
+
 class MultisliceEngine(object):
     """
     Device-resident state for the accelerated path of one reconstruction:
@@ -193,7 +200,7 @@ class MultisliceEngine(object):
             self.plan = Plan(ctx, self.obj_size, self.probe_size, pads, self.k1, kernel, streamed=bool(streamed), **plan_kw)
         self.streamed = self.plan.streamed
         self.workspace_budget = int(workspace_budget)
-        self.slice_pos = None
+        self.slice_pos = self._sparse_args = None
         if slice_pos_cm is not None:
             self.slice_pos = ctx.array(slice_pos_cm.astype(np.float32))
             self._sparse_args = (float(lmbda_nm), float(voxel_nm[0]), float(voxel_nm[1]))
@@ -234,6 +241,17 @@ class MultisliceEngine(object):
         self._all_pos_host = np.ascontiguousarray(probe_pos.astype(np.int32))
         self._all_pos_dev = ctx.array(self._all_pos_host)
         self._ws = self._pos = self._target = self._pred = self._loss = None
+        # the batch given to set_batch()
+        self._B = 0
+        self._cur_pos = self._cur_target = self._pos_host = None
+        self._run_cache = {}                  # set_batch: where in the scan list a position set starts
+        self._cover_ok = collections.OrderedDict()      # _check_cover: most-covered pixel per position set
+        self._acc_done = False                # the launch overlap-added its rounds itself (_multislice_rounds)
+        self._acc_parts = []                  # (workspace, positions) of the overlap-adds whose overflow flag is unread
+        self._ws_parts = []                   # multislice_overlapped: one workspace per round
+        self._probes_b = self._gprobes_b = self._gshift_dummy = None      # multislice(shifts=...): per-position probe sets
+        self._stage_bufs, self._stage_k, self._stage_ring, self._retired_rings = [None, None], 0, None, []      # stage_target
+        self._aux_plan = None                 # cacheless_plan
         if max_batch:
             self._reserve(max_batch)
 
@@ -258,12 +276,7 @@ class MultisliceEngine(object):
     def rounds(self, B):
         """(offset, count) of the launches a batch of B positions takes: one, or for a streamed engine as many equal rounds as
         the workspace budget asks for."""
-        n_rounds = -(-B // self.round_cap()) if self.streamed else 1
-        if n_rounds == 1:
-            return [(0, B)]
-        sizes = [B // n_rounds + (1 if i < B % n_rounds else 0) for i in range(n_rounds)]
-        bounds = [0] + [int(v) for v in np.cumsum(sizes)]
-        return [(bounds[i], bounds[i + 1] - bounds[i]) for i in range(n_rounds)]
+        return equal_parts(B, self.round_cap()) if self.streamed else [(0, B)]
 
     def _reserve(self, batch):
         if batch <= self.max_batch:
@@ -292,7 +305,7 @@ class MultisliceEngine(object):
     def cacheless_plan(self):
         """A twin of the plan (same geometry) without the slice-transmission cache: rotations of arrays other than the object
         (the gradient resampling of rotate_out_of_loop) go through it and leave the cache of ``obj_rot`` alone."""
-        if getattr(self, '_aux_plan', None) is None:
+        if self._aux_plan is None:
             d = self.plan.desc
             self._aux_plan = Plan(self.ctx, self.obj_size, self.probe_size, self.pads, d.k1, self.plan._h[0] + 1j * self.plan._h[1],
                                   binning=d.binning, n_modes=d.n_modes, sign_convention=d.sign_convention, det_mode=_lib.DET_NONE,
@@ -335,7 +348,7 @@ class MultisliceEngine(object):
         run = None
         if self._all_pos_host is not None and B <= len(self._all_pos_host):
             # (the same minibatches come back every epoch: the search over the scan list is done once per distinct batch)
-            cache = self.__dict__.setdefault('_run_cache', {})
+            cache = self._run_cache
             key = pos.tobytes()
             run = cache.get(key, -1)
             if run == -1:
@@ -370,17 +383,16 @@ class MultisliceEngine(object):
         of a PCIe-inclusive step)."""
         host = np.ascontiguousarray(target, dtype=np.float32)
         B = host.shape[0]
-        bufs = self.__dict__.setdefault('_stage_bufs', [None, None])
-        k = self.__dict__.get('_stage_k', 0) ^ 1
-        self._stage_k = k
+        bufs = self._stage_bufs
+        k = self._stage_k = self._stage_k ^ 1
         need = max(B, self.max_batch or 0)
         if bufs[k] is None or bufs[k].shape[0] < B:
             bufs[k] = DeviceArray(self.ctx, (need,) + tuple(self.probe_size), np.float32)
         view = bufs[k].view(0, (B,) + tuple(self.probe_size))
-        ring = self.__dict__.get('_stage_ring')
+        ring = self._stage_ring
         if ring is None or ring.slot_bytes < host.nbytes:
             if ring is not None:
-                self.__dict__.setdefault('_retired_rings', []).append(ring)
+                self._retired_rings.append(ring)
             ring = self._stage_ring = UploadRing(self.ctx, max(host.nbytes, need * int(np.prod(self.probe_size)) * 4), n_slots=2)
         ring.upload(view, host)
         return view
@@ -418,38 +430,27 @@ class MultisliceEngine(object):
         if self.streamed and len(self.rounds(B)) > 1:
             self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos)
             return
+        args = lambda pr_, gp_: self._ms_args(pr_, gp_, want_grad, want_pred, grad_scale, 0, B, self._ws)      # (the whole batch)
         if probes_b is not None:
             if shifts is not None or grad_probe is not None:
                 raise ValueError('probes_b excludes shifts and grad_probe')
             if tuple(probes_b.shape) != (B, self.n_probe_modes, Py, Px, 2):
                 raise ValueError('probes_b must be [%d, %d, %d, %d, 2], got %r' % (B, self.n_probe_modes, Py, Px, tuple(probes_b.shape)))
-            check(lib.adm_multislice_fwd_adj_pp(
-                self.plan.handle, self.obj_rot.ptr, probes_b.ptr, self._cur_pos.ptr, B, self._cur_target.ptr,
-                1 if want_grad else 0, None, self._pred.ptr if want_pred else None, self._loss.ptr, float(grad_scale),
-                self._ws.ptr, self._ws.nbytes))
+            check(lib.adm_multislice_fwd_adj_pp(*args(probes_b, None)))
         elif shifts is None:
-            args = (self.plan.handle, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr, B, self._cur_target.ptr,
-                    1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
-                    self._pred.ptr if want_pred else None, self._loss.ptr, float(grad_scale), self._ws.ptr, self._ws.nbytes)
-            if grad_slice_pos is not None:
-                check(lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
-            else:
-                check(lib.adm_multislice_fwd_adj(*args))
+            self._launch(args(probe, grad_probe), grad_slice_pos)
         else:
             M = self.n_probe_modes
-            if getattr(self, '_probes_b', None) is None or self._probes_b.shape[0] < B:
+            if self._probes_b is None or self._probes_b.shape[0] < B:
                 self._probes_b = DeviceArray(self.ctx, (max(B, self.max_batch), M, Py, Px, 2), np.float32)
                 self._gprobes_b = DeviceArray(self.ctx, (max(B, self.max_batch), M, Py, Px, 2), np.float32)
             idx = shift_index.ptr if shift_index is not None else None
             need_adj = want_grad and (grad_probe is not None or grad_shifts is not None)
             check(lib.adm_probe_shift(self.plan.handle, probe.ptr, shifts.ptr, idx, B, self._probes_b.ptr))
-            check(lib.adm_multislice_fwd_adj_pp(
-                self.plan.handle, self.obj_rot.ptr, self._probes_b.ptr, self._cur_pos.ptr, B, self._cur_target.ptr,
-                1 if want_grad else 0, self._gprobes_b.ptr if need_adj else None,
-                self._pred.ptr if want_pred else None, self._loss.ptr, float(grad_scale), self._ws.ptr, self._ws.nbytes))
+            check(lib.adm_multislice_fwd_adj_pp(*args(self._probes_b, self._gprobes_b if need_adj else None)))
             if need_adj:
                 if grad_shifts is None:
-                    if getattr(self, '_gshift_dummy', None) is None or self._gshift_dummy.size != shifts.size:
+                    if self._gshift_dummy is None or self._gshift_dummy.size != shifts.size:
                         self._gshift_dummy = DeviceArray(self.ctx, (shifts.size,), np.float32)
                     grad_shifts = self._gshift_dummy
                 check(lib.adm_probe_shift_adj(self.plan.handle, probe.ptr, shifts.ptr, idx, B, self._gprobes_b.ptr,
@@ -457,36 +458,42 @@ class MultisliceEngine(object):
         if want_grad and accumulate:
             self.accumulate_tiles()
 
+    def _ms_args(self, probe, grad_probe, want_grad, want_pred, grad_scale, o, n, ws):
+        """The arguments of adm_multislice_fwd_adj[_pp] for positions [o, o + n) of the batch, launched into workspace ``ws``."""
+        px = 4 * o * self.probe_size[0] * self.probe_size[1]
+        return (self.plan.handle, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr + 8 * o, n, self._cur_target.ptr + px,
+                1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
+                self._pred.ptr + px if want_pred else None, self._loss.ptr + 4 * o, float(grad_scale), ws.ptr, ws.nbytes)
+
+    def _launch(self, args, grad_slice_pos=None):
+        if grad_slice_pos is not None:
+            check(self.ctx.lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
+        else:
+            check(self.ctx.lib.adm_multislice_fwd_adj(*args))
+
+    def _overlap_add(self, ws, o, n, add, window=(0, 0), passes=False):
+        """Overlap-add the tile gradients of positions [o, o + n), launched into ``ws``, into grad_rot: ``add`` = 0 writes the rows
+        of ``window`` (default: the part's own), 1 adds to them.  ``passes``: some pixel is covered by more than MAX_COVER of
+        these tiles, so they are added in passes of MAX_COVER positions each."""
+        lib = self.ctx.lib
+        head = (self.plan.handle, ws.ptr, ws.nbytes, self._cur_pos.ptr + 8 * o, n, self._pos_host[o:o + n].ctypes.data, self.grad_rot.ptr)
+        if not passes:
+            check(lib.adm_tile_grad_accumulate_part(*(head + (window[0], window[1], add))))
+            return
+        for lo in range(0, n, self.MAX_COVER):
+            check(lib.adm_tile_grad_accumulate_range(*(head + (lo, min(lo + self.MAX_COVER, n), 1 if add or lo else 0))))
+
     def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None):
         """A streamed engine's batch that does not fit the workspace budget: one launch per round into the same workspace, each
         round's tile gradients overlap-added into grad_rot (zeroed first) before the next round overwrites them.  Losses,
         predictions and the probe gradient are those of one launch; the object gradient too, up to the order of the additions.
         Every round adds its share to ``grad_slice_pos``."""
-        lib, h, B = self.ctx.lib, self.plan.handle, self._B
-        Py, Px = self.probe_size
-        ws = self._ws
-        gp = grad_probe.ptr if grad_probe is not None else None
-        pr = self._pred.ptr if want_pred else None
         if want_grad:
-            check(lib.adm_memset(self.ctx.handle, self.grad_rot.ptr, 0, self.grad_rot.nbytes))
-        for o, n in self.rounds(B):
-            args = (h, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr + 8 * o, n, self._cur_target.ptr + 4 * o * Py * Px,
-                    1 if want_grad else 0, gp, (pr + 4 * o * Py * Px) if pr else None, self._loss.ptr + 4 * o, float(grad_scale),
-                    ws.ptr, ws.nbytes)
-            if grad_slice_pos is not None:
-                check(lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
-            else:
-                check(lib.adm_multislice_fwd_adj(*args))
-            if not want_grad:
-                continue
-            pos_host = np.ascontiguousarray(self._pos_host[o:o + n])
-            if self._check_cover(pos_host) > self.MAX_COVER:
-                for lo in range(0, n, self.MAX_COVER):
-                    check(lib.adm_tile_grad_accumulate_range(h, ws.ptr, ws.nbytes, self._cur_pos.ptr + 8 * o, n, pos_host.ctypes.data,
-                                                             self.grad_rot.ptr, lo, min(lo + self.MAX_COVER, n), 1))
-            else:
-                check(lib.adm_tile_grad_accumulate_part(h, ws.ptr, ws.nbytes, self._cur_pos.ptr + 8 * o, n, pos_host.ctypes.data,
-                                                        self.grad_rot.ptr, 0, 0, 1))
+            check(self.ctx.lib.adm_memset(self.ctx.handle, self.grad_rot.ptr, 0, self.grad_rot.nbytes))
+        for o, n in self.rounds(self._B):
+            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), grad_slice_pos)
+            if want_grad:
+                self._overlap_add(self._ws, o, n, 1, passes=self._check_cover(self._pos_host[o:o + n]) > self.MAX_COVER)
         # (every overlap-add above saw at most MAX_COVER tiles per pixel: nothing to check afterwards)
         self._acc_done = want_grad
         self._accumulated = want_grad
@@ -500,9 +507,8 @@ class MultisliceEngine(object):
         (accumulate_tiles).  Evaluated on the host BEFORE the launch, cached per position set."""
         if len(pos) <= self.MAX_COVER:
             return len(pos)
-        import collections
         key = pos.tobytes()
-        cache = self.__dict__.setdefault('_cover_ok', collections.OrderedDict())
+        cache = self._cover_ok
         if key in cache:
             cache.move_to_end(key)
         else:
@@ -531,21 +537,13 @@ class MultisliceEngine(object):
     def accumulate_tiles(self):
         """Overlap-add the per-position tile gradients into the batch's rows of grad_rot.  A batch in which some pixel is covered
         by more than MAX_COVER tiles (a dense 2-D scan taken as one minibatch) is added in passes of MAX_COVER positions each."""
-        lib, B = self.ctx.lib, self._B
-        if getattr(self, '_acc_done', False):
+        if self._acc_done:
             return                  # (a streamed batch launched in rounds was overlap-added round by round)
-        if self._check_cover(self._pos_host) > self.MAX_COVER:
-            for k, lo in enumerate(range(0, B, self.MAX_COVER)):
-                check(lib.adm_tile_grad_accumulate_range(self.plan.handle, self._ws.ptr, self._ws.nbytes, self._cur_pos.ptr, B,
-                                                         self._pos_host.ctypes.data, self.grad_rot.ptr, lo, min(lo + self.MAX_COVER, B),
-                                                         1 if k else 0))
-            self._accumulated = True
-            self._acc_parts = []            # (a pass of <= MAX_COVER positions cannot overflow a list: nothing to check)
-            return
-        check(lib.adm_tile_grad_accumulate(self.plan.handle, self._ws.ptr, self._ws.nbytes, self._cur_pos.ptr, B,
-                                           self._pos_host.ctypes.data, self.grad_rot.ptr))
+        passes = self._check_cover(self._pos_host) > self.MAX_COVER
+        self._overlap_add(self._ws, 0, self._B, 0, passes=passes)
         self._accumulated = True
-        self._acc_parts = [(self._ws, B)]
+        # (a pass of <= MAX_COVER positions cannot overflow a list: nothing to check)
+        self._acc_parts = [] if passes else [(self._ws, self._B)]
 
     N_CU = 256        # MI355X compute units = multislice workgroups resident at once
 
@@ -567,19 +565,13 @@ class MultisliceEngine(object):
         # equal rounds (544 -> 182 + 181 + 181, not 256 + 256 + 32): a 32-position round costs 1.8 ms, most of a full one, and
         # the chip clocks higher with fewer CUs busy; 8.97 -> 8.44 ms per 544 positions (the same split cost nothing and gained
         # nothing before the kernel's load schedule; one round more: 9.37)
-        n_rounds = -(-B // self.N_CU)
-        sizes = [B // n_rounds + (1 if i < B % n_rounds else 0) for i in range(n_rounds)]
-        bounds = [0] + [int(v) for v in np.cumsum(sizes)]
-        parts = [(bounds[i], bounds[i + 1] - bounds[i]) for i in range(len(bounds) - 1)]
-        if getattr(self, '_ws_parts', None) is None or len(self._ws_parts) < len(parts):
+        parts = equal_parts(B, self.N_CU)
+        if len(self._ws_parts) < len(parts):
             need = self.plan.workspace_bytes(self.N_CU)
             self._ws_parts = [DeviceArray(self.ctx, (need,), np.uint8) for _ in parts]
         lib, h = self.ctx.lib, self.plan.handle
         self._next_loss_buffer()
-        gp = grad_probe.ptr if grad_probe is not None else None
-        pr = self._pred.ptr if want_pred else None
-        y_lo = int(self._pos_host[:, 0].min())
-        y_hi = int(self._pos_host[:, 0].max()) + Py
+        window = (int(self._pos_host[:, 0].min()), int(self._pos_host[:, 0].max()) + Py)
         self._acc_parts = []
         # (the whole batch's coverage is within MAX_COVER here, hence every round's)
         if len(parts) <= 4:
@@ -588,16 +580,13 @@ class MultisliceEngine(object):
             self.ctx.fork()
             for i, (o, n) in enumerate(parts):
                 check(lib.adm_tile_cover_build(h, self._ws_parts[i].ptr, self._ws_parts[i].nbytes, self._cur_pos.ptr + 8 * o, n,
-                                               self._pos_host[o:o + n].ctypes.data, y_lo, y_hi, 1 if i else 0))
+                                               self._pos_host[o:o + n].ctypes.data, window[0], window[1], 1 if i else 0))
             self.ctx.end_fork()
         for i, (o, n) in enumerate(parts):
             ws = self._ws_parts[i]
-            check(lib.adm_multislice_fwd_adj(h, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr + 8 * o, n,
-                                             self._cur_target.ptr + 4 * o * Py * Px, 1, gp, (pr + 4 * o * Py * Px) if pr else None,
-                                             self._loss.ptr + 4 * o, float(grad_scale), ws.ptr, ws.nbytes))
+            self._launch(self._ms_args(probe, grad_probe, True, want_pred, grad_scale, o, n, ws))
             self.ctx.fork()                   # side stream: waits for this round, then runs beside the next one
-            check(lib.adm_tile_grad_accumulate_part(h, ws.ptr, ws.nbytes, self._cur_pos.ptr + 8 * o, n,
-                                                    self._pos_host[o:o + n].ctypes.data, self.grad_rot.ptr, y_lo, y_hi, 1 if i else 0))
+            self._overlap_add(ws, o, n, 1 if i else 0, window=window)
             self.ctx.end_fork()
             self._acc_parts.append((ws, n))
         self.ctx.join()
@@ -605,7 +594,7 @@ class MultisliceEngine(object):
 
     def _check_overflow(self):
         if self._accumulated:
-            for ws, n in getattr(self, '_acc_parts', []):
+            for ws, n in self._acc_parts:
                 if n > 64:                        # a pixel cannot be covered by more tiles than the part has
                     ov = C.c_int(0)
                     check(self.ctx.lib.adm_tile_grad_status(self.plan.handle, ws.ptr, ws.nbytes, n, C.byref(ov)))
@@ -727,6 +716,8 @@ class AngleBatch(object):
         if tuple(self.engine.plan.pads[0]) != (0, 0):
             raise ValueError('AngleBatch: unexpected y padding %s of the stacked geometry' % (self.engine.plan.pads[0],))
         self.block_bytes = Y * X * Z * 2 * 4
+        self._table_ptrs = self._adj_ptrs = None      # the angles' table addresses on the device (rotate_all, rotate_adjoint_all)
+        self._adj_scratch = None                      # rotate_adjoint_all: R copies of the gradient, or False (too large)
 
     def _shifted(self, arr, r):
         Y, X, Z = self.obj_size
@@ -736,7 +727,7 @@ class AngleBatch(object):
         """Block r of the stacked rotated object = ``obj`` rotated with tables[r], all R blocks in ONE launch (adm_rotate_fwd_stack):
         the table addresses go up through the pinned ring (R pointers), nothing else changes hands."""
         eng = self.engine
-        if getattr(self, '_table_ptrs', None) is None:
+        if self._table_ptrs is None:
             self._table_ptrs = DeviceArray(self.ctx, (self.R,), np.uint64)
         self.ctx.uploader().upload(self._table_ptrs, np.array([t.ptr for t in tables], dtype=np.uint64))
         check(self.ctx.lib.adm_rotate_fwd_stack(eng.plan.handle, obj.ptr, self._table_ptrs.ptr, self.R, eng.obj_rot.ptr))
@@ -746,13 +737,13 @@ class AngleBatch(object):
         (adm_rotate_adj_staged_stack): the same additions, in the same order, as R calls of rotate_adjoint."""
         eng = self.engine
         parts = [t.csr(eng.plan) for t in tables]             # (ptr, src, lsrc, w, boxes) device arrays per angle
-        if getattr(self, '_adj_ptrs', None) is None:
+        if self._adj_ptrs is None:
             self._adj_ptrs = DeviceArray(self.ctx, (self.R, 5), np.uint64)
         self.ctx.uploader().upload(self._adj_ptrs, np.array([[p_[0].ptr, p_[1].ptr, p_[2].ptr, p_[3].ptr, p_[4].ptr] for p_ in parts],
                                                             dtype=np.uint64))
         # scratch for the angles' terms side by side (R copies of the real gradient), as long as that stays moderate
         # (ADM_STACK_SCRATCH_MB, 512): the R terms are then formed in parallel and added in angle order by a second launch
-        if getattr(self, '_adj_scratch', None) is None:
+        if self._adj_scratch is None:
             need = self.R * grad_obj.size * 4
             limit = float(os.environ.get('ADM_STACK_SCRATCH_MB', '512')) * 2 ** 20
             self._adj_scratch = DeviceArray(self.ctx, (self.R * grad_obj.size,), np.float32) if need <= limit else False

@@ -108,3 +108,37 @@ def test_per_position_probes_with_binning_are_refused_at_the_c_abi(A, ctx):
     assert rc == _lib.ADM_ERR_UNSUPPORTED
     assert b'binning' in ctx.lib.adm_last_error()
     eng.plan.close()
+
+
+def test_generic_kernel_per_position_probe_gradients_stay_in_their_slots(A, ctx):
+    """(d) adm_multislice_fwd_adj_pp on a generic plan (40 x 24) with a grad_probes buffer: every position's probe gradient is
+    left in its own slot, and nothing is summed over the slots afterwards.  Slot b equals BIT FOR BIT the grad_probe of a
+    batch-of-one adm_multislice_fwd_adj launch of position b into a zeroed buffer with the same grad_scale (same workgroup,
+    same arithmetic, 0 + v = v)."""
+    from adorym_amd._lib import check
+    (Py, Px), B, S, M = (40, 24), 3, 4, 1
+    case = MM.oracle_case((Py, Px), S=S, B=4, seed=4)           # (inputs only; edge_positions makes four corners)
+    obj, pos, target = case['obj'], case['pos'][:B], case['target'][:B]
+    eng = A.MultisliceEngine(ctx, obj.shape[:2] + (S,), (Py, Px), case['pos'], MM.ENERGY_EV, MM.PSIZE_CM, n_probe_modes=M, max_batch=B)
+    eng.set_batch(pos, target)
+    eng.rotate(ctx.array(obj, np.float32), None)
+    probe = MM.c2(case['probes'])                                # [M, Py, Px, 2]
+    d_probe = ctx.array(probe)
+    d_probes = ctx.array(np.ascontiguousarray(np.broadcast_to(probe, (B,) + probe.shape)))
+    d_slots = ctx.zeros((B, M, Py, Px, 2))
+    loss = ctx.zeros((B,))
+    scale = 2.0 / (B * Py * Px)
+    lib, h = ctx.lib, eng.plan.handle
+    check(lib.adm_multislice_fwd_adj_pp(h, eng.obj_rot.ptr, d_probes.ptr, eng._cur_pos.ptr, B, eng._cur_target.ptr, 1, d_slots.ptr, None,
+                                        loss.ptr, scale, eng._ws.ptr, eng._ws.nbytes))
+    slots = d_slots.get()
+    for b in range(B):
+        d_gp = ctx.zeros((M, Py, Px, 2))
+        check(lib.adm_multislice_fwd_adj(h, eng.obj_rot.ptr, d_probe.ptr, eng._cur_pos.ptr + 8 * b, 1, eng._cur_target.ptr + 4 * b * Py * Px,
+                                         1, d_gp.ptr, None, loss.ptr, scale, eng._ws.ptr, eng._ws.nbytes))
+        one = d_gp.get()
+        assert np.abs(one).max() > 0
+        differ = int((slots[b].view(np.uint32) != one.view(np.uint32)).sum())
+        print('slot %d: %d of %d words differ from the batch-of-one launch' % (b, differ, one.size))
+        assert differ == 0, (b, differ)
+    eng.plan.close()
