@@ -447,6 +447,8 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     const size_t cg = plan->streamed ? (size_t)ms_streamed_col_groups(d.probe_y, d.probe_x) : 0;
     const bool sparse = plan->streamed && plan->n_zpos >= 2;
     const size_t n_conv = sparse ? (size_t)plan->n_zpos - 1 : 0;
+    const bool xshift = plan->streamed && plan->exit_shift;
+    const bool dbl = sparse || xshift;       // the layout holds doubles
     WsLayout w;
     size_t at = 0;
     auto take = [&at](size_t bytes) { const size_t off = at; at += bytes; return off; };
@@ -460,10 +462,12 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     // The doubles of dd_part need 8-byte alignment, and MultisliceEngine.round_cap needs a total that is linear in the batch.
     // Every section is a multiple of 8 bytes per position except the loss partials, rounded up here on sparse plans, and the
     // cover lists, 0 or 4 mod 8 whatever the batch, made up for by a pad that does not depend on the batch either.
-    w.loss_part = take(B * (sparse ? (cg * sizeof(float) + 7) & ~(size_t)7 : cg * sizeof(float)));
-    if (sparse && lists % 8) at += 4;
+    w.loss_part = take(B * (dbl ? (cg * sizeof(float) + 7) & ~(size_t)7 : cg * sizeof(float)));
+    if (dbl && lists % 8) at += 4;
     w.keep = take(n_conv * B * M * fld);
     w.dd_part = take(n_conv * B * M * cg * sizeof(double));
+    w.xs_keep = take(xshift ? B * M * fld : 0);
+    w.xs_part = take(xshift ? B * M * cg * 2 * sizeof(double) : 0);
     w.total = at;
     return w;
 }
@@ -475,6 +479,9 @@ extern "C" int adm_plan_set_slice_positions(adm_plan* plan, const float* z_cm_de
     if (!plan->streamed)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions (sparse multislice) need a streamed plan "
                                          "(adm_plan_create_streamed); the one-workgroup kernels keep one transfer function");
+    if (n != 0 && plan->exit_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions together with exit-wave shifts "
+                                         "(adm_plan_set_exit_shift) are not implemented");
     if (n == 0) {
         plan->zpos_dev = nullptr;
         plan->n_zpos = 0;
@@ -513,7 +520,14 @@ extern "C" int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n) 
 
 // The launch of a streamed plan: fields and loss partials from the layout; on a sparse plan also the tables of the gaps (rebuilt
 // first if the slice positions changed), the kept spectra and the dL/dd partials.
-static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* ws, const WsLayout& w, float* grad_slice_pos) {
+static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* ws, const WsLayout& w, float* grad_slice_pos,
+                           const StExitShiftLaunch* shift) {
+    StExitShiftLaunch xs;
+    if (shift) {
+        xs = *shift;
+        xs.keep = (float2*)(ws + w.xs_keep);
+        xs.part = (double*)(ws + w.xs_part);
+    }
     StSparseLaunch sp;
     const bool sparse = plan->n_zpos > 0;
     if (sparse) {
@@ -532,13 +546,15 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
         sp.ax = plan->sp_a_dev ? plan->sp_a_dev + Py : nullptr;
         sp.grad_z = grad_slice_pos;
     }
-    ADM_HIP(ms_streamed_launch(p, batch, (float2*)(ws + w.field), (float*)(ws + w.loss_part), plan->ctx->stream, sparse ? &sp : nullptr));
+    ADM_HIP(ms_streamed_launch(p, batch, (float2*)(ws + w.field), (float*)(ws + w.loss_part), plan->ctx->stream, sparse ? &sp : nullptr,
+                               shift ? &xs : nullptr));
     return ADM_OK;
 }
 
 int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
                          const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
-                         float grad_scale, void* workspace, size_t workspace_bytes, bool per_position, float* grad_slice_pos) {
+                         float grad_scale, void* workspace, size_t workspace_bytes, bool per_position, float* grad_slice_pos,
+                         const StExitShiftLaunch* shift) {
     if (!plan || !obj_rot || !probe || !pos || !target || !loss_sum)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: null argument");
     if (batch <= 0) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: batch must be positive");
@@ -616,7 +632,7 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         for (int i = 0; i < 8; ++i) { p.gen_rx[i] = plan->gen_rx[i]; p.gen_ry[i] = plan->gen_ry[i]; }
         p.gen_twid_y = plan->twid_y_dev; p.gen_hs = plan->hs_dev; p.gen_hfree_s = plan->hfree_s_dev;
         if (plan->streamed) {
-            const int rc = streamed_launch(plan, p, batch, ws, w, grad_slice_pos);
+            const int rc = streamed_launch(plan, p, batch, ws, w, grad_slice_pos, shift);
             if (rc) return rc;
         } else {
             ADM_HIP(ms_generic_launch(p, batch, plan->ctx->stream));
@@ -656,6 +672,35 @@ extern "C" int adm_multislice_fwd_adj_sparse(adm_plan* plan, const float* obj_ro
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_sparse: the plan has no slice positions (adm_plan_set_slice_positions)");
     return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
                            workspace_bytes, false, grad_slice_pos);
+}
+
+extern "C" int adm_plan_set_exit_shift(adm_plan* plan, int on) {
+    if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_exit_shift: null plan");
+    if (!plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts (per-angle projection alignment) need a streamed plan "
+                                         "(adm_plan_create_streamed); the one-workgroup kernels do not apply them");
+    if (on && plan->n_zpos > 0)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with slice positions (sparse multislice) "
+                                         "are not implemented");
+    if (on && plan->n_hfree > 1)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with several detector kernels are not implemented");
+    plan->exit_shift = on != 0;
+    return ADM_OK;
+}
+
+extern "C" int adm_multislice_fwd_adj_exit_shift(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
+                                                 const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
+                                                 float grad_scale, void* workspace, size_t workspace_bytes, const float* shifts,
+                                                 const int32_t* index, float* grad_shifts) {
+    if (plan && !plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_multislice_fwd_adj_exit_shift: exit-wave shifts need a streamed plan (adm_plan_create_streamed)");
+    if (plan && !plan->exit_shift)
+        return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_exit_shift: the plan was not switched to exit-wave shifts (adm_plan_set_exit_shift)");
+    if (!shifts) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_exit_shift: null shifts");
+    StExitShiftLaunch xs;
+    xs.shifts = shifts; xs.index = index; xs.grad_shifts = grad_shifts; xs.keep = nullptr; xs.part = nullptr;
+    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
+                           workspace_bytes, false, nullptr, &xs);
 }
 
 extern "C" int adm_multislice_fwd_adj_pp(adm_plan* plan, const float* obj_rot, const float* probes, const int32_t* pos, int batch,

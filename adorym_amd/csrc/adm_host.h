@@ -52,6 +52,7 @@ struct adm_plan {
     double sp_lambda_nm = 0, sp_voxel_nm_y = 0, sp_voxel_nm_x = 0;
     float2* sp_hs_dev = nullptr;     // [n_zpos-1][Py*Px] H_s / (Py*Px)
     float* sp_a_dev = nullptr;       // [Py] then [Px]: a_yx = sp_a[y] + sp_a[Py + x], the phase of H per nm
+    bool exit_shift = false;         // adm_plan_set_exit_shift (streamed plans): the workspace holds the kept spectrum and the dL/ds partials
     // adm_tile_cover_build: the cover lists in workspace `ws` are current for (pos, batch, window); a few entries, so that every
     // round of a batch launched in parts can have its lists built ahead
     struct CoverKey { const void* ws; const void* pos; int batch, row0, nrows; unsigned long long fp; } cover_keys[4] = {};
@@ -80,6 +81,8 @@ struct WsLayout {
     size_t loss_part;   // streamed plans: [B][cg] float loss partials
     size_t keep;        // sparse plans (streamed, S >= 2): [B][M][S-1][Py][Px] kept spectra
     size_t dd_part;     // sparse plans: [S-1][B*M*cg] double dL/dd partials
+    size_t xs_keep;     // plans with exit-wave shifts (streamed): [B][M][Py][Px] kept detector-step spectra
+    size_t xs_part;     // plans with exit-wave shifts: [B*M*cg][2] double dL/ds partials
     size_t total;
 };
 WsLayout ws_layout(const adm_plan* plan, int batch);
@@ -87,10 +90,12 @@ WsLayout ws_layout(const adm_plan* plan, int batch);
 hipError_t probe_grad_reduce(const float2* part, int batch, size_t n, float2* out, hipStream_t st);
 hipError_t probe_grad_reduce_large(float2* part, int batch, size_t n, float2* out, hipStream_t st);   // two levels, `part` is scratch
 hipError_t ms_launch(int n, const MsParams& p, int batch, hipStream_t st);
+struct StExitShiftLaunch;
 // adm_multislice_fwd_adj's body (per_position: one probe set per position)
 int multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch, const float* target,
                     int want_grad, float* grad_probe, float* pred, float* loss_sum, float grad_scale, void* workspace,
-                    size_t workspace_bytes, bool per_position, float* grad_slice_pos = nullptr);
+                    size_t workspace_bytes, bool per_position, float* grad_slice_pos = nullptr,
+                    const StExitShiftLaunch* shift = nullptr);
 bool ms_generic_supported(int py, int px);
 int ms_generic_threads(int py, int px);
 hipError_t ms_generic_launch(const MsParams& p, int batch, hipStream_t st);
@@ -113,9 +118,27 @@ struct StSparseLaunch {
 hipError_t ms_sparse_table_launch(const StSparseGeom& q, const float* z, float2* hs, float* ay, float* ax, hipStream_t st);
 hipError_t ms_sparse_anchor_launch(float* z, int n, hipStream_t st);
 int ms_sparse_max_slices();
+// per-angle projection alignment on streamed plans (adm_ms_exitshift.hip): the detector step's column launches with a sub-pixel
+// Fourier shift of the exit wave per position
+struct StExitShift {           // kernel argument
+    const float2* shifts;      // [n_entries] (s_y, s_x)
+    const int* index;          // [B] entry of position b, or nullptr: b
+    float2* keep;              // [B][M][Py][Px] Phi H_free * spectrum / (Py*Px) of the forward sweep, or nullptr: not kept / not read
+    double* part;              // [B*M*column groups][2] dL/ds partials (before the factor 2 PI), or nullptr: no sums
+};
+struct StExitShiftLaunch {
+    const float* shifts; const int32_t* index;
+    float* grad_shifts;        // [n_entries][2] += dL/ds, or nullptr
+    float2* keep; double* part;
+};
+// the detector step's column launch: hs = H_free / (Py*Px), or nullptr for H = 1
+hipError_t ms_exitshift_col_launch(const MsParams& p, int batch, float2* fld, const float2* hs, bool conj, const StExitShiftLaunch& xs,
+                                   hipStream_t st);
+hipError_t ms_exitshift_reduce_launch(const MsParams& p, int batch, const StExitShiftLaunch& xs, hipStream_t st);
 // the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials;
-// sp: the tables of a sparse plan, or nullptr
-hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp = nullptr);
+// sp: the tables of a sparse plan, or nullptr; xs: the exit-wave shifts of a plan with adm_plan_set_exit_shift, or nullptr
+hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp = nullptr,
+                              const StExitShiftLaunch* xs = nullptr);
 hipError_t shift_launch(int n, const ShiftParams& q, int batch, bool adjoint, hipStream_t st);
 }  // namespace adm
 

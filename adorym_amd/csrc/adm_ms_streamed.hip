@@ -426,10 +426,16 @@ hipError_t ms_sparse_anchor_launch(float* z, int n, hipStream_t st) {
 }
 int ms_sparse_max_slices() { return ST_MAX_SLICES; }
 
-hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp) {
+hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp,
+                              const StExitShiftLaunch* xs) {
     const int Py = p.gen_py, Px = p.gen_px, S = p.n_steps, M = p.n_modes;
     if (!ms_streamed_supported(Py, Px)) return hipErrorInvalidValue;
-    const bool far = p.det_mode == ADM_DET_FARFIELD_, fresnel = p.det_mode == ADM_DET_FRESNEL_;
+    // exit-wave shifts (adm_ms_exitshift.hip): a far-field magnitude does not see them; an exit-wave detector takes the Fresnel
+    // sequence with H = 1
+    const bool far = p.det_mode == ADM_DET_FARFIELD_;
+    if (far) xs = nullptr;
+    const bool fresnel = p.det_mode == ADM_DET_FRESNEL_ || xs;
+    const float2* hfree_s = p.det_mode == ADM_DET_FRESNEL_ ? p.gen_hfree_s : nullptr;
     int rows = ST_ROW_ELEMS / Px;
     if (rows < 1) rows = 1;
     if (rows > Py) rows = Py;
@@ -472,6 +478,7 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         else hipLaunchKernelGGL(st_col_conv_sparse_kernel<false>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h, q);
         return hipGetLastError();
     };
+    auto det_col = [&](bool conj) { return xs ? ms_exitshift_col_launch(p, batch, fld, hfree_s, conj, *xs, st) : col(hfree_s, conj); };
     hipError_t e = hipSuccess;
     // ---------------- forward ----------------
     const int det_row = far ? (p.det_inverse ? 2 : 1) : (fresnel ? 1 : 0);     // the row transform that starts the detector propagation
@@ -480,7 +487,7 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         if (e == hipSuccess && s < S - 1) e = conv(s, false);
     }
     if (e == hipSuccess && fresnel) {
-        e = col(p.gen_hfree_s, false);
+        e = det_col(false);
         if (e == hipSuccess) e = row(0, 0, 2, 0, 0, 0);
     }
     if (e != hipSuccess) return e;
@@ -492,7 +499,7 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
     // ---------------- adjoint ----------------
     if (fresnel) {
         e = row(0, 0, 1, 0, 0, 0);
-        if (e == hipSuccess) e = col(p.gen_hfree_s, true);
+        if (e == hipSuccess) e = det_col(true);
     }
     const int adj_row = far ? (p.det_inverse ? 1 : 2) : (fresnel ? 2 : 0);
     for (int s = S - 1; s >= 0 && e == hipSuccess; --s) {
@@ -503,6 +510,7 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         hipLaunchKernelGGL(st_sparse_reduce_kernel, dim3(1), dim3(256), 0, st, sp->part, batch * M * ncg, S - 1, sp->grad_z);
         e = hipGetLastError();
     }
+    if (e == hipSuccess && xs && xs->grad_shifts) e = ms_exitshift_reduce_launch(p, batch, *xs, st);
     return e;
 }
 

@@ -168,11 +168,42 @@ class PtychographyModel(ForwardModel):
         self.batch_group = 1
 
     # ------------------------------------------------------------------ helpers
+    # flags of the reference that this model refuses by name (optimize_prj_pos_offset is served: _offset_args)
+    REFUSED_FLAGS = ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_tilt')
+
     def _check_static(self, probe_defocus_mm, probe_pos_offset, probe_pos_correction, prj_pos_offset):
         cv = self.common_vars
-        for flag in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_prj_pos_offset', 'optimize_tilt'):
+        for flag in self.REFUSED_FLAGS:
             if cv.get(flag):
                 raise NotImplementedError('%s is outside the accelerated path (SURVEY section 8 f2)' % flag)
+
+    def _offset_args(self, prj_pos_offset, this_i_theta, B):
+        """forward_model.py:255-256, 352: with optimize_prj_pos_offset every position of the minibatch carries the offset of its
+        angle, prj_pos_offset[this_i_theta], applied to the exit wave (MultisliceEngine.multislice(exit_shifts=...)).  Returns
+        (offsets DeviceArray [n_theta, 2], index DeviceArray int32 [B], all this_i_theta) or (None, None)."""
+        if not self.common_vars.get('optimize_prj_pos_offset'):
+            return None, None
+        if prj_pos_offset is None:
+            raise ValueError('optimize_prj_pos_offset is set but no prj_pos_offset was passed')
+        if not getattr(self.engine, 'exit_shift', False):
+            raise ValueError('optimize_prj_pos_offset needs an engine built with exit_shift=True')
+        if isinstance(prj_pos_offset, DeviceArray):
+            dev = prj_pos_offset
+        else:
+            host = np.ascontiguousarray(np.asarray(prj_pos_offset, dtype=np.float32).reshape(-1, 2))
+            key = (host.shape, host.tobytes())
+            if getattr(self, '_offset_key', None) != key:
+                self._offset_dev = self.device.array(host)
+                self._offset_key = key
+            dev = self._offset_dev
+        if not 0 <= int(this_i_theta) < dev.size // 2:
+            raise ValueError('prj_pos_offset holds %d angles, angle %d was asked for' % (dev.size // 2, int(this_i_theta)))
+        # one resident index array per angle (constant this_i_theta), grown when a larger batch comes: no upload in the minibatch
+        cache = self.__dict__.setdefault('_offset_idx', {})
+        idx = cache.get(int(this_i_theta))
+        if idx is None or idx.size < B:
+            idx = cache[int(this_i_theta)] = self.device.array(np.full(max(B, 64), int(this_i_theta), dtype=np.int32))
+        return dev, idx.view(0, (B,))
 
     def _shift_args(self, probe_pos_correction, this_i_theta, this_ind_batch):
         """forward_model.py:297-311: the probes are Fourier-shifted per position when the corrections are being optimised or
@@ -262,7 +293,7 @@ class PtychographyModel(ForwardModel):
 
     def _run(self, obj, probe_real, probe_imag, this_i_theta, this_pos_batch, target, want_grad, grad_obj=None,
              want_probe_grad=False, want_pred=False, probe_pos_correction=None, this_ind_batch=None, want_shift_grad=False,
-             side_hook=None, regularize=True, init_grad=False, want_slice_pos_grad=False):
+             side_hook=None, regularize=True, init_grad=False, want_slice_pos_grad=False, prj_pos_offset=None, want_offset_grad=False):
         """One evaluation.  Stream plan (same as bench.py): rotation on the main stream; then, on the context's side
         stream, ``side_hook()`` (the driver zeroes the gradient buffer / finishes the previous update there) and the
         regulariser gradient -- they only need the object -- while the multislice chain, which occupies `minibatch` of
@@ -339,15 +370,24 @@ class PtychographyModel(ForwardModel):
             if getattr(self, '_grad_slice_pos_dev', None) is None:
                 self._grad_slice_pos_dev = self.device.empty(eng.slice_pos.shape)
             gz = self._grad_slice_pos_dev.zero_()
+        offs, oidx = self._offset_args(prj_pos_offset, this_i_theta, B)
+        goff = None
+        if want_offset_grad:            # (dL/d prj_pos_offset, dense [n_theta, 2], left in self._grad_offset_dev)
+            if offs is None:
+                raise RuntimeError('gradient w.r.t. prj_pos_offset requested but optimize_prj_pos_offset is not set')
+            if getattr(self, '_grad_offset_dev', None) is None or self._grad_offset_dev.shape != offs.shape:
+                self._grad_offset_dev = self.device.empty(offs.shape)
+            goff = self._grad_offset_dev.zero_()
         mb = B // self.batch_group
         gs = 2.0 / (mb * eng.n_det)     # each reference minibatch is a mean over ITS positions (and the kept detector pixels)
-        if want_grad and shifts is None and B > eng.N_CU and gz is None:
+        if want_grad and shifts is None and B > eng.N_CU and gz is None and offs is None:
             # no join here: the overlapped launch forks again, and the side stream is in order, so its overlap-adds queue
             # behind the regulariser kernel while the first round of workgroups already runs beside it
             eng.multislice_overlapped(probe, grad_probe=gp, grad_scale=gs, want_pred=want_pred)
         else:
             eng.multislice(probe, grad_probe=gp, want_grad=want_grad, want_pred=want_pred, grad_scale=gs, shifts=shifts,
-                           shift_index=idx, grad_shifts=gsh, accumulate=False, grad_slice_pos=gz)
+                           shift_index=idx, grad_shifts=gsh, accumulate=False, grad_slice_pos=gz, exit_shifts=offs,
+                           exit_shift_index=oidx, grad_exit_shifts=goff)
             ctx.join()              # (the side stream's work is a fraction of the kernel's time: the join does not wait)
             if want_grad:
                 eng.accumulate_tiles()
@@ -488,7 +528,7 @@ class PtychographyModel(ForwardModel):
         B = len(this_pos_batch)
         zeros = np.zeros((B,) + tuple(self.engine.probe_size), np.float32)
         self._run(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, zeros, want_grad=False, want_pred=True,
-                  probe_pos_correction=probe_pos_correction, this_ind_batch=this_ind_batch, regularize=False)
+                  probe_pos_correction=probe_pos_correction, this_ind_batch=this_ind_batch, regularize=False, prj_pos_offset=prj_pos_offset)
         self.i_call += 1
         return self.engine.pred()
 
@@ -498,7 +538,7 @@ class PtychographyModel(ForwardModel):
             self._check_static(probe_defocus_mm, probe_pos_offset, probe_pos_correction, prj_pos_offset)
             target = self._target(this_i_theta, this_ind_batch)
             self._run(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, target, want_grad=False,
-                      probe_pos_correction=probe_pos_correction, this_ind_batch=this_ind_batch)
+                      probe_pos_correction=probe_pos_correction, this_ind_batch=this_ind_batch, prj_pos_offset=prj_pos_offset)
             self._queue_loss()
             return self.current_loss
         calculate_loss.forward_model = self
@@ -520,10 +560,12 @@ class PtychographyModel(ForwardModel):
             target = self._target(this_i_theta, this_ind_batch)
         i_pr, i_pi = self.get_argument_index('probe_real'), self.get_argument_index('probe_imag')
         i_pc = self.get_argument_index('probe_pos_correction')
+        i_po = self.get_argument_index('prj_pos_offset')
         want_probe = (i_pr in opt_args_ls) or (i_pi in opt_args_ls)
         gp, gsh = self._run(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, target, want_grad=True, grad_obj=grad_obj,
                             want_probe_grad=want_probe, probe_pos_correction=probe_pos_correction, this_ind_batch=this_ind_batch,
-                            want_shift_grad=i_pc in opt_args_ls, side_hook=_side_hook, init_grad=_init_grad)
+                            want_shift_grad=i_pc in opt_args_ls, side_hook=_side_hook, init_grad=_init_grad,
+                            prj_pos_offset=prj_pos_offset, want_offset_grad=i_po in opt_args_ls)
         self._queue_loss()          # self.current_loss fetches it on first access
         out = []
         for i in opt_args_ls:
@@ -534,6 +576,8 @@ class PtychographyModel(ForwardModel):
                 out.append(gp)
             elif i == i_pc:
                 out.append(gsh)             # DeviceArray, dense like probe_pos_correction (zero outside this minibatch)
+            elif i == i_po:
+                out.append(self._grad_offset_dev)       # DeviceArray [n_theta, 2], zero outside this angle
             else:
                 raise NotImplementedError("gradient w.r.t. '%s' is outside the accelerated path" % self.argument_ls[i])
         return tuple(out)
@@ -562,6 +606,8 @@ class SparseMultisliceModel(PtychographyModel):
         if self.engine is not None and getattr(self.engine, 'slice_pos', None) is None:
             raise ValueError('SparseMultisliceModel needs an engine built with slice_pos_cm (the slice positions in cm)')
         self._slice_pos_host = None
+
+    REFUSED_FLAGS = PtychographyModel.REFUSED_FLAGS + ('optimize_prj_pos_offset',)      # (no exit-wave shifts on a sparse plan)
 
     def _set_slice_pos(self, slice_pos_cm_ls):
         eng = self.engine

@@ -130,7 +130,7 @@ class MultisliceEngine(object):
                  fresnel_approx=True, sign_convention=1, normalize_fft=False, kernel=None, scale_ri_by_k=True,
                  n_probe_modes=1, max_batch=None, loss_function_type='lsq', poisson_multiplier=1., unknown_type='delta_beta',
                  beamstop=None, generic=False, transmission_cache=True, transmissions_only=False, streamed=False,
-                 workspace_budget=4 << 30, slice_pos_cm=None):
+                 workspace_budget=4 << 30, slice_pos_cm=None, exit_shift=False):
         """``free_prop_cm``: 0 / None (exit wave), 'inf' (far field), a distance in cm (Fresnel propagation to the detector), or
         a SEQUENCE of n distances: position b of every launch is propagated to distance b % n (multi-distance data divided into
         sub-tiles, adorym/forward_model.py:999-1018 -- the caller lists every tile n times in a row, ``n_dists`` = n).
@@ -145,7 +145,11 @@ class MultisliceEngine(object):
         ``slice_pos_cm``: a sequence of obj_size[2] slice positions in cm -- SPARSE multislice (adorym/propagate.py:479-534): the
         slices sit at these depths and every gap has its own Fresnel-approximation transfer function, built on the device from
         ``self.slice_pos`` (DeviceArray float32 [S]; whoever changes it in place calls ``slice_pos_changed()``).  Always the
-        streamed plan, whatever the probe size; ``binning`` must be 1; ``kernel`` / ``fresnel_approx`` do not apply to the gaps."""
+        streamed plan, whatever the probe size; ``binning`` must be 1; ``kernel`` / ``fresnel_approx`` do not apply to the gaps.
+
+        ``exit_shift``: the engine takes one sub-pixel offset per position for the field behind the last slice (per-angle
+        projection alignment, adorym/propagate.py:260-261: ``multislice(exit_shifts=...)``).  Always the streamed plan, whatever
+        the probe size; not together with ``slice_pos_cm`` or a sequence of detector distances."""
         self.ctx = ctx
         self.obj_size = tuple(int(v) for v in obj_size)
         self.probe_size = tuple(int(v) for v in probe_size)
@@ -187,6 +191,13 @@ class MultisliceEngine(object):
             if dists and len(dists) > 1:
                 raise NotImplementedError('slice_pos_cm: sparse multislice with a sequence of detector distances is not implemented')
             streamed = True                   # (the one path that applies a transfer function of its own per gap)
+        self.exit_shift = bool(exit_shift)
+        if self.exit_shift:
+            if slice_pos_cm is not None:
+                raise NotImplementedError('exit_shift together with slice_pos_cm (sparse multislice) is not implemented')
+            if dists and len(dists) > 1:
+                raise NotImplementedError('exit_shift together with a sequence of detector distances is not implemented')
+            streamed = True                   # (the one path whose detector convolution is a launch of its own)
         plan_kw = dict(binning=binning, n_modes=n_probe_modes, sign_convention=sign_convention, det_mode=det, normalize_fft=normalize_fft,
                        h_free=h_free, loss_type={'lsq': _lib.LOSS_LSQ, 'poisson': _lib.LOSS_POISSON}[loss_function_type],
                        poisson_multiplier=poisson_multiplier, unknown_type=unknown_type)
@@ -205,6 +216,8 @@ class MultisliceEngine(object):
             self.slice_pos = ctx.array(slice_pos_cm.astype(np.float32))
             self._sparse_args = (float(lmbda_nm), float(voxel_nm[0]), float(voxel_nm[1]))
             self.slice_pos_changed()
+        if self.exit_shift:
+            check(ctx.lib.adm_plan_set_exit_shift(self.plan.handle, 1))
         if dists and len(dists) > 1:
             self.plan.set_detector_kernels([get_kernel(d_ * 1e7, lmbda_nm, voxel_nm, self.probe_size, sign_convention=sign_convention)
                                             for d_ in dists])
@@ -398,7 +411,8 @@ class MultisliceEngine(object):
         return view
 
     def multislice(self, probe, grad_probe=None, want_grad=True, want_pred=False, grad_scale=None, accumulate=True,
-                   shifts=None, shift_index=None, grad_shifts=None, probes_b=None, grad_slice_pos=None):
+                   shifts=None, shift_index=None, grad_shifts=None, probes_b=None, grad_slice_pos=None,
+                   exit_shifts=None, exit_shift_index=None, grad_exit_shifts=None):
         """Launch the fused kernel on the batch given to set_batch().  Returns nothing; read
         results with loss() / pred().
 
@@ -411,12 +425,36 @@ class MultisliceEngine(object):
         full-field probe that the sub-tiles of multi-distance data see, adorym/forward_model.py:944-994); ``probe`` is ignored
         and no probe gradient is formed.
 
-        ``grad_slice_pos`` (DeviceArray float32 [S], +=; engines with ``slice_pos_cm`` only): dL/d slice_pos in 1/cm."""
+        ``grad_slice_pos`` (DeviceArray float32 [S], +=; engines with ``slice_pos_cm`` only): dL/d slice_pos in 1/cm.
+
+        ``exit_shifts`` (DeviceArray float32 [n_entries, 2] = (sy, sx); engines with ``exit_shift`` only): the field behind the
+        last slice of position b is Fourier-shifted by entry ``exit_shift_index[b]`` (DeviceArray int32 [B]; None = b) before the
+        detector step; ``grad_exit_shifts`` (float32 [n_entries, 2], +=) receives dL/d exit_shifts.  A far-field detector does
+        not see the shift: the gradient buffer is left as it is."""
         B = self._B
         Py, Px = self.probe_size
         if grad_scale is None:
             grad_scale = 2.0 / (B * self.n_det)       # d mean((pred-target)^2) / d pred
         lib = self.ctx.lib
+        xs = None
+        if exit_shifts is not None:
+            for other, name in ((shifts, 'shifts'), (probes_b, 'probes_b'), (self.slice_pos, 'slice_pos_cm')):
+                if other is not None:
+                    raise NotImplementedError('exit_shifts together with %s is not implemented' % name)
+            if not self.exit_shift:
+                raise ValueError('exit_shifts: the engine was built without exit_shift=True')
+            for a_, name in ((exit_shifts, 'exit_shifts'), (grad_exit_shifts, 'grad_exit_shifts')):
+                if a_ is not None and (a_.dtype != np.float32 or a_.size % 2):
+                    raise ValueError('%s must be float32 [n_entries, 2]' % name)
+            if grad_exit_shifts is not None and grad_exit_shifts.size != exit_shifts.size:
+                raise ValueError('grad_exit_shifts must have the shape of exit_shifts')
+            if exit_shift_index is None and exit_shifts.size < 2 * B:
+                raise ValueError('exit_shifts holds %d entries for %d positions and no exit_shift_index' % (exit_shifts.size // 2, B))
+            if exit_shift_index is not None and (exit_shift_index.dtype != np.int32 or exit_shift_index.size != B):
+                raise ValueError('exit_shift_index must be int32 [%d]' % B)
+            xs = (exit_shifts, exit_shift_index, grad_exit_shifts)
+        elif exit_shift_index is not None or grad_exit_shifts is not None:
+            raise ValueError('exit_shift_index / grad_exit_shifts need exit_shifts')
         if self.streamed and (shifts is not None or probes_b is not None):
             raise NotImplementedError('streamed multislice (probe %dx%d): sub-pixel probe shifts and per-position probes are not '
                                       'implemented on the streamed path' % (Py, Px))
@@ -428,7 +466,7 @@ class MultisliceEngine(object):
         self._acc_done = False
         self._next_loss_buffer()
         if self.streamed and len(self.rounds(B)) > 1:
-            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos)
+            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos, xs)
             return
         args = lambda pr_, gp_: self._ms_args(pr_, gp_, want_grad, want_pred, grad_scale, 0, B, self._ws)      # (the whole batch)
         if probes_b is not None:
@@ -438,7 +476,7 @@ class MultisliceEngine(object):
                 raise ValueError('probes_b must be [%d, %d, %d, %d, 2], got %r' % (B, self.n_probe_modes, Py, Px, tuple(probes_b.shape)))
             check(lib.adm_multislice_fwd_adj_pp(*args(probes_b, None)))
         elif shifts is None:
-            self._launch(args(probe, grad_probe), grad_slice_pos)
+            self._launch(args(probe, grad_probe), grad_slice_pos, xs)
         else:
             M = self.n_probe_modes
             if self._probes_b is None or self._probes_b.shape[0] < B:
@@ -465,8 +503,15 @@ class MultisliceEngine(object):
                 1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
                 self._pred.ptr + px if want_pred else None, self._loss.ptr + 4 * o, float(grad_scale), ws.ptr, ws.nbytes)
 
-    def _launch(self, args, grad_slice_pos=None):
-        if grad_slice_pos is not None:
+    def _launch(self, args, grad_slice_pos=None, xs=None, o=0):
+        """``xs``: (exit_shifts, exit_shift_index, grad_exit_shifts) of the whole batch; the launch starts at its position ``o``."""
+        if xs is not None:
+            s, idx, g = xs
+            # without an index, position b of the batch uses entry b: the round starting at o reads (and adds to) the entries from o on
+            so = 0 if idx is not None else 8 * o
+            check(self.ctx.lib.adm_multislice_fwd_adj_exit_shift(*(args + (s.ptr + so, idx.ptr + 4 * o if idx is not None else None,
+                                                                         g.ptr + so if g is not None else None))))
+        elif grad_slice_pos is not None:
             check(self.ctx.lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
         else:
             check(self.ctx.lib.adm_multislice_fwd_adj(*args))
@@ -483,15 +528,15 @@ class MultisliceEngine(object):
         for lo in range(0, n, self.MAX_COVER):
             check(lib.adm_tile_grad_accumulate_range(*(head + (lo, min(lo + self.MAX_COVER, n), 1 if add or lo else 0))))
 
-    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None):
+    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None, xs=None):
         """A streamed engine's batch that does not fit the workspace budget: one launch per round into the same workspace, each
         round's tile gradients overlap-added into grad_rot (zeroed first) before the next round overwrites them.  Losses,
         predictions and the probe gradient are those of one launch; the object gradient too, up to the order of the additions.
-        Every round adds its share to ``grad_slice_pos``."""
+        Every round adds its share to ``grad_slice_pos`` and to the gradient of the exit-wave shifts ``xs``."""
         if want_grad:
             check(self.ctx.lib.adm_memset(self.ctx.handle, self.grad_rot.ptr, 0, self.grad_rot.nbytes))
         for o, n in self.rounds(self._B):
-            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), grad_slice_pos)
+            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), grad_slice_pos, xs, o)
             if want_grad:
                 self._overlap_add(self._ws, o, n, 1, passes=self._check_cover(self._pos_host[o:o + n]) > self.MAX_COVER)
         # (every overlap-add above saw at most MAX_COVER tiles per pixel: nothing to check afterwards)

@@ -355,8 +355,7 @@ class _Run(object):
         _not_implemented(self.shrink_cycle is not None, 'shrink-wrap mask updates')
         _not_implemented(self.initial_tilt is not None, 'initial_tilt')
         _not_implemented(self.interpolation != 'bilinear', "interpolation='%s'" % self.interpolation)
-        for nm in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_prj_pos_offset', 'optimize_tilt',
-                   'optimize_ctf_lg_kappa'):
+        for nm in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_tilt', 'optimize_ctf_lg_kappa'):
             _not_implemented(getattr(self, nm), nm)
         if self.update_scheme not in ('immediate', 'per angle'):
             raise ValueError("update_scheme must be 'immediate' or 'per angle'")
@@ -417,6 +416,16 @@ class _Run(object):
             self.free_prop_cm = self.f.get('metadata/free_prop_cm')
         self.is_multi_dist = np.array(self.free_prop_cm).size != 1          # ptychography.py:296-305
         _not_implemented(self.is_sparse_multislice and self.is_multi_dist, 'sparse multislice (slice_pos_cm_ls) with multi-distance data')
+        if self.optimize_prj_pos_offset:
+            # per-angle projection alignment (ptychography.py:706, forward_model.py:255-256): the exit wave is shifted by the detector
+            # step of the streamed kernels, which take one probe set for all positions and one transfer function for all gaps
+            _not_implemented(self.is_sparse_multislice, 'optimize_prj_pos_offset with sparse multislice (slice_pos_cm_ls)')
+            _not_implemented(self.is_multi_dist, 'optimize_prj_pos_offset with multi-distance data')
+            _not_implemented(self.optimize_all_probe_pos or bool(np.any(probe_pos - np.round(probe_pos) > 1e-3)),
+                             'optimize_prj_pos_offset with sub-pixel probe positions (optimize_all_probe_pos or fractional probe_pos)')
+            if isinstance(self.free_prop_cm, str) and self.free_prop_cm == 'inf':
+                warnings.warn('optimize_prj_pos_offset with a far-field detector: the magnitude of a Fourier transform does not depend on a '
+                              'shift of the exit wave, so the gradient is zero and the offsets cannot move.', UserWarning)
         self.holo_tiled = False
         if self.is_multi_dist:
             # one object slice; config 5 is one undivided field of view (n_blocks == 1) without a safe zone
@@ -507,7 +516,9 @@ class _Run(object):
                 # the rotation stores slice transmissions only; rotate_out_of_loop and plugin models read obj_rot
                 transmissions_only=(self.forward_model == 'auto' and not self.rotate_out_of_loop),
                 # probes too large for one workgroup's LDS (beyond 128 x 128) take the streamed kernels; so does sparse multislice
-                streamed='auto', slice_pos_cm=self.slice_pos_cm_ls if self.is_sparse_multislice else None, **common)
+                # ... and per-angle projection alignment (the exit-wave shift is part of their detector step)
+                streamed='auto', slice_pos_cm=self.slice_pos_cm_ls if self.is_sparse_multislice else None,
+                exit_shift=bool(self.optimize_prj_pos_offset), **common)
             # the rule of _shift_args (forward_model.py): sub-pixel shifts when the corrections are optimised or one exceeds 1e-3
             _not_implemented(self.engine.streamed and (self.optimize_all_probe_pos or bool(np.any(self.probe_pos - self.probe_pos_int > 1e-3))),
                              'sub-pixel probe positions (optimize_all_probe_pos or fractional probe_pos) with a %d x %d probe '
@@ -614,7 +625,8 @@ class _Run(object):
                            this_obj_size=self.obj_size, n_theta=self.n_theta, theta_ls=self.theta_ls, energy_ev=self.energy_ev,
                            psize_cm=self.psize_cm, h=self.h, free_prop_cm=self.free_prop_cm, minibatch_size=self.minibatch_size,
                            n_probe_modes=self.n_probe_modes, beamstop=self.beamstop, optimize_probe_defocusing=False,
-                           optimize_probe_pos_offset=False, optimize_prj_pos_offset=False, optimize_all_probe_pos=self.optimize_all_probe_pos,
+                           optimize_probe_pos_offset=False, optimize_prj_pos_offset=bool(self.optimize_prj_pos_offset),
+                           optimize_all_probe_pos=self.optimize_all_probe_pos,
                            optimize_tilt=False, output_folder=self.output_folder, debug=self.debug)
         fm_args = dict(loss_function_type=self.loss_function_type, distribution_mode=self.distribution_mode, device=ctx,
                        common_vars_dict=common_vars, raw_data_type=self.raw_data_type, run_bfloat16=self.run_bfloat16,
@@ -718,6 +730,12 @@ class _Run(object):
             # (+ "regularize transformation of image 0": matrix 0 is pinned to the identity)
             self._add_small('prj_affine_ls', self.optimizer_prj_affine, self.prj_affine_learning_rate,
                             pin=ctx.array(np.array([[1., 0, 0], [0, 1., 0]]), np.float32))
+        if self.optimize_prj_pos_offset:
+            # optimizers.py:863-875: plain gradient descent with a constant step unless an optimiser is supplied
+            gd = GDOptimizer('prj_pos_offset', output_folder=self.output_folder,
+                             options_dict={'step_size': self.prj_pos_offset_learning_rate, 'dynamic_rate': False})
+            self._add_small('prj_pos_offset', self.optimizer_prj_pos_offset if self.optimizer_prj_pos_offset is not None else gd,
+                            self.prj_pos_offset_learning_rate)
         if self.optimize_all_probe_pos:
             # optimizers.py:877-889: Adam on probe_pos_correction [n_theta, n_pos, 2] (+ "prevent position drifting": subtract the
             # mean over (theta, position))
@@ -726,6 +744,7 @@ class _Run(object):
             # optimizers.py:891-903, 1051-1060: Adam on the slice positions (+ "prevent position drifting": subtract the first)
             self._add_small('slice_pos_cm_ls', self.optimizer_slice_pos, self.slice_pos_learning_rate, anchor=True)
         self.slice_pos_history = None         # (return_state: the positions after every update, copied on the device)
+        self.prj_pos_offset_history = None    # (likewise: the offsets after every update)
 
         restored = self.restored_params
         if restored is not None:
@@ -1130,6 +1149,14 @@ class _Run(object):
                 if k < hist.shape[0]:
                     _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * z.size * k, z.ptr, z.nbytes))
                     self.slice_pos_history[1] = k + 1
+        if any(p.key == 'prj_pos_offset' for p in due) and self.return_state and self.n_epochs != 'auto':
+            x = self.optimizable_params['prj_pos_offset']
+            if self.prj_pos_offset_history is None:
+                self.prj_pos_offset_history = [self.ctx.zeros((int(self.n_epochs) * self.n_batch,) + tuple(x.shape)), 0]
+            hist, k = self.prj_pos_offset_history
+            if k < hist.shape[0]:
+                _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * x.size * k, x.ptr, x.nbytes))
+                self.prj_pos_offset_history[1] = k + 1
 
     def _write_intermediate(self, i_batch):
         """output_object(full_output=False) + output_intermediate_parameters of the reference: object TIFFs under
@@ -1152,6 +1179,9 @@ class _Run(object):
                     np.savetxt(os.path.join(d_, 'probe_pos_correction_{}_{}_{}.txt'.format(i_epoch, i_batch, i_t)), v_[i_t])
             elif p.key == 'prj_affine_ls':
                 np.savetxt(os.path.join(d_, 'prj_affine_{}.txt'.format(i_epoch)), np.concatenate(v_, 0))
+            elif p.key == 'prj_pos_offset':         # one line per output, appended (optimizers.py:1135-1138)
+                with open(os.path.join(d_, 'prj_pos_offset.txt'), 'a' if i_batch > 0 or i_epoch > 0 else 'w') as f_:
+                    f_.write('{:4d}, {:4d}, {}\n'.format(i_epoch, i_batch, [float(x_) for x_ in v_.flatten()]))
             else:
                 np.savetxt(os.path.join(d_, '{}_{}.txt'.format(p.key, i_epoch)), np.atleast_1d(v_))
 
@@ -1182,4 +1212,7 @@ class _Run(object):
                 'free_prop_cm': _host(params.get('free_prop_cm', self.free_prop_cm)), 'prj_affine_ls': _host(params.get('prj_affine_ls')),
                 'slice_pos_cm_ls': _host(params.get('slice_pos_cm_ls')),
                 'slice_pos_history': None if self.slice_pos_history is None else self.slice_pos_history[0].get()[:self.slice_pos_history[1]],
+                'prj_pos_offset': np.asarray(_host(params['prj_pos_offset'])),
+                'prj_pos_offset_history': (None if self.prj_pos_offset_history is None
+                                           else self.prj_pos_offset_history[0].get()[:self.prj_pos_offset_history[1]]),
                 'losses': self.loss_history, 'output_folder': self.output_folder}

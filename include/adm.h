@@ -368,6 +368,26 @@ int adm_multislice_fwd_adj_sparse(adm_plan* plan, const float* obj_rot, const fl
                                   float grad_scale, void* workspace, size_t workspace_bytes, float* grad_slice_pos);
 int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n);
 
+/* ---- per-angle projection alignment (streamed plans) ------------------------------------
+ * One sub-pixel offset (s_y, s_x) per projection angle (adorym/propagate.py:260-261, util.py:380-397: shift_exit_wave): the field
+ * behind the last slice is Fourier-shifted before the free-space step,
+ *   Psi_det = IFFT2( Phi * H_free * FFT2(Psi_S) ),  Phi[ky,kx] = exp(-2 PI i (fx s_x + fy s_y)),  f = fftfreq(n, 1),
+ * H_free = 1 for ADM_DET_NONE.  A far-field magnitude does not depend on the shift: with ADM_DET_FARFIELD the launch is
+ * adm_multislice_fwd_adj's and grad_shifts is left untouched.
+ * adm_plan_set_exit_shift(plan, 1) switches a STREAMED plan to it (plans of adm_plan_create: ADM_ERR_UNSUPPORTED; so are plans
+ * with slice positions or several detector kernels).  Call it before the workspace is sized: adm_plan_workspace_bytes grows by
+ * one kept spectrum [B][M][Py][Px] and the gradient partials.  A plan without the switch reports the sizes it always did.
+ * adm_multislice_fwd_adj_exit_shift takes the arguments of adm_multislice_fwd_adj and
+ *   shifts       device float [n_entries][2] = (s_y, s_x) in pixels
+ *   index        device int32 [batch]: position b uses entry index[b]; NULL = entry b
+ *   grad_shifts  device float [n_entries][2], dL/ds ACCUMULATED into it (want_grad = 1), or NULL
+ * The terms of every entry are summed in fp64 in a fixed order (no atomics): two calls give the same bits. */
+int adm_plan_set_exit_shift(adm_plan* plan, int on);
+int adm_multislice_fwd_adj_exit_shift(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
+                                      const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
+                                      float grad_scale, void* workspace, size_t workspace_bytes, const float* shifts,
+                                      const int32_t* index, float* grad_shifts);
+
 /* ---- f2  sub-pixel probe positions -----------------------------------------------------
  * realign_image_fourier (adorym/util.py:380-397) applied to every probe mode for every position of a minibatch:
  *   probes_out[b][m] = IFFT2( exp(-2 PI i (fx*sx_b + fy*sy_b)) * FFT2(probe[m]) ),  PI = 3.14159265359, f = fftfreq.
