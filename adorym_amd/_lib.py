@@ -130,6 +130,8 @@ SIGNATURES = {
     'adm_multislice_fwd_adj_sparse': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _SZ, _VP]),
     'adm_slice_positions_anchor': (_I, [_VP, _VP, _I]),
     'adm_plan_set_exit_shift': (_I, [_VP, _I]),
+    'adm_plan_set_probe_shift': (_I, [_VP, _I]),
+    'adm_multislice_fwd_adj_probe_shift': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _SZ, _VP, _VP, _VP]),
     'adm_multislice_fwd_adj_exit_shift': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _SZ, _VP, _VP, _VP]),
     'adm_probe_shift': (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     'adm_probe_shift_adj': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP]),

@@ -396,6 +396,9 @@ extern "C" int adm_plan_set_detector_kernels(adm_plan* plan, int n, const float*
     if (n > 1 && plan->streamed)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_kernels: several detector kernels need one probe set per position "
                                          "(adm_multislice_fwd_adj_pp), which streamed plans do not run");
+    if (n > 1 && plan->probe_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_kernels: several detector kernels on a plan with probe shifts "
+                                         "(adm_plan_set_probe_shift) are not implemented");
     if (plan->d.det_mode != ADM_DET_FRESNEL) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_kernels: the plan's det_mode is not ADM_DET_FRESNEL");
     const size_t npx = (size_t)plan->d.probe_y * plan->d.probe_x, tot = npx * (size_t)n;
     float2 *a = nullptr, *b = nullptr;
@@ -448,7 +451,8 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     const bool sparse = plan->streamed && plan->n_zpos >= 2;
     const size_t n_conv = sparse ? (size_t)plan->n_zpos - 1 : 0;
     const bool xshift = plan->streamed && plan->exit_shift;
-    const bool dbl = sparse || xshift;       // the layout holds doubles
+    const bool pshift = plan->streamed && plan->probe_shift;
+    const bool dbl = sparse || xshift || pshift;       // the layout holds doubles
     WsLayout w;
     size_t at = 0;
     auto take = [&at](size_t bytes) { const size_t off = at; at += bytes; return off; };
@@ -468,6 +472,8 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     w.dd_part = take(n_conv * B * M * cg * sizeof(double));
     w.xs_keep = take(xshift ? B * M * fld : 0);
     w.xs_part = take(xshift ? B * M * cg * 2 * sizeof(double) : 0);
+    w.ps_phat = take(pshift ? M * fld : 0);
+    w.ps_part = take(pshift ? B * M * cg * 2 * sizeof(double) : 0);
     w.total = at;
     return w;
 }
@@ -482,6 +488,9 @@ extern "C" int adm_plan_set_slice_positions(adm_plan* plan, const float* z_cm_de
     if (n != 0 && plan->exit_shift)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions together with exit-wave shifts "
                                          "(adm_plan_set_exit_shift) are not implemented");
+    if (n != 0 && plan->probe_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions together with probe shifts "
+                                         "(adm_plan_set_probe_shift) are not implemented");
     if (n == 0) {
         plan->zpos_dev = nullptr;
         plan->n_zpos = 0;
@@ -521,7 +530,13 @@ extern "C" int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n) 
 // The launch of a streamed plan: fields and loss partials from the layout; on a sparse plan also the tables of the gaps (rebuilt
 // first if the slice positions changed), the kept spectra and the dL/dd partials.
 static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* ws, const WsLayout& w, float* grad_slice_pos,
-                           const StExitShiftLaunch* shift) {
+                           const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift) {
+    StProbeShiftLaunch ps;
+    if (pshift) {
+        ps = *pshift;
+        ps.phat = (float2*)(ws + w.ps_phat);
+        ps.part = (double*)(ws + w.ps_part);
+    }
     StExitShiftLaunch xs;
     if (shift) {
         xs = *shift;
@@ -547,14 +562,14 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
         sp.grad_z = grad_slice_pos;
     }
     ADM_HIP(ms_streamed_launch(p, batch, (float2*)(ws + w.field), (float*)(ws + w.loss_part), plan->ctx->stream, sparse ? &sp : nullptr,
-                               shift ? &xs : nullptr));
+                               shift ? &xs : nullptr, pshift ? &ps : nullptr));
     return ADM_OK;
 }
 
 int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
                          const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
                          float grad_scale, void* workspace, size_t workspace_bytes, bool per_position, float* grad_slice_pos,
-                         const StExitShiftLaunch* shift) {
+                         const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift) {
     if (!plan || !obj_rot || !probe || !pos || !target || !loss_sum)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: null argument");
     if (batch <= 0) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: batch must be positive");
@@ -632,7 +647,7 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         for (int i = 0; i < 8; ++i) { p.gen_rx[i] = plan->gen_rx[i]; p.gen_ry[i] = plan->gen_ry[i]; }
         p.gen_twid_y = plan->twid_y_dev; p.gen_hs = plan->hs_dev; p.gen_hfree_s = plan->hfree_s_dev;
         if (plan->streamed) {
-            const int rc = streamed_launch(plan, p, batch, ws, w, grad_slice_pos, shift);
+            const int rc = streamed_launch(plan, p, batch, ws, w, grad_slice_pos, shift, pshift);
             if (rc) return rc;
         } else {
             ADM_HIP(ms_generic_launch(p, batch, plan->ctx->stream));
@@ -684,6 +699,9 @@ extern "C" int adm_plan_set_exit_shift(adm_plan* plan, int on) {
                                          "are not implemented");
     if (on && plan->n_hfree > 1)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with several detector kernels are not implemented");
+    if (on && plan->probe_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with probe shifts (adm_plan_set_probe_shift) "
+                                         "are not implemented");
     plan->exit_shift = on != 0;
     return ADM_OK;
 }
@@ -701,6 +719,39 @@ extern "C" int adm_multislice_fwd_adj_exit_shift(adm_plan* plan, const float* ob
     xs.shifts = shifts; xs.index = index; xs.grad_shifts = grad_shifts; xs.keep = nullptr; xs.part = nullptr;
     return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
                            workspace_bytes, false, nullptr, &xs);
+}
+
+extern "C" int adm_plan_set_probe_shift(adm_plan* plan, int on) {
+    if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_probe_shift: null plan");
+    if (!plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts inside the sweep need a streamed plan "
+                                         "(adm_plan_create_streamed); the one-workgroup kernels take them through adm_probe_shift");
+    if (on && plan->n_zpos > 0)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with slice positions (sparse multislice) "
+                                         "are not implemented");
+    if (on && plan->exit_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with exit-wave shifts (adm_plan_set_exit_shift) "
+                                         "are not implemented");
+    if (on && plan->n_hfree > 1)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with several detector kernels are not implemented");
+    plan->probe_shift = on != 0;
+    return ADM_OK;
+}
+
+extern "C" int adm_multislice_fwd_adj_probe_shift(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
+                                                  const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
+                                                  float grad_scale, void* workspace, size_t workspace_bytes, const float* shifts,
+                                                  const int32_t* index, float* grad_shifts) {
+    if (plan && !plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_multislice_fwd_adj_probe_shift: probe shifts inside the sweep need a streamed plan "
+                                         "(adm_plan_create_streamed)");
+    if (plan && !plan->probe_shift)
+        return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_probe_shift: the plan was not switched to probe shifts (adm_plan_set_probe_shift)");
+    if (!shifts) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_probe_shift: null shifts");
+    StProbeShiftLaunch ps;
+    ps.shifts = shifts; ps.index = index; ps.grad_shifts = want_grad ? grad_shifts : nullptr; ps.phat = nullptr; ps.part = nullptr;
+    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
+                           workspace_bytes, false, nullptr, nullptr, &ps);
 }
 
 extern "C" int adm_multislice_fwd_adj_pp(adm_plan* plan, const float* obj_rot, const float* probes, const int32_t* pos, int batch,

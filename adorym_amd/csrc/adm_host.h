@@ -53,6 +53,7 @@ struct adm_plan {
     float2* sp_hs_dev = nullptr;     // [n_zpos-1][Py*Px] H_s / (Py*Px)
     float* sp_a_dev = nullptr;       // [Py] then [Px]: a_yx = sp_a[y] + sp_a[Py + x], the phase of H per nm
     bool exit_shift = false;         // adm_plan_set_exit_shift (streamed plans): the workspace holds the kept spectrum and the dL/ds partials
+    bool probe_shift = false;        // adm_plan_set_probe_shift (streamed plans): the workspace holds FFT2(probe) and the dL/ds partials
     // adm_tile_cover_build: the cover lists in workspace `ws` are current for (pos, batch, window); a few entries, so that every
     // round of a batch launched in parts can have its lists built ahead
     struct CoverKey { const void* ws; const void* pos; int batch, row0, nrows; unsigned long long fp; } cover_keys[4] = {};
@@ -83,6 +84,8 @@ struct WsLayout {
     size_t dd_part;     // sparse plans: [S-1][B*M*cg] double dL/dd partials
     size_t xs_keep;     // plans with exit-wave shifts (streamed): [B][M][Py][Px] kept detector-step spectra
     size_t xs_part;     // plans with exit-wave shifts: [B*M*cg][2] double dL/ds partials
+    size_t ps_phat;     // plans with probe shifts (streamed): [M][Py][Px] FFT2 of the probe modes
+    size_t ps_part;     // plans with probe shifts: [B*M*cg][2] double dL/ds partials
     size_t total;
 };
 WsLayout ws_layout(const adm_plan* plan, int batch);
@@ -91,11 +94,12 @@ hipError_t probe_grad_reduce(const float2* part, int batch, size_t n, float2* ou
 hipError_t probe_grad_reduce_large(float2* part, int batch, size_t n, float2* out, hipStream_t st);   // two levels, `part` is scratch
 hipError_t ms_launch(int n, const MsParams& p, int batch, hipStream_t st);
 struct StExitShiftLaunch;
+struct StProbeShiftLaunch;
 // adm_multislice_fwd_adj's body (per_position: one probe set per position)
 int multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch, const float* target,
                     int want_grad, float* grad_probe, float* pred, float* loss_sum, float grad_scale, void* workspace,
                     size_t workspace_bytes, bool per_position, float* grad_slice_pos = nullptr,
-                    const StExitShiftLaunch* shift = nullptr);
+                    const StExitShiftLaunch* shift = nullptr, const StProbeShiftLaunch* pshift = nullptr);
 bool ms_generic_supported(int py, int px);
 int ms_generic_threads(int py, int px);
 hipError_t ms_generic_launch(const MsParams& p, int batch, hipStream_t st);
@@ -135,10 +139,27 @@ struct StExitShiftLaunch {
 hipError_t ms_exitshift_col_launch(const MsParams& p, int batch, float2* fld, const float2* hs, bool conj, const StExitShiftLaunch& xs,
                                    hipStream_t st);
 hipError_t ms_exitshift_reduce_launch(const MsParams& p, int batch, const StExitShiftLaunch& xs, hipStream_t st);
+// sub-pixel probe positions on streamed plans (adm_plan_set_probe_shift, adm_ms_probeshift.hip): the probe modes Fourier-shifted
+// by an offset per position inside the sweep
+struct StProbeShift {          // kernel argument
+    const float2* shifts;      // [n_entries] (s_y, s_x)
+    const int* index;          // [B] entry of position b, or nullptr: b
+    const float2* phat;        // [M][Py][Px] FFT2(probe_m), unnormalised
+    double* part;              // [B*M*column groups][2] dL/ds partials (before the factor 2 PI), or nullptr: no sums
+};
+struct StProbeShiftLaunch {
+    const float* shifts; const int32_t* index;
+    float* grad_shifts;        // [n_entries][2] += dL/ds, or nullptr
+    float2* phat; double* part;
+};
+hipError_t ms_probeshift_spectrum_launch(const MsParams& p, float2* phat, hipStream_t st);
+hipError_t ms_probeshift_col_launch(const MsParams& p, int batch, float2* fld, bool conj, const StProbeShift& q, hipStream_t st);
+hipError_t ms_probeshift_reduce_launch(const MsParams& p, int batch, const StProbeShift& q, float* grad_shifts, hipStream_t st);
 // the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials;
-// sp: the tables of a sparse plan, or nullptr; xs: the exit-wave shifts of a plan with adm_plan_set_exit_shift, or nullptr
+// sp: the tables of a sparse plan, or nullptr; xs: the exit-wave shifts of a plan with adm_plan_set_exit_shift, or nullptr; ps:
+// the probe shifts of a plan with adm_plan_set_probe_shift, or nullptr
 hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp = nullptr,
-                              const StExitShiftLaunch* xs = nullptr);
+                              const StExitShiftLaunch* xs = nullptr, const StProbeShiftLaunch* ps = nullptr);
 hipError_t shift_launch(int n, const ShiftParams& q, int batch, bool adjoint, hipStream_t st);
 }  // namespace adm
 

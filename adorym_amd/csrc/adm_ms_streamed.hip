@@ -23,6 +23,8 @@
 //                      * conj(t_s), then the row FFT of the next convolution -- or, at s = 0, the probe-gradient slot
 //             col:     the conj(H) convolution between the steps
 //   then probe_grad_reduce sums the slots (adm_api.hip).
+// A plan with probe shifts (adm_plan_set_probe_shift) puts three launches in front of the sweep and up to three behind it
+// (adm_ms_probeshift.hip lists them).
 //
 // Row launches: one workgroup per (position, group of whole rows), all modes in turn (the slice factors are loaded once and the
 // tile gradient of the modes is summed in registers).  Column launches: one workgroup per (position, mode, 8 adjacent columns;
@@ -427,7 +429,7 @@ hipError_t ms_sparse_anchor_launch(float* z, int n, hipStream_t st) {
 int ms_sparse_max_slices() { return ST_MAX_SLICES; }
 
 hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp,
-                              const StExitShiftLaunch* xs) {
+                              const StExitShiftLaunch* xs, const StProbeShiftLaunch* ps) {
     const int Py = p.gen_py, Px = p.gen_px, S = p.n_steps, M = p.n_modes;
     if (!ms_streamed_supported(Py, Px)) return hipErrorInvalidValue;
     // exit-wave shifts (adm_ms_exitshift.hip): a far-field magnitude does not see them; an exit-wave detector takes the Fresnel
@@ -480,10 +482,22 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
     };
     auto det_col = [&](bool conj) { return xs ? ms_exitshift_col_launch(p, batch, fld, hfree_s, conj, *xs, st) : col(hfree_s, conj); };
     hipError_t e = hipSuccess;
+    // sub-pixel probe positions: Phat = FFT2(probe) once, then the fields of every (position, mode) up to their row IFFT, which
+    // the first row launch of the sweep does in front of its modulation
+    StProbeShift pq;
+    if (ps) {
+        pq.shifts = (const float2*)ps->shifts; pq.index = ps->index; pq.phat = ps->phat; pq.part = nullptr;
+        StRow r;
+        r.rows = rows; r.step = 0; r.mode = 0; r.pre = 0; r.post = 1; r.from_probe = 1; r.to_gprobe = 0;
+        hipLaunchKernelGGL(st_row_kernel, dim3(ngr), dim3(ST_ROW_NT), 0, st, p, r, ps->phat);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = ms_probeshift_spectrum_launch(p, ps->phat, st)) != hipSuccess) return e;
+        if ((e = ms_probeshift_col_launch(p, batch, fld, false, pq, st)) != hipSuccess) return e;
+    }
     // ---------------- forward ----------------
     const int det_row = far ? (p.det_inverse ? 2 : 1) : (fresnel ? 1 : 0);     // the row transform that starts the detector propagation
     for (int s = 0; s < S && e == hipSuccess; ++s) {
-        e = row(s, 1, s > 0 ? 2 : 0, s < S - 1 ? 1 : det_row, s == 0, 0);
+        e = row(s, 1, s > 0 || ps ? 2 : 0, s < S - 1 ? 1 : det_row, s == 0 && !ps, 0);
         if (e == hipSuccess && s < S - 1) e = conv(s, false);
     }
     if (e == hipSuccess && fresnel) {
@@ -502,9 +516,19 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         if (e == hipSuccess) e = det_col(true);
     }
     const int adj_row = far ? (p.det_inverse ? 1 : 2) : (fresnel ? 2 : 0);
+    // (probe shifts: the last row launch ends with the row FFT of the shift's adjoint and leaves the field in the buffer)
+    const bool ps_adj = ps && (p.grad_probe || ps->grad_shifts);
     for (int s = S - 1; s >= 0 && e == hipSuccess; --s) {
-        e = row(s, 2, s == S - 1 ? adj_row : 2, s > 0 ? 1 : 0, 0, s == 0);
+        e = row(s, 2, s == S - 1 ? adj_row : 2, s > 0 || ps_adj ? 1 : 0, 0, s == 0 && !ps_adj);
         if (e == hipSuccess && s > 0) e = conv(s - 1, true);
+    }
+    if (e == hipSuccess && ps_adj) {
+        pq.part = ps->grad_shifts ? ps->part : nullptr;
+        e = ms_probeshift_col_launch(p, batch, fld, true, pq, st);
+        if (e == hipSuccess && p.grad_probe) e = row(0, 0, 2, 0, 0, 1);
+        if (e == hipSuccess && ps->grad_shifts) {
+            e = ms_probeshift_reduce_launch(p, batch, pq, ps->grad_shifts, st);
+        }
     }
     if (e == hipSuccess && zgrad) {
         hipLaunchKernelGGL(st_sparse_reduce_kernel, dim3(1), dim3(256), 0, st, sp->part, batch * M * ncg, S - 1, sp->grad_z);

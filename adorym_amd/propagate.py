@@ -130,7 +130,7 @@ class MultisliceEngine(object):
                  fresnel_approx=True, sign_convention=1, normalize_fft=False, kernel=None, scale_ri_by_k=True,
                  n_probe_modes=1, max_batch=None, loss_function_type='lsq', poisson_multiplier=1., unknown_type='delta_beta',
                  beamstop=None, generic=False, transmission_cache=True, transmissions_only=False, streamed=False,
-                 workspace_budget=4 << 30, slice_pos_cm=None, exit_shift=False):
+                 workspace_budget=4 << 30, slice_pos_cm=None, exit_shift=False, probe_shift=False):
         """``free_prop_cm``: 0 / None (exit wave), 'inf' (far field), a distance in cm (Fresnel propagation to the detector), or
         a SEQUENCE of n distances: position b of every launch is propagated to distance b % n (multi-distance data divided into
         sub-tiles, adorym/forward_model.py:999-1018 -- the caller lists every tile n times in a row, ``n_dists`` = n).
@@ -140,7 +140,11 @@ class MultisliceEngine(object):
         probe size, else the latter.  ``self.streamed`` tells which.  A streamed engine runs a batch in rounds whose workspace
         fits ``workspace_budget`` bytes (a position keeps n_steps * Py * Px complex numbers per mode: 134 MB at 256 x 256 and
         256 slices); each round is overlap-added before the next reuses the workspace.  Streamed engines take one probe set
-        shared by all positions: no ``shifts`` / ``probes_b`` and no multi-distance sequence.
+        shared by all positions: no ``probes_b``, no multi-distance sequence, and ``shifts`` only with ``probe_shift``.
+
+        ``probe_shift``: a streamed engine applies ``multislice(shifts=...)`` inside its sweep (adm_plan_set_probe_shift).  It does
+        not change which plan 'auto' picks: on a one-workgroup plan it does nothing and adm_probe_shift serves ``shifts`` as
+        always.  Not together with ``slice_pos_cm``, ``exit_shift`` or a sequence of detector distances.
 
         ``slice_pos_cm``: a sequence of obj_size[2] slice positions in cm -- SPARSE multislice (adorym/propagate.py:479-534): the
         slices sit at these depths and every gap has its own Fresnel-approximation transfer function, built on the device from
@@ -198,6 +202,13 @@ class MultisliceEngine(object):
             if dists and len(dists) > 1:
                 raise NotImplementedError('exit_shift together with a sequence of detector distances is not implemented')
             streamed = True                   # (the one path whose detector convolution is a launch of its own)
+        if probe_shift:
+            if slice_pos_cm is not None:
+                raise NotImplementedError('probe_shift together with slice_pos_cm (sparse multislice) is not implemented')
+            if self.exit_shift:
+                raise NotImplementedError('probe_shift together with exit_shift (per-angle projection alignment) is not implemented')
+            if dists and len(dists) > 1:
+                raise NotImplementedError('probe_shift together with a sequence of detector distances is not implemented')
         plan_kw = dict(binning=binning, n_modes=n_probe_modes, sign_convention=sign_convention, det_mode=det, normalize_fft=normalize_fft,
                        h_free=h_free, loss_type={'lsq': _lib.LOSS_LSQ, 'poisson': _lib.LOSS_POISSON}[loss_function_type],
                        poisson_multiplier=poisson_multiplier, unknown_type=unknown_type)
@@ -218,6 +229,9 @@ class MultisliceEngine(object):
             self.slice_pos_changed()
         if self.exit_shift:
             check(ctx.lib.adm_plan_set_exit_shift(self.plan.handle, 1))
+        self.probe_shift = bool(probe_shift) and self.streamed
+        if self.probe_shift:
+            check(ctx.lib.adm_plan_set_probe_shift(self.plan.handle, 1))
         if dists and len(dists) > 1:
             self.plan.set_detector_kernels([get_kernel(d_ * 1e7, lmbda_nm, voxel_nm, self.probe_size, sign_convention=sign_convention)
                                             for d_ in dists])
@@ -419,7 +433,8 @@ class MultisliceEngine(object):
         ``shifts`` (DeviceArray float [n_entries,2] = (sy, sx)) switches to one Fourier-shifted probe set per position
         (adorym/forward_model.py:296-311); position b uses entry ``shift_index[b]`` (DeviceArray int32 [B]; None = b).
         With want_grad, ``grad_probe`` (+=) and ``grad_shifts`` (float [n_entries,2], +=) then receive the gradients
-        taken through the shift.
+        taken through the shift.  A streamed engine takes ``shifts`` only when built with ``probe_shift=True`` and then applies
+        them inside its sweep (adm_multislice_fwd_adj_probe_shift): no probe set per position exists.
 
         ``probes_b`` (DeviceArray [B, n_modes, Py, Px, 2]): one probe set per position handed over as it is (the windows of a
         full-field probe that the sub-tiles of multi-distance data see, adorym/forward_model.py:944-994); ``probe`` is ignored
@@ -455,7 +470,8 @@ class MultisliceEngine(object):
             xs = (exit_shifts, exit_shift_index, grad_exit_shifts)
         elif exit_shift_index is not None or grad_exit_shifts is not None:
             raise ValueError('exit_shift_index / grad_exit_shifts need exit_shifts')
-        if self.streamed and (shifts is not None or probes_b is not None):
+        ps = None
+        if self.streamed and (probes_b is not None or (shifts is not None and not self.probe_shift)):
             raise NotImplementedError('streamed multislice (probe %dx%d): sub-pixel probe shifts and per-position probes are not '
                                       'implemented on the streamed path' % (Py, Px))
         if grad_slice_pos is not None:
@@ -463,10 +479,21 @@ class MultisliceEngine(object):
                 raise ValueError('grad_slice_pos: the engine was built without slice_pos_cm')
             if grad_slice_pos.size != self.slice_pos.size or grad_slice_pos.dtype != np.float32:
                 raise ValueError('grad_slice_pos must be float32 [%d]' % self.slice_pos.size)
+        if self.streamed and shifts is not None:
+            for a_, name in ((shifts, 'shifts'), (grad_shifts, 'grad_shifts')):
+                if a_ is not None and (a_.dtype != np.float32 or a_.size % 2):
+                    raise ValueError('%s must be float32 [n_entries, 2]' % name)
+            if grad_shifts is not None and grad_shifts.size != shifts.size:
+                raise ValueError('grad_shifts must have the shape of shifts')
+            if shift_index is None and shifts.size < 2 * B:
+                raise ValueError('shifts holds %d entries for %d positions and no shift_index' % (shifts.size // 2, B))
+            if shift_index is not None and (shift_index.dtype != np.int32 or shift_index.size != B):
+                raise ValueError('shift_index must be int32 [%d]' % B)
+            ps = (shifts, shift_index, grad_shifts)
         self._acc_done = False
         self._next_loss_buffer()
         if self.streamed and len(self.rounds(B)) > 1:
-            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos, xs)
+            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos, xs, ps)
             return
         args = lambda pr_, gp_: self._ms_args(pr_, gp_, want_grad, want_pred, grad_scale, 0, B, self._ws)      # (the whole batch)
         if probes_b is not None:
@@ -475,8 +502,8 @@ class MultisliceEngine(object):
             if tuple(probes_b.shape) != (B, self.n_probe_modes, Py, Px, 2):
                 raise ValueError('probes_b must be [%d, %d, %d, %d, 2], got %r' % (B, self.n_probe_modes, Py, Px, tuple(probes_b.shape)))
             check(lib.adm_multislice_fwd_adj_pp(*args(probes_b, None)))
-        elif shifts is None:
-            self._launch(args(probe, grad_probe), grad_slice_pos, xs)
+        elif shifts is None or ps is not None:
+            self._launch(args(probe, grad_probe), grad_slice_pos, xs, ps=ps)
         else:
             M = self.n_probe_modes
             if self._probes_b is None or self._probes_b.shape[0] < B:
@@ -503,14 +530,15 @@ class MultisliceEngine(object):
                 1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
                 self._pred.ptr + px if want_pred else None, self._loss.ptr + 4 * o, float(grad_scale), ws.ptr, ws.nbytes)
 
-    def _launch(self, args, grad_slice_pos=None, xs=None, o=0):
-        """``xs``: (exit_shifts, exit_shift_index, grad_exit_shifts) of the whole batch; the launch starts at its position ``o``."""
-        if xs is not None:
-            s, idx, g = xs
+    def _launch(self, args, grad_slice_pos=None, xs=None, o=0, ps=None):
+        """``xs``: (exit_shifts, exit_shift_index, grad_exit_shifts) of the whole batch, ``ps``: (shifts, shift_index, grad_shifts) of
+        a streamed engine with ``probe_shift``; the launch starts at position ``o`` of the batch."""
+        if xs is not None or ps is not None:
+            s, idx, g = xs if xs is not None else ps
+            fn = self.ctx.lib.adm_multislice_fwd_adj_exit_shift if xs is not None else self.ctx.lib.adm_multislice_fwd_adj_probe_shift
             # without an index, position b of the batch uses entry b: the round starting at o reads (and adds to) the entries from o on
             so = 0 if idx is not None else 8 * o
-            check(self.ctx.lib.adm_multislice_fwd_adj_exit_shift(*(args + (s.ptr + so, idx.ptr + 4 * o if idx is not None else None,
-                                                                         g.ptr + so if g is not None else None))))
+            check(fn(*(args + (s.ptr + so, idx.ptr + 4 * o if idx is not None else None, g.ptr + so if g is not None else None))))
         elif grad_slice_pos is not None:
             check(self.ctx.lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
         else:
@@ -528,15 +556,16 @@ class MultisliceEngine(object):
         for lo in range(0, n, self.MAX_COVER):
             check(lib.adm_tile_grad_accumulate_range(*(head + (lo, min(lo + self.MAX_COVER, n), 1 if add or lo else 0))))
 
-    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None, xs=None):
+    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None, xs=None, ps=None):
         """A streamed engine's batch that does not fit the workspace budget: one launch per round into the same workspace, each
         round's tile gradients overlap-added into grad_rot (zeroed first) before the next round overwrites them.  Losses,
         predictions and the probe gradient are those of one launch; the object gradient too, up to the order of the additions.
-        Every round adds its share to ``grad_slice_pos`` and to the gradient of the exit-wave shifts ``xs``."""
+        Every round adds its share to ``grad_slice_pos`` and to the gradient of the exit-wave shifts ``xs`` or the probe shifts
+        ``ps``."""
         if want_grad:
             check(self.ctx.lib.adm_memset(self.ctx.handle, self.grad_rot.ptr, 0, self.grad_rot.nbytes))
         for o, n in self.rounds(self._B):
-            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), grad_slice_pos, xs, o)
+            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), grad_slice_pos, xs, o, ps)
             if want_grad:
                 self._overlap_add(self._ws, o, n, 1, passes=self._check_cover(self._pos_host[o:o + n]) > self.MAX_COVER)
         # (every overlap-add above saw at most MAX_COVER tiles per pixel: nothing to check afterwards)

@@ -320,6 +320,8 @@ class _Run(object):
         self.comm = kwargs.pop('comm', None) or from_env()       # (the private keywords; the rest of kwargs goes to initialize_probe)
         self.return_state = kwargs.pop('return_state', False)
         self.fuse_per_angle = kwargs.pop('fuse_per_angle', True)
+        # sub-pixel probe positions on the streamed path (probes beyond 128 x 128): applied inside the sweep on request
+        self.streamed_probe_shift = bool(kwargs.pop('streamed_probe_shift', False))
         self.ops = kwargs.pop('ops', None)
         kwargs.pop('probe_size', None)
         self.kwargs = kwargs
@@ -518,11 +520,15 @@ class _Run(object):
                 # probes too large for one workgroup's LDS (beyond 128 x 128) take the streamed kernels; so does sparse multislice
                 # ... and per-angle projection alignment (the exit-wave shift is part of their detector step)
                 streamed='auto', slice_pos_cm=self.slice_pos_cm_ls if self.is_sparse_multislice else None,
-                exit_shift=bool(self.optimize_prj_pos_offset), **common)
+                exit_shift=bool(self.optimize_prj_pos_offset),
+                probe_shift=(self.streamed_probe_shift and not self.is_sparse_multislice and not self.optimize_prj_pos_offset), **common)
             # the rule of _shift_args (forward_model.py): sub-pixel shifts when the corrections are optimised or one exceeds 1e-3
-            _not_implemented(self.engine.streamed and (self.optimize_all_probe_pos or bool(np.any(self.probe_pos - self.probe_pos_int > 1e-3))),
-                             'sub-pixel probe positions (optimize_all_probe_pos or fractional probe_pos) with a %d x %d probe '
-                             '(streamed multislice)' % tuple(probe_size))
+            if self.engine.streamed and not self.engine.probe_shift \
+                    and (self.optimize_all_probe_pos or bool(np.any(self.probe_pos - self.probe_pos_int > 1e-3))):
+                raise NotImplementedError(
+                    'sub-pixel probe positions (optimize_all_probe_pos or fractional probe_pos) with a %d x %d probe (streamed multislice) '
+                    'is outside the accelerated path of adorym_amd (see DESIGN.md, out of scope).  The keyword '
+                    'streamed_probe_shift=True applies them inside the streamed sweep.' % tuple(probe_size))
         tables, theta_ls = {}, self.theta_ls
 
         def rotation_tables(i_theta):
@@ -1215,4 +1221,6 @@ class _Run(object):
                 'prj_pos_offset': np.asarray(_host(params['prj_pos_offset'])),
                 'prj_pos_offset_history': (None if self.prj_pos_offset_history is None
                                            else self.prj_pos_offset_history[0].get()[:self.prj_pos_offset_history[1]]),
-                'losses': self.loss_history, 'output_folder': self.output_folder}
+                'losses': self.loss_history, 'output_folder': self.output_folder,
+                # which multislice path served the run
+                'engine_streamed': bool(self.engine.streamed), 'engine_probe_shift': bool(self.engine.probe_shift)}

@@ -388,6 +388,29 @@ int adm_multislice_fwd_adj_exit_shift(adm_plan* plan, const float* obj_rot, cons
                                       float grad_scale, void* workspace, size_t workspace_bytes, const float* shifts,
                                       const int32_t* index, float* grad_shifts);
 
+/* ---- sub-pixel probe positions inside the sweep (streamed plans) -----------------------
+ * The model of adm_probe_shift below for probes that live in global memory: position b illuminates with
+ *   probe_b,m = IFFT2( Phi_b * FFT2(probe_m) ),  Phi_b[ky,kx] = exp(-2 PI i (fx s_x + fy s_y)),  f = fftfreq(n, 1),
+ * formed inside the launch (FFT2(probe_m) once, then one column launch over the batch; no probe set per position is kept).
+ * The phase argument is formed in fp64 and reduced to one turn (adm_probe_shift forms it in fp32).
+ * adm_plan_set_probe_shift(plan, 1) switches a STREAMED plan to it (plans of adm_plan_create: ADM_ERR_UNSUPPORTED; so are plans
+ * with slice positions, with exit-wave shifts or with several detector kernels, and those setters refuse a plan with this
+ * switch).  Call it before the workspace is sized: adm_plan_workspace_bytes grows by the spectra [M][Py][Px] and the gradient
+ * partials.  A plan without the switch reports the sizes it always did, and adm_multislice_fwd_adj on a switched plan is the
+ * unshifted launch.
+ * adm_multislice_fwd_adj_probe_shift takes the arguments of adm_multislice_fwd_adj and
+ *   shifts       device float [n_entries][2] = (s_y, s_x) in pixels
+ *   index        device int32 [batch]: position b uses entry index[b]; NULL = entry b
+ *   grad_shifts  device float [n_entries][2], dL/ds ACCUMULATED into it (want_grad = 1), or NULL
+ * grad_probe is ACCUMULATED, taken through the shift (sum_b shift_{-s_b} of the per-position gradients).  On a plan without the
+ * switch: ADM_ERR_INVALID.  The terms of every entry are summed in fp64 in a fixed order (no atomics): two calls give the same
+ * bits.  adm_probe_shift, adm_probe_shift_adj and adm_multislice_fwd_adj_pp keep refusing streamed plans. */
+int adm_plan_set_probe_shift(adm_plan* plan, int on);
+int adm_multislice_fwd_adj_probe_shift(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
+                                       const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
+                                       float grad_scale, void* workspace, size_t workspace_bytes, const float* shifts,
+                                       const int32_t* index, float* grad_shifts);
+
 /* ---- f2  sub-pixel probe positions -----------------------------------------------------
  * realign_image_fourier (adorym/util.py:380-397) applied to every probe mode for every position of a minibatch:
  *   probes_out[b][m] = IFFT2( exp(-2 PI i (fx*sx_b + fy*sy_b)) * FFT2(probe[m]) ),  PI = 3.14159265359, f = fftfreq.
