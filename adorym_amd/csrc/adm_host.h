@@ -138,7 +138,6 @@ struct StExitShiftLaunch {
 // the detector step's column launch: hs = H_free / (Py*Px), or nullptr for H = 1
 hipError_t ms_exitshift_col_launch(const MsParams& p, int batch, float2* fld, const float2* hs, bool conj, const StExitShiftLaunch& xs,
                                    hipStream_t st);
-hipError_t ms_exitshift_reduce_launch(const MsParams& p, int batch, const StExitShiftLaunch& xs, hipStream_t st);
 // sub-pixel probe positions on streamed plans (adm_plan_set_probe_shift, adm_ms_probeshift.hip): the probe modes Fourier-shifted
 // by an offset per position inside the sweep
 struct StProbeShift {          // kernel argument
@@ -154,7 +153,6 @@ struct StProbeShiftLaunch {
 };
 hipError_t ms_probeshift_spectrum_launch(const MsParams& p, float2* phat, hipStream_t st);
 hipError_t ms_probeshift_col_launch(const MsParams& p, int batch, float2* fld, bool conj, const StProbeShift& q, hipStream_t st);
-hipError_t ms_probeshift_reduce_launch(const MsParams& p, int batch, const StProbeShift& q, float* grad_shifts, hipStream_t st);
 // the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials;
 // sp: the tables of a sparse plan, or nullptr; xs: the exit-wave shifts of a plan with adm_plan_set_exit_shift, or nullptr; ps:
 // the probe shifts of a plan with adm_plan_set_probe_shift, or nullptr

@@ -29,12 +29,11 @@
 // Row launches: one workgroup per (position, group of whole rows), all modes in turn (the slice factors are loaded once and the
 // tile gradient of the modes is summed in registers).  Column launches: one workgroup per (position, mode, 8 adjacent columns;
 // 4 beyond Py = 1024): every row of the group is a 64-byte (32-byte) run.  Workspace rows (stash, tile gradients) are pixel-major [Py][Px] like the generic
-// kernel's, so the cover lists and the overlap-add (TileGeom::pixel_major) serve both.
+// kernel's, so the cover lists and the overlap-add (TileGeom::pixel_major) serve both.  What a column workgroup is made of (st_cw,
+// its threads and LDS, the load / store / transform helpers) is in adm_ms_col.h, shared with the two shift files.
 #include <hip/hip_runtime.h>
 #include "adm_host.h"
-#include "adm_fft.h"
-#include "adm_ms_math.h"
-#include "adm_ms_gen.h"
+#include "adm_ms_col.h"
 
 namespace adm {
 
@@ -43,19 +42,11 @@ constexpr int ST_ROW_E = 8;                    // elements per thread in a row w
 constexpr int ST_ROW_ELEMS = ST_ROW_NT * ST_ROW_E;   // whole rows, at most this many elements (one row of 2048 at the largest)
 constexpr int ST_MAX_SIDE = 2048;
 constexpr int ST_MAX_SLICES = 1024;         // most slices of a sparse plan (st_sparse_reduce_kernel keeps one sum per gap in LDS)
-constexpr int ST_COL_NT = 512;                 // most threads of a column workgroup (GEN_E elements each)
-// adjacent columns of a column workgroup: 8 (64-byte runs per row) up to Py = 1024, 4 at larger Py (the group is at most
-// ST_COL_NT * GEN_E elements: with more threads the detector kernel's per-element state no longer fits the registers)
-__host__ __device__ __forceinline__ int st_cw(int py) { return py <= ST_COL_NT * GEN_E / 8 ? 8 : 4; }
 
 // row transform passes of the line group in LDS (INV: conjugate twiddles)
 template <bool INV, int E> __device__ __forceinline__ void st_row_fft(const GenCtx& g, const MsParams& p, cf (&v)[E]) {
     int Ns = 1;
     for (int s = 0; s < p.gen_nrx; ++s) { gen_pass<false, INV, E>(g, p.gen_rx[s], Ns, v); Ns *= p.gen_rx[s]; }
-}
-template <bool INV> __device__ __forceinline__ void st_col_fft(const GenCtx& g, const MsParams& p, cf (&v)[GEN_E]) {
-    int Ns = 1;
-    for (int s = 0; s < p.gen_nry; ++s) { gen_pass<true, INV>(g, p.gen_ry[s], Ns, v); Ns *= p.gen_ry[s]; }
 }
 // dir: 0 none, 1 forward, 2 inverse
 template <int E> __device__ __forceinline__ void st_row_dir(const GenCtx& g, const MsParams& p, int dir, cf (&v)[E]) {
@@ -151,29 +142,6 @@ __global__ __launch_bounds__(ST_ROW_NT) void st_row_kernel(MsParams p, StRow r, 
             const int i = g.tid + j * g.nt;
             if (j < g.ne && i < g.n) gtile[i] = gacc[j];
         }
-    }
-}
-
-// LDS of a column workgroup: the [Py][cw] group, then W_Py^j
-__device__ __forceinline__ void st_col_ctx(GenCtx& g, cf* lds, const MsParams& p, int c0, int cw) {
-    g.Py = p.gen_py; g.Px = min(cw, p.gen_px - c0); g.n = g.Py * g.Px;
-    g.tid = threadIdx.x; g.nt = blockDim.x;
-    g.ne = (g.n + g.nt - 1) / g.nt;
-    g.fld = lds;
-    cf* twy = lds + (size_t)g.Py * cw;
-    for (int i = g.tid; i < g.Py; i += g.nt) twy[i] = p.gen_twid_y[i];
-    g.twx = nullptr; g.twy = twy;
-}
-__device__ __forceinline__ void st_col_load(const GenCtx& g, const float2* f, int Px, int c0) {
-    for (int i = g.tid; i < g.n; i += g.nt) {
-        const int y = i / g.Px;
-        g.fld[i] = f[(size_t)y * Px + c0 + (i - y * g.Px)];
-    }
-}
-__device__ __forceinline__ void st_col_store(const GenCtx& g, float2* f, int Px, int c0) {
-    for (int i = g.tid; i < g.n; i += g.nt) {
-        const int y = i / g.Px;
-        f[(size_t)y * Px + c0 + (i - y * g.Px)] = g.fld[i];
     }
 }
 
@@ -292,9 +260,6 @@ __global__ __launch_bounds__(ST_COL_NT) void st_det_kernel(MsParams p, float2* _
 // over its elements (products in fp32, sums in fp64), ONE partial per workgroup; st_sparse_reduce_kernel adds the partials of a
 // step in a fixed order and accumulates dL/dz_j = 1e7 (dL/dd_{j-1} - dL/dd_j) into the caller's buffer.  No atomics.
 
-// fftfreq(n)[i] * n
-__device__ __forceinline__ int st_freq_index(int i, int n) { return i <= (n - 1) / 2 ? i : i - n; }
-
 // hs[s][y][x] = exp(i a_yx d_s) / (Py*Px): the phase (hundreds of radians at 10 um gaps) in fp64, reduced to one turn, then
 // sin / cos in fp32 and one rounding for the division.  ay[y] + ax[x] = a_yx for the gradient kernel (fp32).
 __global__ __launch_bounds__(256) void st_sparse_table_kernel(StSparseGeom q, const float* __restrict__ z, float2* __restrict__ hs,
@@ -341,7 +306,7 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_sp
     __syncthreads();
     cf v[GEN_E];
     st_col_fft<false>(g, p, v);
-    double acc = 0.0;
+    double acc[1] = {0.0};
 #pragma unroll
     for (int j = 0; j < GEN_E; ++j) {
         const int i = g.tid + j * g.nt;
@@ -351,7 +316,7 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_sp
             const cf a = g.fld[i];
             if (CONJ) {
                 const cf w = keep[k];
-                acc += (double)((q.ay[y] + q.ax[x]) * (a.x * w.y - a.y * w.x));
+                acc[0] += (double)((q.ay[y] + q.ax[x]) * (a.x * w.y - a.y * w.x));
                 g.fld[i] = cmulc(a, hs[k]);
             } else {
                 const cf w = cmul(a, hs[k]);
@@ -360,17 +325,8 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_sp
             }
         }
     }
-    if (CONJ) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-        if ((g.tid & 63) == 0) redd[g.tid >> 6] = acc;
-    }
-    __syncthreads();
-    if (CONJ && g.tid == 0) {
-        double s = 0.0;
-        for (int w = 0; w < (g.nt >> 6); ++w) s += redd[w];
-        q.part[(size_t)q.step * gridDim.x + blockIdx.x] = -s;
-    }
+    st_block_sum_f64(acc, redd, g.tid, g.nt, CONJ);
+    if (CONJ && g.tid == 0) q.part[(size_t)q.step * gridDim.x + blockIdx.x] = -acc[0];
     st_col_fft<true>(g, p, v);
     st_col_store(g, f, Px, c0);
 }
@@ -398,6 +354,43 @@ __global__ __launch_bounds__(256) void st_sparse_reduce_kernel(const double* __r
     }
 }
 
+// The dL/ds partials of the shift kernels (adm_ms_exitshift.hip, adm_ms_probeshift.hip; [B*M*column groups][2], index: the entry of
+// position b, or nullptr: b):
+// grad_shifts[e] += 2 PI * (the partials of every position that uses entry e: ascending position, then mode, then column group).
+// One workgroup per position; the first position of an entry gathers for it, the others leave.  per = n_modes * column groups.
+__global__ __launch_bounds__(256) void st_shift_reduce_kernel(const double* __restrict__ part, int batch, int per,
+                                                              const int* __restrict__ index, float* grad_shifts) {
+    __shared__ double red[2 * 256];
+    __shared__ int later;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int e = index ? index[b] : b;
+    if (t == 0) later = 0;
+    __syncthreads();
+    if (index) {
+        int seen = 0;
+        for (int c = t; c < b; c += 256) seen |= (index[c] == e);
+        if (seen) later = 1;           // (every writer stores the same value)
+    }
+    __syncthreads();
+    if (later) return;
+    double ay = 0.0, ax = 0.0;
+    for (int c = b; c < batch; ++c) {
+        if (c != b && (!index || index[c] != e)) continue;
+        const double* pc = part + 2 * (size_t)c * per;
+        for (int i = t; i < per; i += 256) { ay += pc[2 * i]; ax += pc[2 * i + 1]; }
+    }
+    red[2 * t] = ay; red[2 * t + 1] = ax;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) { red[2 * t] += red[2 * (t + h)]; red[2 * t + 1] += red[2 * (t + h) + 1]; }
+        __syncthreads();
+    }
+    if (t < 2) {
+        const double two_pi = 2.0 * 3.14159265359;
+        grad_shifts[2 * (size_t)e + t] += (float)(two_pi * red[t]);
+    }
+}
+
 // loss_sum[b] = the column-group partials of position b, ascending (loss_sum may be host-mapped memory)
 __global__ __launch_bounds__(256) void st_loss_reduce_kernel(const float* __restrict__ part, int ncg, int batch, float* loss_sum) {
     const int b = blockIdx.x * 256 + threadIdx.x;
@@ -408,13 +401,7 @@ __global__ __launch_bounds__(256) void st_loss_reduce_kernel(const float* __rest
 }
 
 bool ms_streamed_supported(int py, int px) { return py >= 1 && px >= 1 && py <= ST_MAX_SIDE && px <= ST_MAX_SIDE; }
-int ms_streamed_col_groups(int py, int px) { return (px + st_cw(py) - 1) / st_cw(py); }
-static int st_col_threads(int py) {
-    const int n = py * st_cw(py);
-    int nt = ((n + GEN_E - 1) / GEN_E + 63) / 64 * 64;
-    if (nt < 256) nt = 256;
-    return nt;
-}
+int ms_streamed_col_groups(int py, int px) { return st_col_geom(py, px).ncg; }
 
 hipError_t ms_sparse_table_launch(const StSparseGeom& q, const float* z, float2* hs, float* ay, float* ax, hipStream_t st) {
     size_t n = (size_t)(q.n_slices - 1) * q.py * q.px;
@@ -441,17 +428,16 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
     int rows = ST_ROW_ELEMS / Px;
     if (rows < 1) rows = 1;
     if (rows > Py) rows = Py;
-    const int ngr = (Py + rows - 1) / rows, ncg = ms_streamed_col_groups(Py, Px);
-    const int cnt = st_col_threads(Py);
-    const size_t clds = ((size_t)Py * st_cw(Py) + Py) * sizeof(float2);
+    const StColGeom cg = st_col_geom(Py, Px);
+    const int ngr = (Py + rows - 1) / rows, ncg = cg.ncg, cnt = cg.threads;
+    const size_t clds = cg.lds;
     static bool attr_set = false;
     if (!attr_set) {
-        const int lim = 160 * 1024 - 256;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_det_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_sparse_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(st_col_conv_sparse_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+        hipError_t e = st_col_raise_lds(st_col_conv_kernel<false>);
+        if (e == hipSuccess) e = st_col_raise_lds(st_col_conv_kernel<true>);
+        if (e == hipSuccess) e = st_col_raise_lds(st_det_kernel);
+        if (e == hipSuccess) e = st_col_raise_lds(st_col_conv_sparse_kernel<false>);
+        if (e == hipSuccess) e = st_col_raise_lds(st_col_conv_sparse_kernel<true>);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
@@ -506,7 +492,7 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
     }
     if (e != hipSuccess) return e;
     // ---------------- detector, loss ----------------
-    hipLaunchKernelGGL(st_det_kernel, dim3(batch * ncg), dim3(cnt), clds + (size_t)Py * st_cw(Py) * sizeof(float), st, p, fld, part);
+    hipLaunchKernelGGL(st_det_kernel, dim3(batch * ncg), dim3(cnt), clds + (size_t)Py * cg.cw * sizeof(float), st, p, fld, part);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(st_loss_reduce_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, part, ncg, batch, p.loss_sum);
     if ((e = hipGetLastError()) != hipSuccess || !p.want_grad) return e;
@@ -527,14 +513,18 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         e = ms_probeshift_col_launch(p, batch, fld, true, pq, st);
         if (e == hipSuccess && p.grad_probe) e = row(0, 0, 2, 0, 0, 1);
         if (e == hipSuccess && ps->grad_shifts) {
-            e = ms_probeshift_reduce_launch(p, batch, pq, ps->grad_shifts, st);
+            hipLaunchKernelGGL(st_shift_reduce_kernel, dim3(batch), dim3(256), 0, st, ps->part, batch, M * ncg, ps->index, ps->grad_shifts);
+            e = hipGetLastError();
         }
     }
     if (e == hipSuccess && zgrad) {
         hipLaunchKernelGGL(st_sparse_reduce_kernel, dim3(1), dim3(256), 0, st, sp->part, batch * M * ncg, S - 1, sp->grad_z);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && xs && xs->grad_shifts) e = ms_exitshift_reduce_launch(p, batch, *xs, st);
+    if (e == hipSuccess && xs && xs->grad_shifts) {
+        hipLaunchKernelGGL(st_shift_reduce_kernel, dim3(batch), dim3(256), 0, st, xs->part, batch, M * ncg, xs->index, xs->grad_shifts);
+        e = hipGetLastError();
+    }
     return e;
 }
 

@@ -1,7 +1,8 @@
 """The launch geometries of the streamed multislice path (adm_ms_streamed.hip) and the fields that reach each of them (test
 infrastructure only).
 
-``geometry`` mirrors the launch arithmetic of ms_streamed_launch (rows per row workgroup, st_cw, st_col_threads) and factor()
+``geometry`` mirrors the launch arithmetic of ms_streamed_launch (rows per row workgroup) and adm_ms_col.h (st_cw, st_col_threads,
+st_col_geom) and factor()
 of adm_api.hip; ``classes`` names what a field exercises of it: how the rows fall into row workgroups, which column workgroup
 runs, what radix passes its two axes take.  ``SHAPES`` is swept against the fp64 oracle by tests/test_gpu_streamed_matrix.py,
 ``SEQUENCES`` (the launch-sequence variants of ms_streamed_launch) at one field of each of the column classes beyond 256 threads.
@@ -10,7 +11,7 @@ without the tables here following.
 """
 from tests import ms_matrix as MM
 
-# adm_ms_streamed.hip, adm_ms_gen.h, factor() of adm_api.hip (compared with the source by the coverage test)
+# adm_ms_streamed.hip, adm_ms_col.h, adm_ms_gen.h, factor() of adm_api.hip (compared with the source by the coverage test)
 ST_ROW_NT, ST_ROW_E = 256, 8
 ST_ROW_ELEMS = ST_ROW_NT * ST_ROW_E
 ST_COL_NT = 512
@@ -249,4 +250,5 @@ KERNELS = {
     'st_col_conv_sparse_kernel<true>': (_M, ('test_sparse_vs_restatement',)),
     'st_sparse_reduce_kernel': (_M, ('test_sparse_vs_restatement',)),
     'st_sparse_anchor_kernel': (_M, ('test_most_slice_positions',)),
+    'st_shift_reduce_kernel': ('test_gpu_prj_offset', ('test_kernels_vs_reference', 'test_geometries_vs_restatement')),
 }

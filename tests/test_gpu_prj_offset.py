@@ -130,7 +130,7 @@ def fixture_case(F, name):
 
 @pytest.mark.parametrize('name', FIXTURE_CASES)
 def test_kernels_vs_reference(A, ctx, F, name):
-    """es_col_conv_kernel<false>, es_col_conv_kernel<true>, es_reduce_kernel: prediction, loss, object gradient, probe gradient and
+    """es_col_conv_kernel<false>, es_col_conv_kernel<true>, st_shift_reduce_kernel: prediction, loss, object gradient, probe gradient and
     dL/ds against the reference's fp64 run, the reference's own fp32 run as the yardstick."""
     case = fixture_case(F, name)
     res = run_shifted(A, ctx, case, canaries=True)
@@ -194,7 +194,7 @@ GEOMETRIES = {
 @pytest.mark.parametrize('shared', [False, True], ids=['index_null', 'shared_entries'])
 @pytest.mark.parametrize('name', list(GEOMETRIES))
 def test_geometries_vs_restatement(A, ctx, name, shared):
-    """es_col_conv_kernel<false>, es_col_conv_kernel<true>, es_reduce_kernel at every column-launch geometry; S = 2, B = 5."""
+    """es_col_conv_kernel<false>, es_col_conv_kernel<true>, st_shift_reduce_kernel at every column-launch geometry; S = 2, B = 5."""
     kw = dict(GEOMETRIES[name])
     case = make_case(kw.pop('P'), shared=shared, **kw)
     r64, e32 = yardstick(case)

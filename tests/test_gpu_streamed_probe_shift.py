@@ -1,5 +1,5 @@
 """Sub-pixel probe positions on the streamed multislice path (adm_plan_set_probe_shift, adm_multislice_fwd_adj_probe_shift;
-ps_colfft_kernel, ps_col_kernel<false / true>, ps_reduce_kernel of adm_ms_probeshift.hip) through the engine (pytest -m gpu).
+ps_colfft_kernel, ps_col_kernel<false / true> of adm_ms_probeshift.hip, st_shift_reduce_kernel) through the engine (pytest -m gpu).
 
 The checker is tests/ms_matrix.py's ``oracle_case(P, pp='shifts')``: shifts of up to +-2.5 px, some entries used by several
 positions, the oracle in fp64 with its own fp32 run as the yardstick.  The bars are ``MM.GENERIC``; the shift gradient must
@@ -141,7 +141,7 @@ GEOMETRY_CASES = {
 
 @pytest.mark.parametrize('name', list(GEOMETRY_CASES))
 def test_geometries_vs_oracle(A, ctx, name):
-    """ps_colfft_kernel, ps_col_kernel<false>, ps_col_kernel<true>, ps_reduce_kernel and the row launches around them at every
+    """ps_colfft_kernel, ps_col_kernel<false>, ps_col_kernel<true>, st_shift_reduce_kernel and the row launches around them at every
     launch geometry (row groups clipped to Py, whole and ragged rows, column groups of 8 and of 4 with a short last group, 256
     to 512 threads) with shifted probes, S = 2, B = 6, far field."""
     kw = dict(GEOMETRY_CASES[name])

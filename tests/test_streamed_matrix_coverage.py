@@ -1,7 +1,8 @@
 """The streamed-path sweep (tests/test_gpu_streamed_matrix.py) covers what adm_ms_streamed.hip launches: tests/st_matrix.py
-mirrors its launch arithmetic, and this CPU test parses the source -- the constants, st_cw, st_col_threads, the row-group rule of
-ms_streamed_launch, GEN_E, factor()'s radix list and the __global__ kernels -- so that a change there fails here until the
-tables follow.  It also asserts that the tables reach every class of geometry they name."""
+mirrors its launch arithmetic, and this CPU test parses the source -- the constants, st_cw, st_col_threads and the column-launch
+geometry of adm_ms_col.h, the row-group rule of ms_streamed_launch, GEN_E, factor()'s radix list and the __global__ kernels -- so
+that a change there fails here until the tables follow.  It also asserts that the tables reach every class of geometry they name
+and that the column helpers which the translation units of the path share are defined once."""
 import os
 import re
 
@@ -52,11 +53,12 @@ def c_int_function(body, consts):
 
 
 def parsed():
-    st, gen, api = _read('adm_ms_streamed.hip'), _read('adm_ms_gen.h'), _read('adm_api.hip')
-    c = constants(st, ['ST_ROW_NT', 'ST_ROW_E', 'ST_ROW_ELEMS', 'ST_MAX_SIDE', 'ST_MAX_SLICES', 'ST_COL_NT'])
+    st, col, gen, api = _read('adm_ms_streamed.hip'), _read('adm_ms_col.h'), _read('adm_ms_gen.h'), _read('adm_api.hip')
+    c = constants(st, ['ST_ROW_NT', 'ST_ROW_E', 'ST_ROW_ELEMS', 'ST_MAX_SIDE', 'ST_MAX_SLICES'])
+    c.update(constants(col, ['ST_COL_NT']))
     c.update(constants(gen, ['GEN_E']))
-    cw = c_int_function(_function_body(st, r'int\s+st_cw\s*\(\s*int\s+py\s*\)'), c)
-    nt = c_int_function(_function_body(st, r'static\s+int\s+st_col_threads\s*\(\s*int\s+py\s*\)'), dict(c, st_cw=cw))
+    cw = c_int_function(_function_body(col, r'int\s+st_cw\s*\(\s*int\s+py\s*\)'), c)
+    nt = c_int_function(_function_body(col, r'inline\s+int\s+st_col_threads\s*\(\s*int\s+py\s*\)'), dict(c, st_cw=cw))
     m = re.search(r'const\s+int\s+pref\[\]\s*=\s*\{([^}]*)\}', api)
     assert m, 'pref[] of factor()'
     pref = tuple(int(v) for v in m.group(1).split(','))
@@ -94,9 +96,15 @@ def test_the_mirror_follows_the_row_groups_of_the_launch():
     st = parsed()[0]
     body = _function_body(st, r'hipError_t\s+ms_streamed_launch\s*\(')
     assert re.search(r'int rows = ST_ROW_ELEMS / Px;\s*if \(rows < 1\) rows = 1;\s*if \(rows > Py\) rows = Py;', body)
-    assert re.search(r'const int ngr = \(Py \+ rows - 1\) / rows, ncg = ms_streamed_col_groups\(Py, Px\);', body)
-    assert 'int ms_streamed_col_groups(int py, int px) { return (px + st_cw(py) - 1) / st_cw(py); }' in st
-    assert 'const size_t clds = ((size_t)Py * st_cw(Py) + Py) * sizeof(float2);' in body
+    # the column launches: the one geometry function of adm_ms_col.h; the detector kernel's float plane on top of its LDS bytes
+    assert 'const StColGeom cg = st_col_geom(Py, Px);' in body
+    assert 'const int ngr = (Py + rows - 1) / rows, ncg = cg.ncg, cnt = cg.threads;' in body and 'const size_t clds = cg.lds;' in body
+    assert 'int ms_streamed_col_groups(int py, int px) { return st_col_geom(py, px).ncg; }' in st
+    assert 'dim3(batch * ncg), dim3(cnt), clds + (size_t)Py * cg.cw * sizeof(float), st, p, fld, part);' in body
+    geom = _function_body(_read('adm_ms_col.h'), r'inline\s+StColGeom\s+st_col_geom\s*\(\s*int\s+Py\s*,\s*int\s+Px\s*\)')
+    for line in ('const int cw = st_cw(Py);', 'c.cw = cw; c.ncg = (Px + cw - 1) / cw; c.threads = st_col_threads(Py);',
+                 'c.lds = ((size_t)Py * cw + Py) * sizeof(float2);'):
+        assert line in geom, line
     g = SM.geometry(2048, 2048)
     assert (g['rows'], g['n_row_groups'], g['row_ne'], g['cw'], g['col_threads'], g['n_col_groups'], g['col_ne']) == (1, 2048, 8, 4, 512, 512, 16)
     g = SM.geometry(2048, 5)
@@ -161,7 +169,7 @@ def test_the_matrix_names_exactly_the_kernels_of_the_source():
     for m in re.finditer(r'(template\s*<\s*bool\s+\w+\s*>\s*)?__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(\w+)\s*\(', st):
         name = m.group(2)
         found |= {name + '<false>', name + '<true>'} if m.group(1) else {name}
-    assert len(re.findall(r'__global__', st)) == 8 and len(found) == 10, sorted(found)
+    assert len(re.findall(r'__global__', st)) == 9 and len(found) == 11, sorted(found)
     assert found == set(SM.KERNELS), found ^ set(SM.KERNELS)
     for k, (module, tests) in SM.KERNELS.items():
         with open(os.path.join(ROOT, 'tests', module + '.py')) as f:
@@ -171,6 +179,28 @@ def test_the_matrix_names_exactly_the_kernels_of_the_source():
     # every instantiation of the templates is launched
     for name in ('st_col_conv_kernel', 'st_col_conv_sparse_kernel'):
         assert {v for v in re.findall(r'hipLaunchKernelGGL\(%s<(\w+)>' % name, st)} == {'true', 'false'}, name
+
+
+def test_the_column_helpers_are_defined_once():
+    """What the translation units of the path share is defined exactly once under adorym_amd/csrc, in adm_ms_col.h, and no copy
+    under the prefix of a translation unit exists."""
+    names = ('st_cw', 'st_col_threads', 'st_col_fft', 'st_col_ctx', 'st_col_load', 'st_col_store', 'st_freq_index', 'st_freq',
+             'st_col_geom', 'st_col_raise_lds', 'st_block_sum_f64')
+    srcs = {f: _read(f) for f in sorted(os.listdir(CSRC)) if f.endswith(('.hip', '.h'))}
+    path = ('adm_ms_col.h', 'adm_ms_streamed.hip', 'adm_ms_exitshift.hip', 'adm_ms_probeshift.hip')
+    # a definition: the name, its parameter list, its body (a call is followed by ';', an operator or ')')
+    definition = r'\b%s\s*\([^;{}()]*(?:\([^;{}()]*\)[^;{}()]*)*\)\s*\{'
+    where = lambda text, files: [f for f in files for _ in re.finditer(text, srcs[f])]
+    for n in names:
+        assert where(definition % n, srcs) == ['adm_ms_col.h'], n
+        assert not where(definition % ('es_' + n[3:]), srcs) + where(definition % ('ps_' + n[3:]), srcs), n
+    # the constant, the LDS bytes (in no other spelling either), the dynamic-LDS limit and the attribute call
+    for text, files in ((r'constexpr\s+int\s+ST_COL_NT\b', srcs), (re.escape('((size_t)Py * cw + Py) * sizeof(float2)'), srcs),
+                        (r'sizeof\(float2\)', path), (re.escape('160 * 1024 - 256'), path), ('hipFuncAttributeMaxDynamicSharedMemorySize', path)):
+        assert where(text, files) == ['adm_ms_col.h'], text
+    assert not where(r'constexpr\s+int\s+(ES|PS)_COL_NT\b', srcs)
+    assert all('#include "adm_ms_col.h"' in srcs[f] for f in path[1:])
+    assert "'adm_ms_col.h'" in re.search(r'^HDRS = \[.*\]$', _read('build.py'), re.M).group(0)
 
 
 @pytest.mark.parametrize('shape', list(SM.SHAPES))
