@@ -477,6 +477,48 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     w.total = at;
     return w;
 }
+
+// out[i] += sum_b part[b][i], b ascending: the per-position probe gradients of a launch, summed deterministically
+__global__ __launch_bounds__(256) void probe_grad_reduce_kernel(const float2* __restrict__ part, int batch, size_t stride, size_t n,
+                                                                float2* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float2 acc = out[i];
+    for (int b = 0; b < batch; ++b) {
+        const float2 v = part[(size_t)b * stride + i];
+        acc.x += v.x;
+        acc.y += v.y;
+    }
+    out[i] = acc;
+}
+// Large batches (a dense 2-D scan taken as one minibatch: 2704 positions): one thread per element walking the whole batch is a
+// chain of `batch` dependent adds on 21 workgroups.  Two levels instead: chunk c of PGR_CHUNK slots is summed in slot order into
+// its first slot (every thread touches element i of every slot only: in place), then the chunk sums are added in chunk order.
+// A fixed order either way: bit-reproducible.
+#define PGR_CHUNK 32
+__global__ __launch_bounds__(256) void probe_grad_reduce_chunks_kernel(float2* __restrict__ part, int batch, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int b0 = blockIdx.y * PGR_CHUNK, b1 = min(b0 + PGR_CHUNK, batch);
+    float2 acc = part[(size_t)b0 * n + i];
+    for (int b = b0 + 1; b < b1; ++b) {
+        const float2 v = part[(size_t)b * n + i];
+        acc.x += v.x;
+        acc.y += v.y;
+    }
+    part[(size_t)b0 * n + i] = acc;
+}
+hipError_t probe_grad_reduce_large(float2* part, int batch, size_t n, float2* out, hipStream_t st) {
+    const int chunks = (batch + PGR_CHUNK - 1) / PGR_CHUNK;
+    hipLaunchKernelGGL(probe_grad_reduce_chunks_kernel, dim3((unsigned)((n + 255) / 256), chunks), dim3(256), 0, st, part, batch, n);
+    // the chunk sums sit PGR_CHUNK slots apart
+    hipLaunchKernelGGL(probe_grad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float2*)part, chunks, (size_t)PGR_CHUNK * n, n, out);
+    return hipGetLastError();
+}
+hipError_t probe_grad_reduce(const float2* part, int batch, size_t n, float2* out, hipStream_t st) {
+    hipLaunchKernelGGL(probe_grad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, batch, n, n, out);
+    return hipGetLastError();
+}
 }  // namespace adm
 
 extern "C" int adm_plan_set_slice_positions(adm_plan* plan, const float* z_cm_dev, int n, double lambda_nm, double voxel_nm_y,

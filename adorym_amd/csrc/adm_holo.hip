@@ -42,11 +42,6 @@ struct adm_holo {
 
 namespace adm {
 
-static inline int grid_for(size_t n) {
-    size_t b = (n + 255) / 256;
-    return (int)(b > 4096 ? 4096 : (b ? b : 1));
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // batched row FFT with transposed store
 // ---------------------------------------------------------------------------------------------------------------

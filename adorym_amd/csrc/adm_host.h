@@ -8,7 +8,7 @@
 #include "../../include/adm.h"
 #include "adm_common.h"
 
-#define ADM_MAXCOVER 64    // cover-list entries per rotated-frame pixel (adm_object.hip: cover_build_kernel)
+#define ADM_MAXCOVER 64    // cover-list entries per rotated-frame pixel (adm_overlap_add.hip: cover_build_kernel)
 
 struct adm_ctx {
     int device;
@@ -159,6 +159,10 @@ hipError_t ms_probeshift_col_launch(const MsParams& p, int batch, float2* fld, b
 hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp = nullptr,
                               const StExitShiftLaunch* xs = nullptr, const StProbeShiftLaunch* ps = nullptr);
 hipError_t shift_launch(int n, const ShiftParams& q, int batch, bool adjoint, hipStream_t st);
+inline int stream_grid(size_t n) {      // blocks of 256 threads for a grid-stride pass over n elements
+    size_t b = (n + 255) / 256;
+    return (int)(b > 4096 ? 4096 : (b ? b : 1));
+}
 }  // namespace adm
 
 #define ADM_HIP(call)                                          \

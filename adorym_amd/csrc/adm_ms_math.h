@@ -83,7 +83,7 @@ template <int R, int KS> __device__ __forceinline__ void st_line(const cf (&a)[R
 // of a modulation step.  R1 even: the elements of a thread are stored in pairs, [k/2][tid][2], so that ONE 16-byte access
 // per lane moves two of them -- the CU issues vector-memory instructions at a fixed cost per wave-instruction (~40
 // cycles each when the 11 waves issue together, tools/stamps.py), so halving their number halves that phase.
-// R1 odd: [k][tid].  tile_accumulate (adm_object.hip) addresses the tile gradients with ws_elem_offset().
+// R1 odd: [k][tid].  tile_accumulate (adm_overlap_add.hip) addresses the tile gradients with ws_elem_offset().
 __host__ __device__ __forceinline__ unsigned ws_elem_offset(int R1, int NT, int k, int tid) {
     return (R1 % 2 == 0) ? (unsigned)(((k >> 1) * NT + tid) * 2 + (k & 1)) : (unsigned)(k * NT + tid);
 }

@@ -1,5 +1,5 @@
 // Element-wise optimiser arithmetic shared by the kernels that apply it: adam_kernel / small_adam_kernel / gd_kernel /
-// momentum_kernel (adm_object.hip: one rank, or the owned shard after an RCCL reduce-scatter) and the peer-to-peer fused
+// momentum_kernel (adm_optimize.hip: one rank, or the owned shard after an RCCL reduce-scatter) and the peer-to-peer fused
 // exchange (adm_p2p.hip: sum over the ranks' gradient buffers + the same step + write to every replica).  One definition,
 // contraction off, so that every caller produces the same bits.
 //   AdamOptimizer.apply_gradient      adorym/optimizers.py:309-318

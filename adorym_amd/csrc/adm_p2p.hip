@@ -185,11 +185,6 @@ __global__ __launch_bounds__(256) void p2p_sum_kernel(MailTable t, int R, float*
     }
 }
 
-int stream_grid(size_t n) {
-    const size_t b = (n + 255) / 256;
-    return (int)(b > 4096 ? 4096 : (b ? b : 1));
-}
-
 // everything this rank has queued so far becomes visible at system scope, then every peer's flag `slot` of this rank is raised
 int signal(adm_ctx* ctx, P2P* p, int slot) {
     ADM_HIP(hipEventRecord(p->fence, ctx->stream));
@@ -214,6 +209,7 @@ int need(adm_ctx* ctx, const char* what, bool connected) {
 }  // namespace
 
 using adm::fail;
+using adm::stream_grid;
 
 extern "C" int adm_p2p_create(adm_ctx* ctx, int rank, int nranks, size_t mailbox_bytes) {
     if (!ctx) return fail(ADM_ERR_INVALID, "adm_p2p_create: null context");

@@ -1,0 +1,667 @@
+// Rotation about axis 0 (R2): gather, adjoint (atomic, CSR gather, LDS-staged), stacked forms, the slice-transmission cache.
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include "adm_host.h"
+#include "adm_ms_math.h"
+
+namespace adm {
+// --------------------------------------------------------------------------------------------
+// Rotation about axis 0.  Reference: apply_rotation -> w.grid_sample (adorym/util.py:536-552,
+// adorym/wrappers.py:1105-1147), torch grid_sampler bilinear / border / align_corners=False.
+// One thread owns one rotated-frame (x', z') and loops over the y planes, so the coordinate
+// pipeline (fp16 table -> fp64 normalise -> fp32 un-normalise -> clamp -> weights) runs once per
+// thread.  A 16x16 (x', z') patch per block keeps the source footprint compact for any angle;
+// writes are 128-B row segments of the slice-major [Z][Yp][Xp][2] layout.
+// --------------------------------------------------------------------------------------------
+struct RotGeom {
+    int Y, X, Z, Yp, Xp, pad_y0, pad_x0;
+};
+
+struct Bilin {
+    int i00, i01, i10, i11;   // float2 offsets inside one y plane of obj ([X][Z])
+    float w00, w01, w10, w11;
+};
+
+__device__ __forceinline__ Bilin make_bilin(const uint16_t* coords, int xr, int zr, int X, int Z) {
+#pragma clang fp contract(off)      // torch / NumPy evaluate this pipeline without fused multiply-adds: match them bit for bit
+    Bilin b;
+    if (coords == nullptr) {
+        b.i00 = b.i01 = b.i10 = b.i11 = xr * Z + zr;
+        b.w00 = 1.f; b.w01 = b.w10 = b.w11 = 0.f;
+        return b;
+    }
+    const __half* ch = reinterpret_cast<const __half*>(coords) + 2 * ((size_t)xr * Z + zr);
+    const double x_old = (double)__half2float(ch[0]);
+    const double z_old = (double)__half2float(ch[1]);
+    // wrappers.py:1137: grid = -1 + 2*grid/arr_shape + 1/arr_shape on the flipped (z, x) pair, arr_shape = (X, Z)
+    const float gz = (float)(-1.0 + 2.0 * z_old / (double)X + 1.0 / (double)X);
+    const float gx = (float)(-1.0 + 2.0 * x_old / (double)Z + 1.0 / (double)Z);
+    float iz = ((gz + 1.f) * (float)Z - 1.f) / 2.f;
+    float ix = ((gx + 1.f) * (float)X - 1.f) / 2.f;
+    iz = fminf((float)(Z - 1), fmaxf(iz, 0.f));
+    ix = fminf((float)(X - 1), fmaxf(ix, 0.f));
+    const float fz = floorf(iz), fx = floorf(ix);
+    const float tz = iz - fz, tx = ix - fx;
+    const int z0 = (int)fz, x0 = (int)fx;
+    const bool vz = (z0 + 1 <= Z - 1), vx = (x0 + 1 <= X - 1);
+    const int z1 = vz ? z0 + 1 : z0, x1 = vx ? x0 + 1 : x0;
+    b.i00 = x0 * Z + z0; b.i01 = x0 * Z + z1; b.i10 = x1 * Z + z0; b.i11 = x1 * Z + z1;
+    b.w00 = (1.f - tx) * (1.f - tz);
+    b.w01 = vz ? (1.f - tx) * tz : 0.f;
+    b.w10 = vx ? tx * (1.f - tz) : 0.f;
+    b.w11 = (vx && vz) ? tx * tz : 0.f;
+    return b;
+}
+
+// trans != nullptr: the slice transmission of every gathered voxel is stored beside it (same layout), so that the
+// multislice kernel multiplies with a loaded number instead of evaluating exp / sincos per covering position and sweep.
+__global__ __launch_bounds__(256) void rotate_fwd_kernel(const float2* __restrict__ obj, const uint16_t* __restrict__ coords,
+                                                         float2* __restrict__ rot, float2* __restrict__ trans, float k1, float sigma,
+                                                         RotGeom g, int y_lo, int y_hi, int y_chunk) {
+    const int xr = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int zr = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (xr >= g.X || zr >= g.Z) return;
+    const Bilin b = make_bilin(coords, xr, zr, g.X, g.Z);
+    const int ya = y_lo + blockIdx.z * y_chunk;
+    const int yb = min(ya + y_chunk, y_hi);
+    const size_t plane = (size_t)g.X * g.Z;
+    for (int y = ya; y < yb; ++y) {
+        const float2* o = obj + (size_t)y * plane;
+        const float2 v00 = o[b.i00], v01 = o[b.i01], v10 = o[b.i10], v11 = o[b.i11];
+        float2 r;
+        r.x = v00.x * b.w00 + v01.x * b.w01 + v10.x * b.w10 + v11.x * b.w11;
+        r.y = v00.y * b.w00 + v01.y * b.w01 + v10.y * b.w10 + v11.y * b.w11;
+        const size_t o_rot = ((size_t)zr * g.Yp + g.pad_y0 + y) * g.Xp + g.pad_x0 + xr;
+        if (rot) rot[o_rot] = r;
+        if (trans) trans[o_rot] = slice_transmission(r, k1, sigma);
+    }
+}
+
+// R objects stacked along y, block r (planes [r * Yb, (r + 1) * Yb) of the stacked rotated frame) gathered with ITS angle's table
+// from the ONE real object (adorym_amd.AngleBatch: the 16 angles of a config-2 update): one launch instead of R launches of a
+// few blocks each.  Same arithmetic per voxel as rotate_fwd_kernel.
+__global__ __launch_bounds__(256) void rotate_fwd_stack_kernel(const float2* __restrict__ obj, const uint16_t* const* __restrict__ tables,
+                                                               int Yb, float2* __restrict__ rot, float2* __restrict__ trans, float k1,
+                                                               float sigma, RotGeom g, int y_chunk) {
+    const int xr = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int zr = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (xr >= g.X || zr >= g.Z) return;
+    const int ya = blockIdx.z * y_chunk;                 // (y_chunk divides Yb: a block never straddles two angles)
+    const int r = ya / Yb;
+    const Bilin b = make_bilin(tables[r], xr, zr, g.X, g.Z);
+    const int yb = min(ya + y_chunk, g.Y);
+    const size_t plane = (size_t)g.X * g.Z;
+    for (int y = ya; y < yb; ++y) {
+        const float2* o = obj + (size_t)(y - r * Yb) * plane;
+        const float2 v00 = o[b.i00], v01 = o[b.i01], v10 = o[b.i10], v11 = o[b.i11];
+        float2 q;
+        q.x = v00.x * b.w00 + v01.x * b.w01 + v10.x * b.w10 + v11.x * b.w11;
+        q.y = v00.y * b.w00 + v01.y * b.w01 + v10.y * b.w10 + v11.y * b.w11;
+        const size_t o_rot = ((size_t)zr * g.Yp + g.pad_y0 + y) * g.Xp + g.pad_x0 + xr;
+        if (rot) rot[o_rot] = q;
+        if (trans) trans[o_rot] = slice_transmission(q, k1, sigma);
+    }
+}
+
+// No rotation (coords == nullptr) on a thin object -- the 2-D modes, Z = 1: the general kernels above would keep one thread in
+// sixteen busy (their 16 x 16 patches span (x', z')).  One thread per voxel, z fastest like the object: the same numbers (weights
+// 1, 0, 0, 0), 13-14 us -> a plain copy's time on the config-1 shape.
+__global__ __launch_bounds__(256) void identity_fwd_kernel(const float2* __restrict__ obj, float2* __restrict__ rot, float2* __restrict__ trans,
+                                                           float k1, float sigma, RotGeom g, int y_lo, int y_hi) {
+    const size_t n = (size_t)(y_hi - y_lo) * g.X * g.Z;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int z = (int)(i % g.Z);
+        const size_t yx = i / g.Z;
+        const int x = (int)(yx % g.X), y = y_lo + (int)(yx / g.X);
+        const float2 r = obj[((size_t)y * g.X + x) * g.Z + z];
+        const size_t o_rot = ((size_t)z * g.Yp + g.pad_y0 + y) * g.Xp + g.pad_x0 + x;
+        if (rot) rot[o_rot] = r;
+        if (trans) trans[o_rot] = slice_transmission(r, k1, sigma);
+    }
+}
+__global__ __launch_bounds__(256) void identity_adj_kernel(const float2* __restrict__ grot, float2* __restrict__ gobj, RotGeom g, int y_lo,
+                                                           int y_hi) {
+    const size_t n = (size_t)(y_hi - y_lo) * g.X * g.Z;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int z = (int)(i % g.Z);
+        const size_t yx = i / g.Z;
+        const int x = (int)(yx % g.X), y = y_lo + (int)(yx / g.X);
+        const float2 v = grot[((size_t)z * g.Yp + g.pad_y0 + y) * g.Xp + g.pad_x0 + x];
+        float2* o = gobj + ((size_t)y * g.X + x) * g.Z + z;
+        float2 c = *o;
+        c.x += v.x;
+        c.y += v.y;
+        *o = c;
+    }
+}
+
+// slice transmissions of rows [row_lo, row_hi) of every slice of a rotated-frame buffer (pads included): the cache's
+// initial fill (obj_rot == nullptr: vacuum, 1 + 0i) and adm_transmission_refresh
+__global__ __launch_bounds__(256) void transmission_kernel(const float2* __restrict__ rot, float2* __restrict__ trans, float k1,
+                                                           float sigma, int Z, int Yp, int Xp, int row_lo, int row_hi) {
+    const size_t per = (size_t)(row_hi - row_lo) * Xp;
+    const size_t n = per * Z;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t z = i / per, r = i - z * per;
+        const size_t o = (z * Yp + row_lo) * Xp + r;
+        trans[o] = rot ? slice_transmission(rot[o], k1, sigma) : make_float2(1.f, 0.f);
+    }
+}
+
+__global__ __launch_bounds__(256) void rotate_adj_kernel(const float2* __restrict__ grot, const uint16_t* __restrict__ coords,
+                                                         float* __restrict__ gobj, RotGeom g, int y_lo, int y_hi, int y_chunk) {
+    const int xr = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int zr = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (xr >= g.X || zr >= g.Z) return;
+    const Bilin b = make_bilin(coords, xr, zr, g.X, g.Z);
+    const int ya = y_lo + blockIdx.z * y_chunk;
+    const int yb = min(ya + y_chunk, y_hi);
+    const size_t plane = (size_t)g.X * g.Z;
+    for (int y = ya; y < yb; ++y) {
+        const float2 v = grot[((size_t)zr * g.Yp + g.pad_y0 + y) * g.Xp + g.pad_x0 + xr];
+        float* o = gobj + 2 * (size_t)y * plane;
+        if (b.w00 != 0.f) { atomicAdd(o + 2 * b.i00, v.x * b.w00); atomicAdd(o + 2 * b.i00 + 1, v.y * b.w00); }
+        if (b.w01 != 0.f) { atomicAdd(o + 2 * b.i01, v.x * b.w01); atomicAdd(o + 2 * b.i01 + 1, v.y * b.w01); }
+        if (b.w10 != 0.f) { atomicAdd(o + 2 * b.i10, v.x * b.w10); atomicAdd(o + 2 * b.i10 + 1, v.y * b.w10); }
+        if (b.w11 != 0.f) { atomicAdd(o + 2 * b.i11, v.x * b.w11); atomicAdd(o + 2 * b.i11 + 1, v.y * b.w11); }
+    }
+}
+
+// Rotation adjoint as a GATHER (deterministic, no atomics): the transpose of the bilinear sampling
+// operator is prebuilt per angle as a CSR matrix over object-plane voxels (host: adorym_amd/util.py
+// build_rotation_adjoint_csr, same fp32 coordinate pipeline as make_bilin).  One thread owns one object
+// voxel column (x, z) -- consecutive threads are consecutive z, the fastest object axis, so the
+// read-modify-write of grad_obj is coalesced -- and walks the y planes four at a time.
+// A block owns a 16 x 16 patch of object-plane voxels and four y planes.  ALONG_X = false: lanes run along z (the
+// fastest object axis): gobj accesses are coalesced, and so are the gathers from grad_rot when |sin(theta)| is large
+// (a step in z is then a step in x').  ALONG_X = true (|cos| > |sin|): lanes run along x so that the gathered
+// rotated-frame voxels are consecutive in x' (the fastest axis of [Z][Yp][Xp]); the patch is then transposed through
+// LDS so that the read-modify-write of gobj is still issued along z.
+template <bool ALONG_X>
+__global__ __launch_bounds__(256) void rotate_adj_csr_kernel(const float2* __restrict__ grot, const int* __restrict__ ptr,
+                                                             const int* __restrict__ src, const float* __restrict__ wgt,
+                                                             float2* __restrict__ gobj, RotGeom g, int y_lo, int y_hi) {
+    __shared__ float2 tile[4][16][17];
+    const int lx = ALONG_X ? (threadIdx.x & 15) : (threadIdx.x >> 4);
+    const int lz = ALONG_X ? (threadIdx.x >> 4) : (threadIdx.x & 15);
+    const int x = blockIdx.x * 16 + lx, z = blockIdx.y * 16 + lz;
+    const bool ok = (x < g.X) && (z < g.Z);
+    const int t = ok ? x * g.Z + z : 0;
+    const int beg = ok ? ptr[t] : 0, end = ok ? ptr[t + 1] : 0;
+    const int y0 = y_lo + blockIdx.z * 4;
+    const int ny = min(4, y_hi - y0);
+    const size_t plane = (size_t)g.X * g.Z;
+    float2 a[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = make_float2(0.f, 0.f);
+    const size_t row = (size_t)(g.pad_y0 + y0) * g.Xp;
+    if (ny == 4) {
+        for (int j = beg; j < end; ++j) {
+            const float w = wgt[j];
+            const float2* q = grot + (size_t)src[j] + row;
+            const float2 v0 = q[0], v1 = q[g.Xp], v2 = q[2 * (size_t)g.Xp], v3 = q[3 * (size_t)g.Xp];
+            a[0].x += w * v0.x; a[0].y += w * v0.y;
+            a[1].x += w * v1.x; a[1].y += w * v1.y;
+            a[2].x += w * v2.x; a[2].y += w * v2.y;
+            a[3].x += w * v3.x; a[3].y += w * v3.y;
+        }
+    } else {
+        for (int j = beg; j < end; ++j) {
+            const float w = wgt[j];
+            const float2* q = grot + (size_t)src[j] + row;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < ny) { const float2 v = q[(size_t)i * g.Xp]; a[i].x += w * v.x; a[i].y += w * v.y; }
+        }
+    }
+    int wx = lx, wz = lz;
+    if (ALONG_X) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) tile[i][lx][lz] = a[i];
+        __syncthreads();
+        wx = threadIdx.x >> 4; wz = threadIdx.x & 15;          // now lanes run along z
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = tile[i][wx][wz];
+    }
+    const int ox = blockIdx.x * 16 + wx, oz = blockIdx.y * 16 + wz;
+    if (ox < g.X && oz < g.Z) {
+        float2* o = gobj + (size_t)y0 * plane + (size_t)ox * g.Z + oz;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < ny) { float2 c = o[(size_t)i * plane]; c.x += a[i].x; c.y += a[i].y; o[(size_t)i * plane] = c; }
+    }
+}
+
+// LDS-staged variant of the CSR rotation adjoint: the sources of a 16 x 16 patch of object-plane voxels lie in a
+// (x', z') bounding box of at most ~27 x 27 rotated-frame voxels (host-computed per patch and angle).  The box rows are
+// loaded contiguously along x' into LDS for four y planes, and the bilinear-transpose gather then runs out of LDS -- the
+// memory access pattern no longer depends on the angle (the direct gather is 10x slower at 45 degrees than at 0).
+// lsrc[j] = (z' - box.z0) * box.w + (x' - box.x0) of CSR entry j.
+#define ADM_STAGE_MAX 1024          // float2 elements per plane in LDS when four planes are staged at once
+__global__ __launch_bounds__(256) void rotate_adj_staged_kernel(const float2* __restrict__ grot, const int* __restrict__ ptr,
+                                                                const int* __restrict__ src, const unsigned short* __restrict__ lsrc,
+                                                                const float* __restrict__ wgt,
+                                                                const int4* __restrict__ boxes, float2* __restrict__ gobj, RotGeom g,
+                                                                int y_lo, int y_hi) {
+    __shared__ float2 stage[4 * ADM_STAGE_MAX];
+    const int4 box = boxes[blockIdx.y * gridDim.x + blockIdx.x];      // (x0, z0, w, h)
+    const int y0 = y_lo + blockIdx.z * 4;
+    const int ny = min(4, y_hi - y0);
+    const int bw = box.z, bh = box.w, per = bw * bh;
+    const size_t slice = (size_t)g.Yp * g.Xp;
+    const size_t plane = (size_t)g.X * g.Z;
+    const int lx = threadIdx.x >> 4, lz = threadIdx.x & 15;          // lanes along z, the fastest object axis
+    const int x = blockIdx.x * 16 + lx, z = blockIdx.y * 16 + lz;
+    const bool ok = (x < g.X) && (z < g.Z);
+    const int t = ok ? x * g.Z + z : 0;
+    const int beg = ok ? ptr[t] : 0, end = ok ? ptr[t + 1] : 0;
+    float2* o = gobj + (size_t)y0 * plane + (size_t)x * g.Z + z;
+    if (bw == 0) {
+        // no usable box (only for objects much larger than 256^3): gather from global memory
+        if (!ok) return;
+        const size_t row = (size_t)(g.pad_y0 + y0) * g.Xp;
+        float2 a[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = make_float2(0.f, 0.f);
+        for (int j = beg; j < end; ++j) {
+            const float w = wgt[j];
+            const float2* q = grot + (size_t)src[j] + row;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < ny) { const float2 v = q[(size_t)i * g.Xp]; a[i].x += w * v.x; a[i].y += w * v.y; }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < ny) { float2 c = o[(size_t)i * plane]; c.x += a[i].x; c.y += a[i].y; o[(size_t)i * plane] = c; }
+        return;
+    }
+    if (per <= ADM_STAGE_MAX) {
+        // interior patch: the boxes of four y planes fit at once
+        for (int idx = threadIdx.x; idx < 4 * per; idx += 256) {
+            const int p = idx / per, rem = idx - p * per;
+            const int zz = rem / bw, xx = rem - zz * bw;
+            float2 v = make_float2(0.f, 0.f);
+            if (p < ny) v = grot[(size_t)(box.y + zz) * slice + (size_t)(g.pad_y0 + y0 + p) * g.Xp + g.pad_x0 + box.x + xx];
+            stage[p * ADM_STAGE_MAX + rem] = v;
+        }
+        __syncthreads();
+        if (!ok) return;
+        float2 a[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = make_float2(0.f, 0.f);
+        for (int j = beg; j < end; ++j) {
+            const float w = wgt[j];
+            const int q = lsrc[j];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { const float2 v = stage[i * ADM_STAGE_MAX + q]; a[i].x += w * v.x; a[i].y += w * v.y; }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < ny) { float2 c = o[(size_t)i * plane]; c.x += a[i].x; c.y += a[i].y; o[(size_t)i * plane] = c; }
+        return;
+    }
+    // rim patch (border clamping folds a corner of the rotated frame onto it: box of up to 4096 voxels): one or two planes
+    // per pass over the CSR entries, whatever fits the 32 KB stage
+    const int npp = (2 * per <= 4 * ADM_STAGE_MAX) ? 2 : 1;
+    for (int p0 = 0; p0 < ny; p0 += npp) {
+        for (int idx = threadIdx.x; idx < npp * per; idx += 256) {
+            const int pp = idx / per, rem = idx - pp * per;
+            const int zz = rem / bw, xx = rem - zz * bw;
+            float2 v = make_float2(0.f, 0.f);
+            if (p0 + pp < ny) v = grot[(size_t)(box.y + zz) * slice + (size_t)(g.pad_y0 + y0 + p0 + pp) * g.Xp + g.pad_x0 + box.x + xx];
+            stage[idx] = v;
+        }
+        __syncthreads();
+        if (ok) {
+            float2 acc0 = make_float2(0.f, 0.f), acc1 = make_float2(0.f, 0.f);
+            const int second = (npp == 2) ? per : 0;
+            for (int j = beg; j < end; j += 8) {       // eight entries' weight/offset loads in flight, then the LDS gathers
+                float w[8];
+                int q[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int jj = min(j + u, end - 1);
+                    w[u] = (j + u < end) ? wgt[jj] : 0.f;
+                    q[u] = lsrc[jj];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const float2 v0 = stage[q[u]];
+                    const float2 v1 = stage[q[u] + second];
+                    acc0.x += w[u] * v0.x; acc0.y += w[u] * v0.y;
+                    acc1.x += w[u] * v1.x; acc1.y += w[u] * v1.y;
+                }
+            }
+            float2 c = o[(size_t)p0 * plane];
+            c.x += acc0.x;
+            c.y += acc0.y;
+            o[(size_t)p0 * plane] = c;
+            if (npp == 2 && p0 + 1 < ny) {
+                float2 d = o[(size_t)(p0 + 1) * plane];
+                d.x += acc1.x;
+                d.y += acc1.y;
+                o[(size_t)(p0 + 1) * plane] = d;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// The staged adjoint for R objects stacked along y (adorym_amd.AngleBatch): block r of the stacked gradient image is back-rotated with
+// ITS angle's CSR and all R contributions are added, r ascending, to the ONE real gradient -- c = g; c += a_0; c += a_1; ... ; g = c:
+// the additions R sequential launches of rotate_adj_staged_kernel would make, in the same order, in one launch (16 launches of
+// 6 - 12 us each per config-2 update).  Same three cases per (patch, angle) as above, written without early exits so that every
+// thread reaches the barriers that separate one angle's use of the LDS stage from the next.
+struct AdjTables { const int* ptr; const int* src; const unsigned short* lsrc; const float* wgt; const int4* boxes; };
+// `part` != nullptr: the angles run in PARALLEL -- blockIdx.z = (angle, plane group), the block leaves its angle's term a_r in
+// part[r][y][x][z] and stack_sum_kernel forms c = g; c += a_0; c += a_1; ... afterwards (the same additions in the same order: same
+// bits); a block walking all R angles one after the other is a chain of R stage-fill / barrier / gather rounds (86 us for 16
+// angles of a 64^3 object against 20 + 8).
+__global__ __launch_bounds__(256) void rotate_adj_staged_stack_kernel(const float2* __restrict__ grot, const AdjTables* __restrict__ tabs,
+                                                                      int R, int Yb, float2* __restrict__ gobj, RotGeom g, int npl,
+                                                                      float2* __restrict__ part) {
+    __shared__ float2 stage[4 * ADM_STAGE_MAX];
+    const int nzg = (Yb + npl - 1) / npl;                // plane groups
+    const int zg = part ? (int)blockIdx.z % nzg : (int)blockIdx.z;
+    const int r_lo = part ? (int)blockIdx.z / nzg : 0, r_hi = part ? r_lo + 1 : R;
+    const int y0 = zg * npl;                             // first plane (of the REAL object, Yb planes) of this block: npl = 1, 2 or 4 planes
+    const int ny = min(npl, Yb - y0);
+    const size_t slice = (size_t)g.Yp * g.Xp;
+    const size_t plane = (size_t)g.X * g.Z;
+    const int lx = threadIdx.x >> 4, lz = threadIdx.x & 15;
+    const int x = blockIdx.x * 16 + lx, z = blockIdx.y * 16 + lz;
+    const bool ok = (x < g.X) && (z < g.Z);
+    const int t = ok ? x * g.Z + z : 0;
+    float2* o = (part ? part + (size_t)r_lo * Yb * plane : gobj) + (size_t)y0 * plane + (size_t)x * g.Z + z;
+    float2 c[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = (ok && i < ny && !part) ? o[(size_t)i * plane] : make_float2(0.f, 0.f);
+    for (int r = r_lo; r < r_hi; ++r) {
+        const AdjTables T = tabs[r];
+        const int4 box = T.boxes[blockIdx.y * gridDim.x + blockIdx.x];      // (x0, z0, w, h)
+        const int ys = r * Yb + y0;                     // the same planes in block r of the stacked image
+        const int bw = box.z, bh = box.w, per = bw * bh;
+        const int beg = ok ? T.ptr[t] : 0, end = ok ? T.ptr[t + 1] : 0;
+        if (bw == 0) {
+            const size_t row = (size_t)(g.pad_y0 + ys) * g.Xp;
+            float2 a[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[i] = make_float2(0.f, 0.f);
+            for (int j = beg; j < end; ++j) {
+                const float w = T.wgt[j];
+                const float2* q = grot + (size_t)T.src[j] + row;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (i < ny) { const float2 v = q[(size_t)i * g.Xp]; a[i].x += w * v.x; a[i].y += w * v.y; }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { c[i].x += a[i].x; c[i].y += a[i].y; }
+        } else if (per <= ADM_STAGE_MAX) {
+            for (int idx = threadIdx.x; idx < npl * per; idx += 256) {
+                const int p = idx / per, rem = idx - p * per;
+                const int zz = rem / bw, xx = rem - zz * bw;
+                float2 v = make_float2(0.f, 0.f);
+                if (p < ny) v = grot[(size_t)(box.y + zz) * slice + (size_t)(g.pad_y0 + ys + p) * g.Xp + g.pad_x0 + box.x + xx];
+                stage[p * ADM_STAGE_MAX + rem] = v;
+            }
+            __syncthreads();
+            float2 a[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[i] = make_float2(0.f, 0.f);
+            for (int j = beg; j < end; ++j) {
+                const float w = T.wgt[j];
+                const int q = T.lsrc[j];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (i < ny) { const float2 v = stage[i * ADM_STAGE_MAX + q]; a[i].x += w * v.x; a[i].y += w * v.y; }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { c[i].x += a[i].x; c[i].y += a[i].y; }
+        } else {
+            const int npp = (npl >= 2 && 2 * per <= 4 * ADM_STAGE_MAX) ? 2 : 1;
+            for (int p0 = 0; p0 < ny; p0 += npp) {
+                for (int idx = threadIdx.x; idx < npp * per; idx += 256) {
+                    const int pp = idx / per, rem = idx - pp * per;
+                    const int zz = rem / bw, xx = rem - zz * bw;
+                    float2 v = make_float2(0.f, 0.f);
+                    if (p0 + pp < ny) v = grot[(size_t)(box.y + zz) * slice + (size_t)(g.pad_y0 + ys + p0 + pp) * g.Xp + g.pad_x0 + box.x + xx];
+                    stage[idx] = v;
+                }
+                __syncthreads();
+                float2 acc0 = make_float2(0.f, 0.f), acc1 = make_float2(0.f, 0.f);
+                const int second = (npp == 2) ? per : 0;
+                for (int j = beg; j < end; j += 8) {
+                    float w[8];
+                    int q[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int jj = min(j + u, end - 1);
+                        w[u] = (j + u < end) ? T.wgt[jj] : 0.f;
+                        q[u] = T.lsrc[jj];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const float2 v0 = stage[q[u]];
+                        const float2 v1 = stage[q[u] + second];
+                        acc0.x += w[u] * v0.x; acc0.y += w[u] * v0.y;
+                        acc1.x += w[u] * v1.x; acc1.y += w[u] * v1.y;
+                    }
+                }
+                // (p0 is uniform: the static indices below keep c[] in registers)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (i == p0) { c[i].x += acc0.x; c[i].y += acc0.y; }
+                    if (npp == 2 && i == p0 + 1) { c[i].x += acc1.x; c[i].y += acc1.y; }
+                }
+                __syncthreads();
+            }
+        }
+        __syncthreads();                                 // the next angle refills the stage
+    }
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < ny) o[(size_t)i * plane] = c[i];
+    }
+}
+}  // namespace adm
+using namespace adm;
+
+extern "C" int adm_rotate_fwd(adm_plan* plan, const float* obj, const uint16_t* coords, float* obj_rot, int y_lo, int y_hi) {
+    if (!plan || !obj || !obj_rot) return fail(ADM_ERR_INVALID, "adm_rotate_fwd: null argument");
+    const adm_plan_desc& d = plan->d;
+    if (y_lo < 0 || y_hi > d.obj_y || y_lo > y_hi) return fail(ADM_ERR_INVALID, "adm_rotate_fwd: bad y range");
+    if (y_lo == y_hi) return ADM_OK;
+    RotGeom g{d.obj_y, d.obj_x, d.obj_z, plan->Yp, plan->Xp, d.pad_y0, d.pad_x0};
+    // y planes per block: 32 (the (x', z') sampling weights are decoded once per block and reused) -- unless that leaves the chip
+    // empty: a 64^3 object has 16 patches x 2 chunks = 32 blocks that each walk 32 planes one dependent gather after the other
+    // (17 us per launch, 16 launches per config-2 update); then fewer planes per block, down to one
+    int y_chunk = 32;
+    const int n_patch = ((d.obj_x + 15) / 16) * ((d.obj_z + 15) / 16);
+    while (y_chunk > 1 && n_patch * ((y_hi - y_lo + y_chunk - 1) / y_chunk) < 512) y_chunk >>= 1;
+    dim3 grid((d.obj_x + 15) / 16, (d.obj_z + 15) / 16, (y_hi - y_lo + y_chunk - 1) / y_chunk);
+    // cache mode 2: only the transmissions are written (half the stores); obj_rot then merely names the image the cache holds
+    float2* rot_out = (plan->trans_dev && plan->trans_only) ? (float2*)nullptr : (float2*)obj_rot;
+    if (!coords && d.obj_z < 16)
+        hipLaunchKernelGGL(identity_fwd_kernel, dim3(stream_grid((size_t)(y_hi - y_lo) * d.obj_x * d.obj_z)), dim3(256), 0, plan->ctx->stream,
+                           (const float2*)obj, rot_out, plan->trans_dev, d.k1, (float)d.sign_convention, g, y_lo, y_hi);
+    else
+        hipLaunchKernelGGL(rotate_fwd_kernel, grid, dim3(256), 0, plan->ctx->stream, (const float2*)obj, coords, rot_out, plan->trans_dev,
+                           d.k1, (float)d.sign_convention, g, y_lo, y_hi, y_chunk);
+    ADM_HIP(hipGetLastError());
+    if (plan->trans_dev) plan->trans_src = obj_rot;
+    return ADM_OK;
+}
+
+extern "C" int adm_rotate_fwd_stack(adm_plan* plan, const float* obj, const void* tables_dev, int n_tables, float* obj_rot) {
+    if (!plan || !obj || !tables_dev || !obj_rot) return fail(ADM_ERR_INVALID, "adm_rotate_fwd_stack: null argument");
+    const adm_plan_desc& d = plan->d;
+    if (n_tables < 1 || d.obj_y % n_tables) return fail(ADM_ERR_INVALID, "adm_rotate_fwd_stack: the plan's y extent is not n_tables blocks");
+    const int Yb = d.obj_y / n_tables;
+    RotGeom g{d.obj_y, d.obj_x, d.obj_z, plan->Yp, plan->Xp, d.pad_y0, d.pad_x0};
+    int y_chunk = 32;
+    while (y_chunk > 1 && Yb % y_chunk) y_chunk >>= 1;
+    const int n_patch = ((d.obj_x + 15) / 16) * ((d.obj_z + 15) / 16);
+    while (y_chunk > 1 && n_patch * (d.obj_y / y_chunk) < 512) y_chunk >>= 1;
+    dim3 grid((d.obj_x + 15) / 16, (d.obj_z + 15) / 16, d.obj_y / y_chunk);
+    float2* rot_out = (plan->trans_dev && plan->trans_only) ? (float2*)nullptr : (float2*)obj_rot;
+    hipLaunchKernelGGL(rotate_fwd_stack_kernel, grid, dim3(256), 0, plan->ctx->stream, (const float2*)obj,
+                       (const uint16_t* const*)tables_dev, Yb, rot_out, plan->trans_dev, d.k1, (float)d.sign_convention, g, y_chunk);
+    ADM_HIP(hipGetLastError());
+    if (plan->trans_dev) plan->trans_src = obj_rot;
+    return ADM_OK;
+}
+
+static int transmission_fill(adm_plan* plan, const float* obj_rot, int row_lo, int row_hi) {
+    const adm_plan_desc& d = plan->d;
+    const size_t n = (size_t)(row_hi - row_lo) * plan->Xp * d.obj_z;
+    hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0, plan->ctx->stream,
+                       (const float2*)obj_rot, plan->trans_dev, d.k1, (float)d.sign_convention, d.obj_z, plan->Yp, plan->Xp, row_lo,
+                       row_hi);
+    ADM_HIP(hipGetLastError());
+    return ADM_OK;
+}
+
+extern "C" int adm_plan_set_transmission_cache(adm_plan* plan, int on) {
+    if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_transmission_cache: null plan");
+    const adm_plan_desc& d = plan->d;
+    if (!on) {
+        if (plan->trans_dev) {
+            ADM_HIP(hipStreamSynchronize(plan->ctx->main_stream));
+            ADM_HIP(hipFree(plan->trans_dev));
+        }
+        plan->trans_dev = nullptr;
+        plan->trans_src = nullptr;
+        plan->trans_only = false;
+        return ADM_OK;
+    }
+    if (d.unknown_type != 0 || d.binning != 1)      // (validated first: a refused call leaves the plan as it was)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_transmission_cache: needs unknown_type delta_beta and binning 1");
+    if (!plan->trans_dev) {
+        float2* t = nullptr;
+        ADM_HIP(hipMalloc((void**)&t, (size_t)d.obj_z * plan->Yp * plan->Xp * sizeof(float2)));
+        plan->trans_dev = t;
+        plan->trans_src = nullptr;
+        const int rc = transmission_fill(plan, nullptr, 0, plan->Yp);      // vacuum everywhere: the pads keep it forever
+        if (rc) {
+            (void)hipFree(t);
+            plan->trans_dev = nullptr;
+            plan->trans_only = false;
+            return rc;
+        }
+    }
+    plan->trans_only = (on == 2);
+    return ADM_OK;
+}
+
+extern "C" int adm_transmission_refresh(adm_plan* plan, const float* obj_rot, int y_lo, int y_hi) {
+    if (!plan || !obj_rot) return fail(ADM_ERR_INVALID, "adm_transmission_refresh: null argument");
+    if (!plan->trans_dev) return fail(ADM_ERR_INVALID, "adm_transmission_refresh: the plan has no transmission cache");
+    const adm_plan_desc& d = plan->d;
+    if (y_lo < 0 || y_hi > d.obj_y || y_lo > y_hi) return fail(ADM_ERR_INVALID, "adm_transmission_refresh: bad y range");
+    plan->trans_src = obj_rot;
+    if (y_lo == y_hi) return ADM_OK;
+    return transmission_fill(plan, obj_rot, d.pad_y0 + y_lo, d.pad_y0 + y_hi);
+}
+
+extern "C" int adm_rotate_adj(adm_plan* plan, const float* grad_rot, const uint16_t* coords, float* grad_obj, int y_lo, int y_hi) {
+    if (!plan || !grad_rot || !grad_obj) return fail(ADM_ERR_INVALID, "adm_rotate_adj: null argument");
+    const adm_plan_desc& d = plan->d;
+    if (y_lo < 0 || y_hi > d.obj_y || y_lo > y_hi) return fail(ADM_ERR_INVALID, "adm_rotate_adj: bad y range");
+    if (y_lo == y_hi) return ADM_OK;
+    RotGeom g{d.obj_y, d.obj_x, d.obj_z, plan->Yp, plan->Xp, d.pad_y0, d.pad_x0};
+    const int y_chunk = 32;
+    dim3 grid((d.obj_x + 15) / 16, (d.obj_z + 15) / 16, (y_hi - y_lo + y_chunk - 1) / y_chunk);
+    if (!coords && d.obj_z < 16)
+        hipLaunchKernelGGL(identity_adj_kernel, dim3(stream_grid((size_t)(y_hi - y_lo) * d.obj_x * d.obj_z)), dim3(256), 0, plan->ctx->stream,
+                           (const float2*)grad_rot, (float2*)grad_obj, g, y_lo, y_hi);
+    else
+        hipLaunchKernelGGL(rotate_adj_kernel, grid, dim3(256), 0, plan->ctx->stream, (const float2*)grad_rot, coords, grad_obj, g, y_lo,
+                           y_hi, y_chunk);
+    ADM_HIP(hipGetLastError());
+    return ADM_OK;
+}
+
+extern "C" int adm_rotate_adj_csr(adm_plan* plan, const float* grad_rot, const int32_t* csr_ptr, const int32_t* csr_src,
+                                  const float* csr_w, float* grad_obj, int y_lo, int y_hi, int lanes_along_x) {
+    if (!plan || !grad_rot || !csr_ptr || !csr_src || !csr_w || !grad_obj) return fail(ADM_ERR_INVALID, "adm_rotate_adj_csr: null argument");
+    const adm_plan_desc& d = plan->d;
+    if (y_lo < 0 || y_hi > d.obj_y || y_lo > y_hi) return fail(ADM_ERR_INVALID, "adm_rotate_adj_csr: bad y range");
+    if (y_lo == y_hi) return ADM_OK;
+    RotGeom g{d.obj_y, d.obj_x, d.obj_z, plan->Yp, plan->Xp, d.pad_y0, d.pad_x0};
+    dim3 grid((d.obj_x + 15) / 16, (d.obj_z + 15) / 16, (y_hi - y_lo + 3) / 4);
+    if (lanes_along_x)
+        hipLaunchKernelGGL(rotate_adj_csr_kernel<true>, grid, dim3(256), 0, plan->ctx->stream, (const float2*)grad_rot, csr_ptr, csr_src,
+                           csr_w, (float2*)grad_obj, g, y_lo, y_hi);
+    else
+        hipLaunchKernelGGL(rotate_adj_csr_kernel<false>, grid, dim3(256), 0, plan->ctx->stream, (const float2*)grad_rot, csr_ptr, csr_src,
+                           csr_w, (float2*)grad_obj, g, y_lo, y_hi);
+    ADM_HIP(hipGetLastError());
+    return ADM_OK;
+}
+
+extern "C" int adm_rotate_adj_staged(adm_plan* plan, const float* grad_rot, const int32_t* csr_ptr, const int32_t* csr_src,
+                                     const uint16_t* csr_lsrc, const float* csr_w, const int32_t* boxes, float* grad_obj, int y_lo,
+                                     int y_hi) {
+    if (!plan || !grad_rot || !csr_ptr || !csr_src || !csr_lsrc || !csr_w || !boxes || !grad_obj)
+        return fail(ADM_ERR_INVALID, "adm_rotate_adj_staged: null argument");
+    const adm_plan_desc& d = plan->d;
+    if (y_lo < 0 || y_hi > d.obj_y || y_lo > y_hi) return fail(ADM_ERR_INVALID, "adm_rotate_adj_staged: bad y range");
+    if (y_lo == y_hi) return ADM_OK;
+    RotGeom g{d.obj_y, d.obj_x, d.obj_z, plan->Yp, plan->Xp, d.pad_y0, d.pad_x0};
+    dim3 grid((d.obj_x + 15) / 16, (d.obj_z + 15) / 16, (y_hi - y_lo + 3) / 4);
+    hipLaunchKernelGGL(rotate_adj_staged_kernel, grid, dim3(256), 0, plan->ctx->stream, (const float2*)grad_rot, csr_ptr, csr_src,
+                       (const unsigned short*)csr_lsrc, csr_w, (const int4*)boxes, (float2*)grad_obj, g, y_lo, y_hi);
+    ADM_HIP(hipGetLastError());
+    return ADM_OK;
+}
+
+#ifndef ADM_STACK_MIN_BLOCKS
+#define ADM_STACK_MIN_BLOCKS 2048
+#endif
+// g[i] = ((g[i] + a_0[i]) + a_1[i]) + ... : the terms of the R angles in angle order
+__global__ __launch_bounds__(256) void stack_sum_kernel(const float2* __restrict__ part, int R, size_t n, float2* __restrict__ gobj) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float2 c = gobj[i];
+    for (int r = 0; r < R; ++r) {
+        const float2 a = part[(size_t)r * n + i];
+        c.x += a.x;
+        c.y += a.y;
+    }
+    gobj[i] = c;
+}
+
+extern "C" int adm_rotate_adj_staged_stack(adm_plan* plan, const float* grad_rot, const void* tables_dev, int n_tables, float* grad_obj,
+                                           float* scratch, size_t scratch_bytes) {
+    if (!plan || !grad_rot || !tables_dev || !grad_obj) return fail(ADM_ERR_INVALID, "adm_rotate_adj_staged_stack: null argument");
+    const adm_plan_desc& d = plan->d;
+    if (n_tables < 1 || d.obj_y % n_tables) return fail(ADM_ERR_INVALID, "adm_rotate_adj_staged_stack: the plan's y extent is not n_tables blocks");
+    const int Yb = d.obj_y / n_tables;
+    RotGeom g{d.obj_y, d.obj_x, d.obj_z, plan->Yp, plan->Xp, d.pad_y0, d.pad_x0};
+    // planes per block: four (one pass over a patch's CSR entries serves four planes) unless that leaves the chip short of blocks --
+    // every block walks the n_tables angles one after the other, so a 64^3 object wants all 1024 (patch, plane) pairs in flight
+    int npl = 4;
+    const int n_patch = ((d.obj_x + 15) / 16) * ((d.obj_z + 15) / 16);
+    while (npl > 1 && n_patch * ((Yb + npl - 1) / npl) < 1024) npl >>= 1;
+    const size_t n_real = (size_t)Yb * d.obj_x * d.obj_z;
+    if (scratch) {
+        // the angles side by side (scratch: n_tables copies of the real gradient's size), then their sum in angle order
+        if (scratch_bytes < (size_t)n_tables * n_real * sizeof(float2))
+            return fail(ADM_ERR_INVALID, "adm_rotate_adj_staged_stack: scratch smaller than n_tables x the real object");
+        npl = 4;
+        while (npl > 1 && (size_t)n_patch * ((Yb + npl - 1) / npl) * n_tables < (size_t)ADM_STACK_MIN_BLOCKS) npl >>= 1;
+        dim3 gridp((d.obj_x + 15) / 16, (d.obj_z + 15) / 16, ((Yb + npl - 1) / npl) * n_tables);
+        hipLaunchKernelGGL(rotate_adj_staged_stack_kernel, gridp, dim3(256), 0, plan->ctx->stream, (const float2*)grad_rot,
+                           (const AdjTables*)tables_dev, n_tables, Yb, (float2*)grad_obj, g, npl, (float2*)scratch);
+        hipLaunchKernelGGL(stack_sum_kernel, dim3((unsigned)((n_real + 255) / 256)), dim3(256), 0, plan->ctx->stream,
+                           (const float2*)scratch, n_tables, n_real, (float2*)grad_obj);
+        ADM_HIP(hipGetLastError());
+        return ADM_OK;
+    }
+    dim3 grid((d.obj_x + 15) / 16, (d.obj_z + 15) / 16, (Yb + npl - 1) / npl);
+    hipLaunchKernelGGL(rotate_adj_staged_stack_kernel, grid, dim3(256), 0, plan->ctx->stream, (const float2*)grad_rot,
+                       (const AdjTables*)tables_dev, n_tables, Yb, (float2*)grad_obj, g, npl, (float2*)nullptr);
+    ADM_HIP(hipGetLastError());
+    return ADM_OK;
+}

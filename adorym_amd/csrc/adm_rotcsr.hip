@@ -19,7 +19,7 @@
 
 namespace adm {
 
-// identical to make_bilin of adm_object.hip (kept in step by tests/test_gpu_parity.py: GPU-built vs host-built tables)
+// identical to make_bilin of adm_rotate.hip (kept in step by tests/test_gpu_parity.py: GPU-built vs host-built tables)
 struct Bilin4 {
     int idx[4];
     float w[4];

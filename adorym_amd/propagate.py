@@ -573,7 +573,7 @@ class MultisliceEngine(object):
         self._accumulated = want_grad
         self._acc_parts = []
 
-    MAX_COVER = 64        # ADM_MAXCOVER of adm_object.hip: cover-list entries per rotated-frame pixel
+    MAX_COVER = 64        # ADM_MAXCOVER of adm_host.h: cover-list entries per rotated-frame pixel
 
     def _check_cover(self, pos):
         """How many tiles of ``pos`` cover the most-covered pixel (an upper bound of len(pos) is returned for small batches).  The

@@ -1,4 +1,4 @@
-"""The overlap-add of the per-position tile gradients (adm_object.hip: cover_build_kernel, tile_accumulate_kernel and the host
+"""The overlap-add of the per-position tile gradients (adm_overlap_add.hip: cover_build_kernel, tile_accumulate_kernel and the host
 code around them) against a host reference that reproduces it BIT FOR BIT (test infrastructure only).
 
 The operation is fp32 addition in a fixed order: per padded pixel and modulation step the elements of the covering positions are
@@ -46,7 +46,7 @@ def probe_shape(P):
 
 
 def thread_geometry(N):
-    """(R1, R2, G, LPW, NT) of a tuned size: Geo<N, R1, R2> of adm_ms_math.h as tile_geom (adm_object.hip) fills it in."""
+    """(R1, R2, G, LPW, NT) of a tuned size: Geo<N, R1, R2> of adm_ms_math.h as tile_geom (adm_overlap_add.hip) fills it in."""
     R1, R2 = SIZES[N]
     G = max(R1, R2)
     LPW = 64 // G

@@ -1,4 +1,4 @@
-"""Every path of the rotation kernels (adm_object.hip, adm_rotcsr.hip) against two references (test infrastructure only: the
+"""Every path of the rotation kernels (adm_rotate.hip, adm_rotcsr.hip) against two references (test infrastructure only: the
 oracle is the checker, never the product).  Case tables, input builder, references and bars; the GPU tests are in
 tests/test_gpu_rotation_matrix.py, and tests/test_rotation_matrix_coverage.py checks on the CPU -- from the kernel source and
 the host table builder -- that the tables below reach every branch they claim.
@@ -48,7 +48,7 @@ SENTINEL = np.float32(-12345.678)
 POISON = np.float32(1e30)
 
 # --------------------------------------------------------------------------- what the launch code decides, restated
-# (defaults = the constants of adm_object.hip / adm_rotcsr.hip / util.py; the coverage test parses them from the source,
+# (defaults = the constants of adm_rotate.hip / adm_rotcsr.hip / util.py; the coverage test parses them from the source,
 # asserts they are these and recomputes every claim below from the parsed values)
 STAGE_MAX = 1024          # ADM_STAGE_MAX: float2 per plane when four planes are staged
 BOX_LIMIT = 4096          # boxes above it get bw = 0 (device and host builder)

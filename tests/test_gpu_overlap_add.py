@@ -1,4 +1,4 @@
-"""The overlap-add of the per-position tile gradients -- cover_build_kernel, tile_accumulate_kernel (adm_object.hip) and the host
+"""The overlap-add of the per-position tile gradients -- cover_build_kernel, tile_accumulate_kernel (adm_overlap_add.hip) and the host
 code around them: tile_geom, the key cache of the lists built ahead, the window / part form, the range passes and the overflow
 flag -- called through the C ABI and compared BIT FOR BIT with the float32 host reference of tests/oa_matrix.py
 (pytest -m gpu).  Every comparison is an equality of uint32 views; there is no tolerance anywhere in this module.

@@ -1,4 +1,4 @@
-"""Every rotation entry point of the C ABI and every branch of its kernels (adm_object.hip, adm_rotcsr.hip) against reference S
+"""Every rotation entry point of the C ABI and every branch of its kernels (adm_rotate.hip, adm_rotcsr.hip) against reference S
 under bar 1 (element-wise, derived) and the fp64 oracle under bar 2 (the 3x rule), with adjointness and bitwise canaries
 (pytest -m gpu).  tests/rot_matrix.py holds the tables, the references and the bars;
 tests/test_rotation_matrix_coverage.py proves on the CPU that the tables reach what the ids below name: the no-box branch

@@ -42,7 +42,7 @@ def _define(src, name):
 def test_the_mirror_uses_the_source_constants():
     from adorym_amd.propagate import MultisliceEngine
     assert _define(_read('adm_host.h'), 'ADM_MAXCOVER') == OA.MAXCOVER == MultisliceEngine.MAX_COVER
-    assert _define(_read('adm_object.hip'), 'TA_STEPS') == OA.TA_STEPS
+    assert _define(_read('adm_overlap_add.hip'), 'TA_STEPS') == OA.TA_STEPS
     m = re.search(r'#define\s+ADM_FOR_EACH_SIZE\(X\)(.*)', _read('adm_multislice.hip'))
     assert m, 'ADM_FOR_EACH_SIZE'
     sizes = {int(n): (int(a), int(b)) for n, a, b in re.findall(r'X\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\)', m.group(1))}
@@ -52,7 +52,7 @@ def test_the_mirror_uses_the_source_constants():
 
 
 def test_the_mirror_follows_cover_build_kernel():
-    src = _read('adm_object.hip')
+    src = _read('adm_overlap_add.hip')
     head = re.search(r'__global__\s+__launch_bounds__\((\d+)\)\s+void\s+cover_build_kernel\s*\(', src)
     assert head and int(head.group(1)) == OA.CHUNK
     body = _flat(_function_body(src, r'void\s+cover_build_kernel\s*\('))
@@ -100,7 +100,7 @@ def test_the_mirror_follows_cover_build_kernel():
 
 
 def test_the_mirror_follows_tile_accumulate_kernel():
-    src = _read('adm_object.hip')
+    src = _read('adm_overlap_add.hip')
     head = re.search(r'__global__\s+__launch_bounds__\((\d+)\)\s+void\s+tile_accumulate_kernel\s*\(', src)
     assert head and int(head.group(1)) == OA.BLOCK_X * OA.BLOCK_Y
     body = _flat(_function_body(src, r'void\s+tile_accumulate_kernel\s*\('))

@@ -20,7 +20,7 @@ def _read(*parts):
 
 
 def _object_src():
-    return _read(CSRC, 'adm_object.hip')
+    return _read(CSRC, 'adm_rotate.hip')
 
 
 def _rotcsr_src():
@@ -34,7 +34,7 @@ def _one(pattern, text, what):
 
 
 def parsed_constants():
-    """The constants and thresholds the tables depend on, from adm_object.hip, adm_rotcsr.hip and util.py."""
+    """The constants and thresholds the tables depend on, from adm_rotate.hip, adm_rotcsr.hip and util.py."""
     src = _object_src()
     k = {}
     k['stage_max'] = int(_one(r'#define\s+ADM_STAGE_MAX\s+(\d+)', src, 'ADM_STAGE_MAX'))
