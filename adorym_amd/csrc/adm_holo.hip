@@ -154,6 +154,12 @@ __device__ __forceinline__ cf holo_transmission(float2 o, int real_imag, float k
     sincosf(-sigma * k1 * o.x, &sn, &cs);
     return make_float2(e * cs, e * sn);
 }
+// a * b rounded on its own: with contraction off the product cannot merge with a following addition into one fused multiply-add,
+// so that `old + mul_rounded(a, b)` adds the very float an overwriting launch stores (accumulated = seeded + overwritten, bit for bit)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 __device__ __forceinline__ cf holo_h(float uv2, float dist_cm, float c1) {
     // -sigma*PI*lambda (c1, rounded once on the host) * dist_nm * (u^2+v^2), every product in fp32 like the reference
     const float arg = (c1 * (dist_cm * 1e7f)) * uv2;
@@ -166,6 +172,20 @@ __device__ __forceinline__ float base_coord(int i, int n) {
     const float step = 2.0f / (float)(n - 1);
     const float lin = (i < n / 2) ? fmaf(step, (float)i, -1.0f) : fmaf(-step, (float)(n - 1 - i), 1.0f);
     return (lin * (float)(n - 1)) / (float)n;
+}
+
+// Where pixel (X, Y) (base coordinates) of the registered hologram is sampled, in pixels of the measured one, before clamping.
+// Every product and sum is rounded on its own, as the reference's element-wise float32 tensors round them (contraction off):
+// near the identity the points sit on pixel centres, where the last bit of the coordinate decides which one-sided derivative
+// of the bilinear interpolation the affine gradient sees -- with th[0] * X contracted into the sum, the matrix gradient of a
+// 64 x 512 field was 2.5e-3 off where the reference's own float32 evaluation is 2e-5 off.  One function for both loops of K3:
+// the samples fetched ahead and the weights applied to them come from the same floats.
+__device__ __forceinline__ void affine_coords(const float (&th)[6], float X, float Y, int nx, int ny, float& ix, float& iy) {
+#pragma clang fp contract(off)
+    const float gx = th[0] * X + th[1] * Y + th[2];
+    const float gy = th[3] * X + th[4] * Y + th[5];
+    ix = ((gx + 1.f) * (float)nx - 1.f) * 0.5f;
+    iy = ((gy + 1.f) * (float)ny - 1.f) * 0.5f;
 }
 
 struct HoloArgs {
@@ -317,8 +337,8 @@ template <int NX, bool GRAD> __global__ __launch_bounds__(256) void holo_k3(Holo
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
         const float X = base_coord(t + j * LG::TPR, NX);
-        float ix = (((th[0] * X + th[1] * Y + th[2]) + 1.f) * (float)NX - 1.f) * 0.5f;
-        float iy = (((th[3] * X + th[4] * Y + th[5]) + 1.f) * (float)ny - 1.f) * 0.5f;
+        float ix, iy;
+        affine_coords(th, X, Y, NX, ny, ix, iy);
         ix = fminf(fmaxf(ix, 0.f), (float)(NX - 1));
         iy = fminf(fmaxf(iy, 0.f), (float)(ny - 1));
         const int x0 = (int)floorf(ix), y0 = (int)floorf(iy);
@@ -335,10 +355,8 @@ template <int NX, bool GRAD> __global__ __launch_bounds__(256) void holo_k3(Holo
     for (int j = 0; j < PPT; ++j) {
         const int x = t + j * LG::TPR;
         const float X = base_coord(x, NX);
-        const float gx = th[0] * X + th[1] * Y + th[2];
-        const float gy = th[3] * X + th[4] * Y + th[5];
-        float ix = ((gx + 1.f) * (float)NX - 1.f) * 0.5f;
-        float iy = ((gy + 1.f) * (float)ny - 1.f) * 0.5f;
+        float ix, iy;
+        affine_coords(th, X, Y, NX, ny, ix, iy);
         const float mx = (ix > 0.f && ix < (float)(NX - 1)) ? 1.f : 0.f;     // grid_sampler's clip_coordinates_set_grad
         const float my = (iy > 0.f && iy < (float)(ny - 1)) ? 1.f : 0.f;
         ix = fminf(fmaxf(ix, 0.f), (float)(NX - 1));
@@ -487,7 +505,7 @@ __device__ __forceinline__ void holo_sum_one(const HoloArgs& A, bool grad, int o
             }
         }
         else if (q < 7) A.grad_affine[d * 6 + q - 1] = (A.set_obj ? 0.f : A.grad_affine[d * 6 + q - 1]) + s;
-        else A.grad_dists[d] = (A.set_obj ? 0.f : A.grad_dists[d]) + 1e7f * s;
+        else A.grad_dists[d] = (A.set_obj ? 0.f : A.grad_dists[d]) + mul_rounded(1e7f, s);
     }
 }
 __global__ __launch_bounds__(64) void holo_sums_kernel(HoloArgs A) { holo_sum_one<false>(A, false, blockIdx.x); }
@@ -545,8 +563,8 @@ template <int NX, bool FUSE> __global__ __launch_bounds__(256) void holo_k5(Holo
             } else {
                 const cf pm = cmul(p, c);                  // post-modulation field psi'
                 const float wre = g.x * pm.x + g.y * pm.y, wim = g.x * pm.y - g.y * pm.x;     // w = conj(G) psi'
-                go.y += -A.k1 * wre;                       // d/dbeta
-                go.x += A.sigma * A.k1 * wim;              // d/ddelta
+                go.y += mul_rounded(-A.k1, wre);           // d/dbeta
+                go.x += mul_rounded(A.sigma * A.k1, wim);  // d/ddelta
             }
             if (FUSE) {
                 // the object's Adam step on the gradient just formed (channels 2 i and 2 i + 1 of the flat object array)
