@@ -238,6 +238,91 @@ __global__ __launch_bounds__(256) void rotate_adj_csr_kernel(const float2* __res
 // memory access pattern no longer depends on the angle (the direct gather is 10x slower at 45 degrees than at 0).
 // lsrc[j] = (z' - box.z0) * box.w + (x' - box.x0) of CSR entry j.
 #define ADM_STAGE_MAX 1024          // float2 elements per plane in LDS when four planes are staged at once
+// The staged kernels are bound by memory latency, not by the bytes they move: a block's work is a chain of dependent round trips
+// (tables -> box -> CSR entries -> gradient), so each link issues all of its loads before it uses the first.
+// Planes [0, NPL) of a box go to stage[p * pitch + rem], rem = z * bw + x inside the box: RB elements x NPL planes are loaded
+// (one division per element, serving its NPL planes) before the first LDS store.  Nothing is branched around, or the compiler
+// sinks the loads to their stores, one wait each: a plane at or past `nvalid` is staged as a copy of the last valid one (its
+// sums are formed and never stored), and a thread past the box's end loads and stores the box's last element once more.
+template <int NPL, int RB>
+__device__ __forceinline__ void stage_box(float2* __restrict__ stage, const float2* __restrict__ box0, int Xp, size_t slice, int bw, int per,
+                                          int pitch, int nvalid) {
+    for (int r0 = threadIdx.x; r0 < per; r0 += 256 * RB) {
+        float2 v[RB][NPL];
+#pragma unroll
+        for (int b = 0; b < RB; ++b) {
+            const int rem = min(r0 + 256 * b, per - 1);
+            const int zz = rem / bw, xx = rem - zz * bw;
+            const float2* q = box0 + (size_t)zz * slice + xx;
+#pragma unroll
+            for (int p = 0; p < NPL; ++p) v[b][p] = q[(size_t)min(p, nvalid - 1) * Xp];
+        }
+#pragma unroll
+        for (int b = 0; b < RB; ++b) {
+            const int rem = min(r0 + 256 * b, per - 1);
+#pragma unroll
+            for (int p = 0; p < NPL; ++p) stage[p * pitch + rem] = v[b][p];
+        }
+    }
+}
+
+// weights and LDS offsets of entries [j, j + 8) of a CSR row that ends at `end`: sixteen loads in flight (entries past the end repeat
+// the last one and are left out by gather_row; an empty row reads entry 0)
+__device__ __forceinline__ void load_row8(const float* __restrict__ wgt, const unsigned short* __restrict__ lsrc, int j, int end, float* w,
+                                          int* q) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int jj = max(min(j + u, end - 1), 0);
+        w[u] = wgt[jj];
+        q[u] = lsrc[jj];
+    }
+}
+
+// a[i] = fma(w, v, a[i]) for four entries of which the first n exist, planes [0, ny) (ny is uniform).  An entry that does not exist
+// leaves a[i] as it is: a zero weight in its place would turn a sum of -0 into +0.  Its LDS read is made all the same (its offset
+// is the row's last, a valid one): the empty asm statements pin all sixteen reads ahead of the first select, where the compiler
+// would otherwise sink each read to its own branch and wait there.
+__device__ __forceinline__ void gather4(const float2* __restrict__ stage, float2* a, const float* w, const int* q, int n, int ny) {
+    float2 v[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < ny) v[u][i] = stage[i * ADM_STAGE_MAX + q[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < ny) asm volatile("" ::"v"(v[u][i].x), "v"(v[u][i].y));
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i < ny) {
+                const float ax = __builtin_fmaf(w[u], v[u][i].x, a[i].x), ay = __builtin_fmaf(w[u], v[u][i].y, a[i].y);
+                a[i].x = (u < n) ? ax : a[i].x;
+                a[i].y = (u < n) ? ay : a[i].y;
+            }
+        }
+    }
+}
+
+// the bilinear-transpose gather of one voxel out of a staged interior box: every entry of its CSR row [beg, end) in CSR order, from
+// zero, one fused multiply-add each.  w, q: load_row8 of (beg, end), issued by the caller ahead of the staging so that a row of up
+// to eight entries (all but the rim's) costs no round trip of its own
+__device__ __forceinline__ void gather_row(const float2* __restrict__ stage, const float* __restrict__ wgt,
+                                           const unsigned short* __restrict__ lsrc, int beg, int end, float* w, int* q, float2* a, int ny) {
+    int j = beg;
+    while (j < end) {
+        gather4(stage, a, w, q, end - j, ny);
+        if (j + 4 < end) gather4(stage, a, w + 4, q + 4, end - j - 4, ny);
+        j += 8;
+        if (j < end) load_row8(wgt, lsrc, j, end, w, q);
+    }
+}
+
 __global__ __launch_bounds__(256) void rotate_adj_staged_kernel(const float2* __restrict__ grot, const int* __restrict__ ptr,
                                                                 const int* __restrict__ src, const unsigned short* __restrict__ lsrc,
                                                                 const float* __restrict__ wgt,
@@ -275,42 +360,37 @@ __global__ __launch_bounds__(256) void rotate_adj_staged_kernel(const float2* __
             if (i < ny) { float2 c = o[(size_t)i * plane]; c.x += a[i].x; c.y += a[i].y; o[(size_t)i * plane] = c; }
         return;
     }
+    // the four read-modify-write targets and the first eight entries of the voxel's CSR row travel together with the box: nothing
+    // below waits for a load that could have been issued here (a thread outside the object, or a plane past ny, reads a valid
+    // address and drops it)
+    const float2* oc = gobj + (size_t)y0 * plane + t;
+    float2 c[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = oc[(size_t)min(i, ny - 1) * plane];
+    const float2* box0 = grot + (size_t)box.y * slice + (size_t)(g.pad_y0 + y0) * g.Xp + g.pad_x0 + box.x;
     if (per <= ADM_STAGE_MAX) {
         // interior patch: the boxes of four y planes fit at once
-        for (int idx = threadIdx.x; idx < 4 * per; idx += 256) {
-            const int p = idx / per, rem = idx - p * per;
-            const int zz = rem / bw, xx = rem - zz * bw;
-            float2 v = make_float2(0.f, 0.f);
-            if (p < ny) v = grot[(size_t)(box.y + zz) * slice + (size_t)(g.pad_y0 + y0 + p) * g.Xp + g.pad_x0 + box.x + xx];
-            stage[p * ADM_STAGE_MAX + rem] = v;
-        }
+        float w[8];
+        int q[8];
+        load_row8(wgt, lsrc, beg, end, w, q);
+        stage_box<4, 2>(stage, box0, g.Xp, slice, bw, per, ADM_STAGE_MAX, ny);
         __syncthreads();
         if (!ok) return;
         float2 a[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) a[i] = make_float2(0.f, 0.f);
-        for (int j = beg; j < end; ++j) {
-            const float w = wgt[j];
-            const int q = lsrc[j];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { const float2 v = stage[i * ADM_STAGE_MAX + q]; a[i].x += w * v.x; a[i].y += w * v.y; }
-        }
+        gather_row(stage, wgt, lsrc, beg, end, w, q, a, 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            if (i < ny) { float2 c = o[(size_t)i * plane]; c.x += a[i].x; c.y += a[i].y; o[(size_t)i * plane] = c; }
+            if (i < ny) { c[i].x += a[i].x; c[i].y += a[i].y; o[(size_t)i * plane] = c[i]; }
         return;
     }
     // rim patch (border clamping folds a corner of the rotated frame onto it: box of up to 4096 voxels): one or two planes
     // per pass over the CSR entries, whatever fits the 32 KB stage
     const int npp = (2 * per <= 4 * ADM_STAGE_MAX) ? 2 : 1;
     for (int p0 = 0; p0 < ny; p0 += npp) {
-        for (int idx = threadIdx.x; idx < npp * per; idx += 256) {
-            const int pp = idx / per, rem = idx - pp * per;
-            const int zz = rem / bw, xx = rem - zz * bw;
-            float2 v = make_float2(0.f, 0.f);
-            if (p0 + pp < ny) v = grot[(size_t)(box.y + zz) * slice + (size_t)(g.pad_y0 + y0 + p0 + pp) * g.Xp + g.pad_x0 + box.x + xx];
-            stage[idx] = v;
-        }
+        if (npp == 2) stage_box<2, 4>(stage, box0 + (size_t)p0 * g.Xp, g.Xp, slice, bw, per, per, ny - p0);
+        else stage_box<1, 8>(stage, box0 + (size_t)p0 * g.Xp, g.Xp, slice, bw, per, per, 1);
         __syncthreads();
         if (ok) {
             float2 acc0 = make_float2(0.f, 0.f), acc1 = make_float2(0.f, 0.f);
@@ -332,15 +412,11 @@ __global__ __launch_bounds__(256) void rotate_adj_staged_kernel(const float2* __
                     acc1.x += w[u] * v1.x; acc1.y += w[u] * v1.y;
                 }
             }
-            float2 c = o[(size_t)p0 * plane];
-            c.x += acc0.x;
-            c.y += acc0.y;
-            o[(size_t)p0 * plane] = c;
-            if (npp == 2 && p0 + 1 < ny) {
-                float2 d = o[(size_t)(p0 + 1) * plane];
-                d.x += acc1.x;
-                d.y += acc1.y;
-                o[(size_t)(p0 + 1) * plane] = d;
+            // (p0 is uniform: the static indices below keep c[] in registers)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i == p0) { c[i].x += acc0.x; c[i].y += acc0.y; o[(size_t)i * plane] = c[i]; }
+                if (npp == 2 && i == p0 + 1 && i < ny) { c[i].x += acc1.x; c[i].y += acc1.y; o[(size_t)i * plane] = c[i]; }
             }
         }
         __syncthreads();
@@ -375,13 +451,24 @@ __global__ __launch_bounds__(256) void rotate_adj_staged_stack_kernel(const floa
     float2* o = (part ? part + (size_t)r_lo * Yb * plane : gobj) + (size_t)y0 * plane + (size_t)x * g.Z + z;
     float2 c[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = (ok && i < ny && !part) ? o[(size_t)i * plane] : make_float2(0.f, 0.f);
+    for (int i = 0; i < 4; ++i) c[i] = make_float2(0.f, 0.f);
+    if (!part) {
+        // all four loads in flight at once: a thread outside the object, or a plane past ny, reads a valid address and drops it
+        const float2* oc = gobj + (size_t)y0 * plane + t;
+        float2 l[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) l[i] = oc[(size_t)min(i, ny - 1) * plane];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (ok && i < ny) c[i] = l[i];
+    }
     for (int r = r_lo; r < r_hi; ++r) {
         const AdjTables T = tabs[r];
         const int4 box = T.boxes[blockIdx.y * gridDim.x + blockIdx.x];      // (x0, z0, w, h)
         const int ys = r * Yb + y0;                     // the same planes in block r of the stacked image
         const int bw = box.z, bh = box.w, per = bw * bh;
         const int beg = ok ? T.ptr[t] : 0, end = ok ? T.ptr[t + 1] : 0;
+        const float2* box0 = grot + (size_t)box.y * slice + (size_t)(g.pad_y0 + ys) * g.Xp + g.pad_x0 + box.x;
         if (bw == 0) {
             const size_t row = (size_t)(g.pad_y0 + ys) * g.Xp;
             float2 a[4];
@@ -397,36 +484,24 @@ __global__ __launch_bounds__(256) void rotate_adj_staged_stack_kernel(const floa
 #pragma unroll
             for (int i = 0; i < 4; ++i) { c[i].x += a[i].x; c[i].y += a[i].y; }
         } else if (per <= ADM_STAGE_MAX) {
-            for (int idx = threadIdx.x; idx < npl * per; idx += 256) {
-                const int p = idx / per, rem = idx - p * per;
-                const int zz = rem / bw, xx = rem - zz * bw;
-                float2 v = make_float2(0.f, 0.f);
-                if (p < ny) v = grot[(size_t)(box.y + zz) * slice + (size_t)(g.pad_y0 + ys + p) * g.Xp + g.pad_x0 + box.x + xx];
-                stage[p * ADM_STAGE_MAX + rem] = v;
-            }
+            float w[8];
+            int q[8];
+            load_row8(T.wgt, T.lsrc, beg, end, w, q);                       // ahead of the staging: see rotate_adj_staged_kernel
+            if (npl == 4) stage_box<4, 2>(stage, box0, g.Xp, slice, bw, per, ADM_STAGE_MAX, ny);
+            else if (npl == 2) stage_box<2, 4>(stage, box0, g.Xp, slice, bw, per, ADM_STAGE_MAX, ny);
+            else stage_box<1, 8>(stage, box0, g.Xp, slice, bw, per, ADM_STAGE_MAX, 1);
             __syncthreads();
             float2 a[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) a[i] = make_float2(0.f, 0.f);
-            for (int j = beg; j < end; ++j) {
-                const float w = T.wgt[j];
-                const int q = T.lsrc[j];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (i < ny) { const float2 v = stage[i * ADM_STAGE_MAX + q]; a[i].x += w * v.x; a[i].y += w * v.y; }
-            }
+            gather_row(stage, T.wgt, T.lsrc, beg, end, w, q, a, ny);
 #pragma unroll
             for (int i = 0; i < 4; ++i) { c[i].x += a[i].x; c[i].y += a[i].y; }
         } else {
             const int npp = (npl >= 2 && 2 * per <= 4 * ADM_STAGE_MAX) ? 2 : 1;
             for (int p0 = 0; p0 < ny; p0 += npp) {
-                for (int idx = threadIdx.x; idx < npp * per; idx += 256) {
-                    const int pp = idx / per, rem = idx - pp * per;
-                    const int zz = rem / bw, xx = rem - zz * bw;
-                    float2 v = make_float2(0.f, 0.f);
-                    if (p0 + pp < ny) v = grot[(size_t)(box.y + zz) * slice + (size_t)(g.pad_y0 + ys + p0 + pp) * g.Xp + g.pad_x0 + box.x + xx];
-                    stage[idx] = v;
-                }
+                if (npp == 2) stage_box<2, 4>(stage, box0 + (size_t)p0 * g.Xp, g.Xp, slice, bw, per, per, ny - p0);
+                else stage_box<1, 8>(stage, box0 + (size_t)p0 * g.Xp, g.Xp, slice, bw, per, per, 1);
                 __syncthreads();
                 float2 acc0 = make_float2(0.f, 0.f), acc1 = make_float2(0.f, 0.f);
                 const int second = (npp == 2) ? per : 0;
