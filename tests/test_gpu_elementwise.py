@@ -19,6 +19,8 @@ kernels.  The whole module takes a few seconds.
 import numpy as np
 import pytest
 
+from tests.ew_matrix import block_sum_mirror, center_rows_mirror          # noqa: F401 (the mirrors of block_sum_f32's order)
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 1), (3, 4, 5), (2, 3, 96), (2, 2, 200)]
@@ -232,34 +234,6 @@ def test_real_imag_unit_weights_are_the_unweighted_l1(ctx, plans, shape, alphas)
 
 
 # ---- the drift guard ----------------------------------------------------------------------------------------------------------
-def block_sum_mirror(v, descending=False):
-    """block_sum_f32 of 256 per-thread float32 values: inside each wave of 64 lanes v[l] += v[l + off] for off = 32 ... 1 (lane 0
-    ends with the wave's sum), then the wave sums one by one, ascending (descending: the order the kernel must NOT use)."""
-    v = np.array(v, np.float32).reshape(4, 64)
-    for off in (32, 16, 8, 4, 2, 1):
-        v[:, :off] = v[:, :off] + v[:, off:2 * off]
-    red = v[:, 0][::-1] if descending else v[:, 0]
-    t = red[0]
-    for w in range(1, 4):
-        t = np.float32(t + red[w])
-    return t
-
-
-def center_rows_mirror(x, descending=False):
-    x = np.array(x, np.float32)
-    n_rows, n_cols = x.shape
-    per = -(-n_rows // 256)
-    for c in range(n_cols):
-        col = np.zeros(per * 256, np.float32)
-        col[:n_rows] = x[:, c]
-        acc = np.zeros(256, np.float32)
-        for j in range(per):                           # thread t adds the rows t, t + 256, ... in this order (+0 where it has none)
-            acc = acc + col[j * 256:(j + 1) * 256]
-        mu = np.float32(block_sum_mirror(acc, descending) / np.float32(n_rows))
-        x[:, c] = x[:, c] - mu
-    return x
-
-
 @pytest.mark.parametrize('n_cols', [1, 2, 3])
 @pytest.mark.parametrize('n_rows', [1, 63, 64, 257, 1000])
 def test_center_rows_is_the_mirrored_sum(ctx, n_rows, n_cols):
