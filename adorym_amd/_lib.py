@@ -121,6 +121,8 @@ SIGNATURES = {
     'adm_rotation_table_build': (_I, [_VP, _I, _I, C.c_float, C.c_float, _VP]),
     'adm_rotation_csr_scratch_bytes': (_SZ, [_VP]),
     'adm_rotation_csr_build': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    'adm_project_z': (_I, [_VP, _VP, _I, _I, _VP]),
+    'adm_project_z_adj': (_I, [_VP, _VP, _I, _I, _VP]),
     'adm_multislice_fwd_adj': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _SZ]),
     'adm_plan_set_transmission_cache': (_I, [_VP, _I]),
     'adm_transmission_refresh': (_I, [_VP, _VP, _I, _I]),

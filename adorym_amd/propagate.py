@@ -759,6 +759,85 @@ class MultisliceEngine(object):
         return self.loss()
 
 
+class ProjectionEngine(object):
+    """
+    The projection approximation (``pure_projection=True``, adorym/propagate.py:158-193; unknown_type 'delta_beta'): the rotated
+    object is summed along the beam and the probe is multiplied ONCE by exp(-k1 sum(beta)) (cos, sin)(-sigma k1 sum(delta)) -- the
+    multislice problem of an object with one slice, no propagation inside the sample:
+
+      obj [Y,X,Z,2] --adm_rotate_fwd--> obj_rot [Z][Yp][Xp][2] --adm_project_z--> [1][Yp][Xp][2] --adm_multislice_fwd_adj (one slice)-->
+      [1][Yp][Xp][2] --adm_project_z_adj--> grad_rot [Z][Yp][Xp][2] --adm_rotate_adj--> grad_obj [Y,X,Z,2]
+
+    Two engines built from the same positions, so that their pads agree: ``volume`` (obj_size; rotations, the [Z] buffers, and the
+    ``plan`` that regularisers and rotation tables ask for) and ``slab`` (Y, X, 1), which launches nothing but the one-slice problem.
+    ``rotate`` and ``rotate_adjoint`` are the two-stage forms above; every other method and attribute a caller uses on a
+    MultisliceEngine -- set_batch, multislice, accumulate_tiles, the losses, predictions, probe and shift gradients, ``streamed`` --
+    is the slab's, looked up there.  ``binning`` has no effect on this model (the reference ignores it): accepted and dropped.
+
+    Neither engine caches transmissions.  The volume's cache would hold exp() of single voxels, which nobody reads (the sum needs the
+    rotated (delta, beta)).  The slab's would have to be refreshed after every projection (adm_transmission_refresh: one more launch
+    per minibatch, and a [Yp][Xp] image written and read again) to save one exp and one sincos per tile pixel in a kernel that then
+    spends a 2-D transform on that pixel; with and without the cache the kernel gives the same bits.
+    """
+
+    def __init__(self, ctx, obj_size, probe_size, probe_pos, energy_ev, psize_cm, **kw):
+        for name, why in (('slice_pos_cm', 'sparse multislice'), ('exit_shift', 'per-angle projection alignment')):
+            if kw.get(name) is not None and kw.get(name) is not False:
+                raise NotImplementedError('ProjectionEngine: %s (%s) with the projection approximation is not implemented' % (name, why))
+        if kw.get('unknown_type', 'delta_beta') != 'delta_beta':
+            raise NotImplementedError("ProjectionEngine: unknown_type='%s' (the reference multiplies real and imaginary parts channel by "
+                                      "channel there) is not implemented" % kw['unknown_type'])
+        fp = kw.get('free_prop_cm', 'inf')
+        if not isinstance(fp, str) and np.ndim(fp) > 0 and np.size(fp) > 1:
+            raise NotImplementedError('ProjectionEngine: a sequence of detector distances (multi-distance data) is not implemented')
+        for name in ('binning', 'transmission_cache', 'transmissions_only'):
+            kw.pop(name, None)
+        self.ctx = ctx
+        self.obj_size = tuple(int(v) for v in obj_size)
+        Y, X, _ = self.obj_size
+        self.slab = MultisliceEngine(ctx, (Y, X, 1), probe_size, probe_pos, energy_ev, psize_cm, transmission_cache=False, **kw)
+        self.volume = MultisliceEngine(ctx, self.obj_size, probe_size, probe_pos, energy_ev, psize_cm, free_prop_cm=0, streamed='auto',
+                                       scale_ri_by_k=kw.get('scale_ri_by_k', True), transmission_cache=False)
+        if self.volume.plan.rot_shape[1:] != self.slab.plan.rot_shape[1:] or self.volume.plan.pads != self.slab.plan.pads:
+            raise RuntimeError('ProjectionEngine: the padded frames of the two plans differ')
+        self.plan = self.volume.plan
+        self.obj_rot, self.grad_rot = self.volume.obj_rot, self.volume.grad_rot
+
+    def __getattr__(self, name):
+        # (only reached for names this object does not have: the one-slice engine's)
+        if name in ('slab', 'volume'):
+            raise AttributeError(name)
+        return getattr(self.slab, name)
+
+    def rotate(self, obj, coords, y_range=None):
+        """Rotate the rows, then sum them along the beam into the slab's rotated object."""
+        lo, hi = y_range if y_range is not None else (0, self.obj_size[0])
+        self.volume.rotate(obj, coords, (lo, hi))
+        check(self.ctx.lib.adm_project_z(self.plan.handle, self.obj_rot.ptr, lo, hi, self.slab.obj_rot.ptr))
+
+    def rotate_adjoint(self, grad_obj, coords, y_range=None):
+        """grad_obj += R^T (the slab's overlap-added gradient, copied to every slice)."""
+        lo, hi = y_range if y_range is not None else (0, self.obj_size[0])
+        check(self.ctx.lib.adm_project_z_adj(self.plan.handle, self.slab.grad_rot.ptr, lo, hi, self.grad_rot.ptr))
+        self.volume.rotate_adjoint(grad_obj, coords, (lo, hi))
+
+    def cacheless_plan(self):
+        return self.plan
+
+    def close(self):
+        self.slab.plan.close()
+        self.volume.plan.close()
+
+    def loss_and_grad(self, obj, grad_obj, coords, probe, pos_batch, target, grad_probe=None, footprint=True):
+        """One minibatch: grad_obj += d loss / d obj; returns the (host) loss."""
+        self.slab.set_batch(pos_batch, target)
+        yr = self.slab.y_footprint(pos_batch)
+        self.rotate(obj, coords, yr if footprint else None)
+        self.slab.multislice(probe, grad_probe=grad_probe)
+        self.rotate_adjoint(grad_obj, coords, yr)
+        return self.slab.loss()
+
+
 class AngleBatch(object):
     """R rotation angles of an UNDIVIDED full-field dataset evaluated in one multislice launch (BASELINE config 2's "minibatch
     16": the reference forces minibatch_size = 1 for such data, adorym/ptychography.py:342-346, so 16 in flight are 16 ranks
@@ -773,6 +852,9 @@ class AngleBatch(object):
     on one stream.  Same sums as R separate evaluations accumulated into one buffer, in the same order per voxel."""
 
     def __init__(self, ctx, obj_size, probe_size, n_angles, energy_ev, psize_cm, probe_pos=(0, 0), **engine_kwargs):
+        if engine_kwargs.pop('pure_projection', False):
+            raise NotImplementedError('AngleBatch: pure_projection (the projection approximation, ProjectionEngine) on the stacked '
+                                      'geometry of a full-field angle batch is not implemented')
         self.ctx = ctx
         self.obj_size = tuple(int(v) for v in obj_size)
         self.R = int(n_angles)

@@ -34,7 +34,7 @@ from .differentiator import Differentiator
 from .dp import DataParallelObject, HipOps, constraint_flags
 from .forward_model import PtychographyModel, MultiDistModel, SparseMultisliceModel
 from .optimizers import Optimizer, AdamOptimizer, GDOptimizer, MomentumOptimizer, apply_small_params, plain_adam
-from .propagate import MultisliceEngine, RotationTable, get_kernel
+from .propagate import MultisliceEngine, ProjectionEngine, RotationTable, get_kernel
 from .regularizers import L1Regularizer, TVRegularizer, ReweightedL1Regularizer, combined_weights
 from ._io import DataFile, write_tiff, read_tiff
 
@@ -348,7 +348,14 @@ class _Run(object):
             _not_implemented(self.object_type != 'normal', "object_type='%s' with unknown_type='real_imag'" % self.object_type)
             _not_implemented(self.binning != 1, "binning > 1 with unknown_type='real_imag'")
         _not_implemented(self.multiscale_level != 1, 'multiscale_level > 1')
-        _not_implemented(self.pure_projection or self.forward_algorithm != 'fresnel', 'pure_projection / CTF forward algorithm')
+        _not_implemented(self.forward_algorithm != 'fresnel', "forward_algorithm='%s'" % (self.forward_algorithm,))
+        if self.pure_projection:
+            # the projection approximation (ProjectionEngine): delta_beta unknowns summed along the beam, rotated inside the loop
+            # (the ones that need the data's shape -- sparse multislice, multi-distance data: read_data)
+            _not_implemented(self.unknown_type == 'real_imag', "pure_projection with unknown_type='real_imag'")
+            _not_implemented(self.is_minus_logged, 'pure_projection with is_minus_logged')
+            _not_implemented(bool(self.optimize_prj_pos_offset), 'pure_projection with optimize_prj_pos_offset')
+            _not_implemented(bool(self.rotate_out_of_loop), 'pure_projection with rotate_out_of_loop')
         _not_implemented(self.use_epie, 'ePIE')
         _not_implemented(self.is_minus_logged, 'is_minus_logged')
         _not_implemented(not self.common_probe_pos, 'common_probe_pos=False')
@@ -418,6 +425,8 @@ class _Run(object):
             self.free_prop_cm = self.f.get('metadata/free_prop_cm')
         self.is_multi_dist = np.array(self.free_prop_cm).size != 1          # ptychography.py:296-305
         _not_implemented(self.is_sparse_multislice and self.is_multi_dist, 'sparse multislice (slice_pos_cm_ls) with multi-distance data')
+        _not_implemented(self.pure_projection and self.is_sparse_multislice, 'pure_projection with sparse multislice (slice_pos_cm_ls)')
+        _not_implemented(self.pure_projection and self.is_multi_dist, 'pure_projection with multi-distance data')
         if self.optimize_prj_pos_offset:
             # per-angle projection alignment (ptychography.py:706, forward_model.py:255-256): the exit wave is shifted by the detector
             # step of the streamed kernels, which take one probe set for all positions and one transfer function for all gaps
@@ -510,7 +519,10 @@ class _Run(object):
             self.engine = MultisliceEngine(ctx, obj_size, (8, 8), np.zeros((1, 2), int), self.energy_ev, self.psize_cm, free_prop_cm=0,
                                            max_batch=1, unknown_type=self.unknown_type)
         else:
-            self.engine = MultisliceEngine(
+            # the projection approximation sums the object along the beam and runs the one-slice problem; an object that HAS one
+            # slice is that problem already (the sum of one slice is the slice) and takes the ordinary engine
+            cls = ProjectionEngine if (self.pure_projection and obj_size[2] > 1) else MultisliceEngine
+            self.engine = cls(
                 ctx, obj_size, probe_size, self.probe_pos_int, self.energy_ev, self.psize_cm, free_prop_cm=self.free_prop_cm,
                 binning=self.binning, fresnel_approx=self.fresnel_approx, normalize_fft=self.normalize_fft, kernel=self.h,
                 n_probe_modes=self.n_probe_modes, max_batch=self.minibatch_size, loss_function_type=self.loss_function_type,
@@ -622,7 +634,8 @@ class _Run(object):
         ctx, unknown_type = self.ctx, self.unknown_type
         common_vars = dict(unknown_type=unknown_type, normalize_fft=self.normalize_fft, sign_convention=self.sign_convention,
                            rotate_out_of_loop=self.rotate_out_of_loop, scale_ri_by_k=self.scale_ri_by_k, is_minus_logged=self.is_minus_logged,
-                           forward_algorithm=self.forward_algorithm, stdout_options=self.stdout_options, poisson_multiplier=self.poisson_multiplier,
+                           forward_algorithm=self.forward_algorithm, pure_projection=bool(self.pure_projection),
+                           stdout_options=self.stdout_options, poisson_multiplier=self.poisson_multiplier,
                            common_probe_pos=self.common_probe_pos, binning=self.binning, prj=self.prj, engine=self.engine,
                            holo_engine=self.holo_engine, tile_engine=self.tile_engine, safe_zone_width=self.safe_zone_width,
                            n_dp_batch=self.n_dp_batch, optimize_prj_affine=self.optimize_prj_affine, optimize_free_prop=self.optimize_free_prop,

@@ -285,6 +285,22 @@ size_t adm_rotation_csr_scratch_bytes(const adm_plan* plan);
 int adm_rotation_csr_build(adm_plan* plan, const uint16_t* coords, int32_t* csr_ptr, int32_t* csr_src, uint16_t* csr_lsrc,
                            float* csr_w, int32_t* boxes, void* scratch, size_t scratch_bytes);
 
+/* ---- projection approximation (pure_projection=True, adorym/propagate.py:158-193) -------------------------------
+ * The reference sums the rotated object along the beam (w.sum(grid_batch, axis=-2)) and multiplies the probe ONCE by
+ * exp(-k1 sum(beta)) (cos, sin)(-sigma k1 sum(delta)): the multislice problem of an object with one slice, whose slice is the sum.
+ * adm_project_z forms that slice from the rotated object of a plan with obj_z = Z slices:
+ *   obj_rot device [Z][Yp][Xp][2] (the plan's rotated-frame layout), proj device [1][Yp][Xp][2] (the same padded frame, one slice:
+ *   the obj_rot of a plan created for (obj_y, obj_x, 1) with the same pads).
+ * For the object rows y_lo <= y < y_hi every column of the padded row -- x pads included -- is written with
+ * round_fp32(sum over z of obj_rot[z]), the sum accumulated in double in an order fixed by the arguments (no atomics: the same
+ * call gives the same bits); rows outside the range and the y pads of proj are not touched.
+ * adm_project_z_adj is the transpose: the rows [y_lo, y_hi) of grad_proj [1][Yp][Xp][2] are copied into each of the Z slices of
+ * grad_rot [Z][Yp][Xp][2]; everything else in grad_rot is left alone.
+ * Both are asynchronous on the context's stream; a null pointer or a range outside 0 <= y_lo <= y_hi <= obj_y is ADM_ERR_INVALID.
+ * A plan that caches transmissions does not learn of a proj written here: refresh it (adm_transmission_refresh) or leave its cache off. */
+int adm_project_z(adm_plan* plan, const float* obj_rot, int y_lo, int y_hi, float* proj);
+int adm_project_z_adj(adm_plan* plan, const float* grad_proj, int y_lo, int y_hi, float* grad_rot);
+
 /* ---- R3,R5-R8,R10  multislice forward + loss + adjoint ------------------------------
  * Replaces, for one minibatch of `batch` probe positions of one rotation angle:
  *   tile extraction            adorym/forward_model.py:313-331
