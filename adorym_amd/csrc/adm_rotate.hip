@@ -279,16 +279,19 @@ __device__ __forceinline__ void load_row8(const float* __restrict__ wgt, const u
 }
 
 // a[i] = fma(w, v, a[i]) for four entries of which the first n exist, planes [0, ny) (ny is uniform).  An entry that does not exist
-// leaves a[i] as it is: a zero weight in its place would turn a sum of -0 into +0.  Its LDS read is made all the same (its offset
-// is the row's last, a valid one): the empty asm statements pin all sixteen reads ahead of the first select, where the compiler
-// would otherwise sink each read to its own branch and wait there.
+// leaves a[i] as it is: a zero weight in its place would turn a sum of -0 into +0.  Its LDS read is made all the same: the empty asm
+// statements pin all sixteen reads ahead of the first select, where the compiler would otherwise sink each read to its own branch
+// and wait there.  It reads stage[threadIdx.x], whatever that holds (on a small box LDS this block never wrote: intended, the
+// select drops the value), and not the row's last offset once more: near the axes a row
+// has one or two entries and a wave's offsets lie a box row apart, so every repeated read would queue on the same few LDS banks
+// (0 rad, 256^3: 55 us per launch against 41 with four reads per entry that exists); consecutive lanes share no bank.
 __device__ __forceinline__ void gather4(const float2* __restrict__ stage, float2* a, const float* w, const int* q, int n, int ny) {
     float2 v[4][4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            if (i < ny) v[u][i] = stage[i * ADM_STAGE_MAX + q[u]];
+            if (i < ny) v[u][i] = stage[i * ADM_STAGE_MAX + ((u < n) ? q[u] : (int)threadIdx.x)];
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -323,24 +326,95 @@ __device__ __forceinline__ void gather_row(const float2* __restrict__ stage, con
     }
 }
 
+// weights and LDS offsets of entries [j, j + 4) of a rim voxel's CSR row that ends at `end`; an entry past the end repeats the last
+// one (an empty row reads entry 0).  No branch and no select here: either would be where the compiler waits for the load
+__device__ __forceinline__ void rim_next4(const float* __restrict__ wgt, const unsigned short* __restrict__ lsrc, int j, int end, float* w,
+                                          int* q) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int jj = max(min(j + u, end - 1), 0);
+        w[u] = wgt[jj];
+        q[u] = lsrc[jj];
+    }
+}
+
+// The staged adjoint's blocks are a 1-D grid walked in dispatch order, and a rim patch's block is a chain several times as long as an interior
+// one's: the launch ends one such chain after the last rim block STARTS.  Rim patches are border patches of the nx x nz patch grid
+// (clamping folds the frame's corner onto the object's edge), so the border ring goes first: slots [0, ring) are the ring, the
+// rest the inside, row by row.  A pure function of the patch grid: nothing per angle, nothing stored.
+__host__ __device__ inline int patch_ring_size(int nx, int nz) { return (nx > 2 && nz > 2) ? 2 * nx + 2 * (nz - 2) : nx * nz; }
+__host__ __device__ inline void ring_patch(int i, int nx, int nz, int& px, int& pz) {      // slot i < ring -> (px, pz)
+    if (nx <= 2 || nz <= 2) {                                    // all border
+        pz = i / nx;
+        px = i - pz * nx;
+    } else if (i < 2 * nx) {                                     // rows z = 0 and z = nz - 1
+        pz = (i < nx) ? 0 : nz - 1;
+        px = (i < nx) ? i : i - nx;
+    } else {                                                     // the two columns between them
+        pz = 1 + ((i - 2 * nx) >> 1);
+        px = ((i - 2 * nx) & 1) ? nx - 1 : 0;
+    }
+}
+__host__ __device__ inline int patch_of_slot(int i, int nx, int nz) {      // -> pz * nx + px
+    const int ring = patch_ring_size(nx, nz);
+    int px, pz;
+    if (i < ring) {
+        ring_patch(i, nx, nz, px, pz);
+    } else {
+        pz = 1 + (i - ring) / (nx - 2);
+        px = 1 + (i - ring) % (nx - 2);
+    }
+    return pz * nx + px;
+}
+
+// Grid (1-D): every ring patch has ADM_RING_SPLIT blocks per group of four planes, every other patch one.  Ring blocks first --
+// plane group slowest, then the part, then the ring slot -- then the inside.  What a ring block does is known once its box is read
+// (the angle's table): part h of a rim patch takes its share of the group's planes, so that no block chains more than that share
+// of the patch's passes; any other ring patch does all four planes in part 0, and its other parts return at once.  (A rim box on
+// a patch that is not on the ring would be walked by its one block, pass after pass.)
+#ifndef ADM_RING_SPLIT
+#define ADM_RING_SPLIT 2
+#endif
+static_assert(ADM_RING_SPLIT == 1 || ADM_RING_SPLIT == 2 || ADM_RING_SPLIT == 4, "a ring patch's blocks share a group of four planes");
 __global__ __launch_bounds__(256) void rotate_adj_staged_kernel(const float2* __restrict__ grot, const int* __restrict__ ptr,
                                                                 const int* __restrict__ src, const unsigned short* __restrict__ lsrc,
                                                                 const float* __restrict__ wgt,
                                                                 const int4* __restrict__ boxes, float2* __restrict__ gobj, RotGeom g,
                                                                 int y_lo, int y_hi) {
     __shared__ float2 stage[4 * ADM_STAGE_MAX];
-    const int4 box = boxes[blockIdx.y * gridDim.x + blockIdx.x];      // (x0, z0, w, h)
-    const int y0 = y_lo + blockIdx.z * 4;
+    const int nx = (g.X + 15) >> 4, nz = (g.Z + 15) >> 4, ngrp = (y_hi - y_lo + 3) >> 2;
+    const int nring = patch_ring_size(nx, nz);
+    int bi = blockIdx.x, slot, half = 0;
+    const bool ring = bi < ADM_RING_SPLIT * nring * ngrp;
+    if (ring) {
+        slot = bi % nring;
+        bi /= nring;
+        half = bi % ADM_RING_SPLIT;
+        bi /= ADM_RING_SPLIT;
+    } else {
+        bi -= ADM_RING_SPLIT * nring * ngrp;
+        const int nin = nx * nz - nring;
+        slot = nring + bi % nin;
+        bi /= nin;
+    }
+    const int patch = patch_of_slot(slot, nx, nz);
+    const int pz = patch / nx, px = patch - pz * nx;
+    const int4 box = boxes[patch];      // (x0, z0, w, h)
+    const int y0 = y_lo + bi * 4;
     const int ny = min(4, y_hi - y0);
     const int bw = box.z, bh = box.w, per = bw * bh;
     const size_t slice = (size_t)g.Yp * g.Xp;
     const size_t plane = (size_t)g.X * g.Z;
     const int lx = threadIdx.x >> 4, lz = threadIdx.x & 15;          // lanes along z, the fastest object axis
-    const int x = blockIdx.x * 16 + lx, z = blockIdx.y * 16 + lz;
+    const int x = px * 16 + lx, z = pz * 16 + lz;
     const bool ok = (x < g.X) && (z < g.Z);
     const int t = ok ? x * g.Z + z : 0;
     const int beg = ok ? ptr[t] : 0, end = ok ? ptr[t + 1] : 0;
     float2* o = gobj + (size_t)y0 * plane + (size_t)x * g.Z + z;
+    // planes [pa, pb) of the group are this block's if the patch is a rim patch
+    const bool rim = per > ADM_STAGE_MAX;
+    const int pa = half * (4 / ADM_RING_SPLIT), pb = ring ? min(ny, pa + 4 / ADM_RING_SPLIT) : ny;
+    if (half && (!rim || pa >= ny)) return;
     if (bw == 0) {
         // no usable box (only for objects much larger than 256^3): gather from global memory
         if (!ok) return;
@@ -360,16 +434,15 @@ __global__ __launch_bounds__(256) void rotate_adj_staged_kernel(const float2* __
             if (i < ny) { float2 c = o[(size_t)i * plane]; c.x += a[i].x; c.y += a[i].y; o[(size_t)i * plane] = c; }
         return;
     }
-    // the four read-modify-write targets and the first eight entries of the voxel's CSR row travel together with the box: nothing
-    // below waits for a load that could have been issued here (a thread outside the object, or a plane past ny, reads a valid
-    // address and drops it)
     const float2* oc = gobj + (size_t)y0 * plane + t;
-    float2 c[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = oc[(size_t)min(i, ny - 1) * plane];
     const float2* box0 = grot + (size_t)box.y * slice + (size_t)(g.pad_y0 + y0) * g.Xp + g.pad_x0 + box.x;
     if (per <= ADM_STAGE_MAX) {
-        // interior patch: the boxes of four y planes fit at once
+        // interior patch: the boxes of four y planes fit at once.  The four read-modify-write targets and the first eight entries
+        // of the voxel's CSR row travel together with the box: nothing below waits for a load that could have been issued here (a
+        // thread outside the object, or a plane past ny, reads a valid address and drops it)
+        float2 c[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[i] = oc[(size_t)min(i, ny - 1) * plane];
         float w[8];
         int q[8];
         load_row8(wgt, lsrc, beg, end, w, q);
@@ -386,38 +459,50 @@ __global__ __launch_bounds__(256) void rotate_adj_staged_kernel(const float2* __
         return;
     }
     // rim patch (border clamping folds a corner of the rotated frame onto it: box of up to 4096 voxels): one or two planes
-    // per pass over the CSR entries, whatever fits the 32 KB stage
+    // per pass over the CSR entries, whatever fits the 32 KB stage.  The row (up to ~115 entries) is walked through a ring of
+    // sixteen entries: the first sixteen travel with the box, and every four slots are reloaded with the entries sixteen further on
+    // as soon as their LDS gathers are issued, ahead of their multiply-adds -- sixteen entries' loads stay in flight behind the
+    // gathers, where a batch of eight used to be loaded, waited for and used before the next was asked for.  The pass's two
+    // read-modify-write targets are asked for behind the barrier and arrive during the walk.
     const int npp = (2 * per <= 4 * ADM_STAGE_MAX) ? 2 : 1;
-    for (int p0 = 0; p0 < ny; p0 += npp) {
-        if (npp == 2) stage_box<2, 4>(stage, box0 + (size_t)p0 * g.Xp, g.Xp, slice, bw, per, per, ny - p0);
+    for (int p0 = pa; p0 < pb; p0 += npp) {
+        float w[16];
+        int q[16];
+        int b0 = beg;       // opaque per pass: hoisted out of this loop, the first sixteen entries would hold 32 registers across the walk
+        asm volatile("" : "+v"(b0));
+#pragma unroll
+        for (int u0 = 0; u0 < 16; u0 += 4) rim_next4(wgt, lsrc, b0 + u0, end, w + u0, q + u0);
+        if (npp == 2) stage_box<2, 4>(stage, box0 + (size_t)p0 * g.Xp, g.Xp, slice, bw, per, per, pb - p0);
         else stage_box<1, 8>(stage, box0 + (size_t)p0 * g.Xp, g.Xp, slice, bw, per, per, 1);
         __syncthreads();
         if (ok) {
+            const bool two = (npp == 2) && (p0 + 1 < pb);
+            float2 c0 = oc[(size_t)p0 * plane], c1 = oc[(size_t)(two ? p0 + 1 : p0) * plane];
             float2 acc0 = make_float2(0.f, 0.f), acc1 = make_float2(0.f, 0.f);
             const int second = (npp == 2) ? per : 0;
-            for (int j = beg; j < end; j += 8) {       // eight entries' weight/offset loads in flight, then the LDS gathers
-                float w[8];
-                int q[8];
+            for (int j = beg; j < end; j += 16) {
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int jj = min(j + u, end - 1);
-                    w[u] = (j + u < end) ? wgt[jj] : 0.f;
-                    q[u] = lsrc[jj];
-                }
+                for (int u0 = 0; u0 < 16; u0 += 4) {
+                    float2 v0[4], v1[4];
+                    float wc[4];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float2 v0 = stage[q[u]];
-                    const float2 v1 = stage[q[u] + second];
-                    acc0.x += w[u] * v0.x; acc0.y += w[u] * v0.y;
-                    acc1.x += w[u] * v1.x; acc1.y += w[u] * v1.y;
+                    for (int u = 0; u < 4; ++u) {
+                        v0[u] = stage[q[u0 + u]];
+                        v1[u] = stage[q[u0 + u] + second];
+                        wc[u] = (j + u0 + u < end) ? w[u0 + u] : 0.f;      // past the row's end: a zero weight on its last entry
+                    }
+                    rim_next4(wgt, lsrc, j + 16 + u0, end, w + u0, q + u0);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        acc0.x += wc[u] * v0[u].x; acc0.y += wc[u] * v0[u].y;
+                        acc1.x += wc[u] * v1[u].x; acc1.y += wc[u] * v1[u].y;
+                    }
+                    __builtin_amdgcn_sched_barrier(0);      // one group of four at a time: merged, the groups' gathers want 200 registers
                 }
             }
-            // (p0 is uniform: the static indices below keep c[] in registers)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (i == p0) { c[i].x += acc0.x; c[i].y += acc0.y; o[(size_t)i * plane] = c[i]; }
-                if (npp == 2 && i == p0 + 1 && i < ny) { c[i].x += acc1.x; c[i].y += acc1.y; o[(size_t)i * plane] = c[i]; }
-            }
+            c0.x += acc0.x; c0.y += acc0.y;
+            o[(size_t)p0 * plane] = c0;
+            if (two) { c1.x += acc1.x; c1.y += acc1.y; o[(size_t)(p0 + 1) * plane] = c1; }
         }
         __syncthreads();
     }
@@ -684,11 +769,20 @@ extern "C" int adm_rotate_adj_staged(adm_plan* plan, const float* grad_rot, cons
     if (y_lo < 0 || y_hi > d.obj_y || y_lo > y_hi) return fail(ADM_ERR_INVALID, "adm_rotate_adj_staged: bad y range");
     if (y_lo == y_hi) return ADM_OK;
     RotGeom g{d.obj_y, d.obj_x, d.obj_z, plan->Yp, plan->Xp, d.pad_y0, d.pad_x0};
-    dim3 grid((d.obj_x + 15) / 16, (d.obj_z + 15) / 16, (y_hi - y_lo + 3) / 4);
-    hipLaunchKernelGGL(rotate_adj_staged_kernel, grid, dim3(256), 0, plan->ctx->stream, (const float2*)grad_rot, csr_ptr, csr_src,
-                       (const unsigned short*)csr_lsrc, csr_w, (const int4*)boxes, (float2*)grad_obj, g, y_lo, y_hi);
+    // one block per (patch, group of four planes), ADM_RING_SPLIT for the patches of the border ring: see rotate_adj_staged_kernel
+    const int nx = (d.obj_x + 15) / 16, nz = (d.obj_z + 15) / 16;
+    const size_t blocks = ((size_t)nx * nz + (ADM_RING_SPLIT - 1) * patch_ring_size(nx, nz)) * ((y_hi - y_lo + 3) / 4);
+    if (blocks > 0x7fffffffu) return fail(ADM_ERR_UNSUPPORTED, "adm_rotate_adj_staged: more than 2^31 blocks");
+    hipLaunchKernelGGL(rotate_adj_staged_kernel, dim3((unsigned)blocks), dim3(256), 0, plan->ctx->stream, (const float2*)grad_rot, csr_ptr,
+                       csr_src, (const unsigned short*)csr_lsrc, csr_w, (const int4*)boxes, (float2*)grad_obj, g, y_lo, y_hi);
     ADM_HIP(hipGetLastError());
     return ADM_OK;
+}
+
+extern "C" int adm_patch_order(int nx, int nz, int32_t* order) {
+    if (nx < 1 || nz < 1 || !order) return fail(ADM_ERR_INVALID, "adm_patch_order: bad argument");
+    for (int i = 0; i < nx * nz; ++i) order[i] = patch_of_slot(i, nx, nz);
+    return patch_ring_size(nx, nz);
 }
 
 #ifndef ADM_STACK_MIN_BLOCKS

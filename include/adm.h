@@ -261,6 +261,10 @@ int adm_rotate_adj_csr(adm_plan* plan, const float* grad_rot, const int32_t* csr
  * patch without a usable box, which gathers through csr_src as adm_rotate_adj_csr does. */
 int adm_rotate_adj_staged(adm_plan* plan, const float* grad_rot, const int32_t* csr_ptr, const int32_t* csr_src,
                           const uint16_t* csr_lsrc, const float* csr_w, const int32_t* boxes, float* grad_obj, int y_lo, int y_hi);
+/* The order in which adm_rotate_adj_staged's blocks take the nx x nz grid of 16 x 16 patches (host only, no device work):
+ * order [nx*nz] = z-patch * nx + x-patch of every slot, the border ring of the grid first (rim patches, the long blocks, lie
+ * there).  Returns the number of ring patches, or a negative error code. */
+int adm_patch_order(int nx, int nz, int32_t* order);
 /* adm_rotate_adj_staged for a plan whose y extent is n_tables stacked blocks (see adm_rotate_fwd_stack): block r of grad_rot is
  * back-rotated with the r-th set of CSR tables and the n_tables contributions are ADDED, r ascending, into the ONE gradient
  * grad_obj [obj_y / n_tables, X, Z, 2] -- the additions n_tables sequential calls would make (`gradient.arr = comm.allreduce(...)`
