@@ -19,13 +19,18 @@
 
 namespace adm {
 
-// Phi at (fy, fx) for the offset s = (s_y, s_x): the argument in fp32, contraction off, as shift_phases (adm_multislice.hip)
-__device__ __forceinline__ cf es_phase(float fy, float fx, float2 s) {
-#pragma clang fp contract(off)
-    const float m2pi = (float)(-2.0 * 3.14159265359);
-    const float arg = m2pi * (fx * s.y + fy * s.x);
+// Phi at spectral element (y, x) for the offset s = (s_y, s_x).  Per-angle alignment exists to recover offsets of tens of pixels:
+// the argument -2 PI (fx s_x + fy s_y) then reaches hundreds of radians (2000 rad at 640 px and an offset beyond the field), where
+// an fp32 argument -- as the reference and shift_phases (adm_multislice.hip) form it -- is 1e-4 rad off and the prediction 2.3e-5
+// from the fp64 model (640 x 12, tests/test_gpu_value_domain.py).  So: ps_phase's scheme (adm_ms_probeshift.hip), the argument in
+// fp64 from the integer frequency index, reduced to one turn, then sin / cos in fp32.
+__device__ __forceinline__ cf es_phase(int y, int py, int x, int px, float2 s) {
+    const double fy = (double)st_freq_index(y, py) / (double)py, fx = (double)st_freq_index(x, px) / (double)px;
+    double arg = -2.0 * 3.14159265359 * (fx * (double)s.y + fy * (double)s.x);
+    const double two_pi = 6.283185307179586476925287;
+    arg -= two_pi * rint(arg / two_pi);
     float sn, cs;
-    sincos_fast(arg, sn, cs);
+    sincos_fast((float)arg, sn, cs);
     return make_float2(cs, sn);
 }
 
@@ -59,7 +64,7 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void es_col_conv_ke
             const int y = i / g.Px, x = c0 + (i - y * g.Px);
             const size_t k = (size_t)y * Px + x;
             const float fy = st_freq(y, Py), fx = st_freq(x, Px);
-            const cf ph = es_phase(fy, fx, s);
+            const cf ph = es_phase(y, Py, x, Px, s);
             const cf a = g.fld[i];
             if (CONJ) {
                 if (sums) {

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(1024) void ms_generic_kernel(MsParams p) {
             // far field: natural-order spectrum element (ky, kx) is the fftshifted detector pixel ((ky + Py/2) % Py, ...)
             const int my = far ? (ky + g.Py / 2) % g.Py : ky, mx = far ? (kx + g.Px / 2) % g.Px : kx;
             const size_t di = ((size_t)b * g.Py + my) * g.Px + mx;
-            const float wq = p.det_weight ? p.det_weight[my * g.Px + mx] : 1.f;
+            const bool drop = p.det_weight && p.det_weight[my * g.Px + mx] == 0.f;    // dropped, not weighted: the data there may be NaN
             float mag;
             if (M > 1) mag = sqrtf(inten[j]);
             else {
@@ -114,9 +114,10 @@ __global__ __launch_bounds__(1024) void ms_generic_kernel(MsParams p) {
                 mag = sqrtf(psi.x * psi.x + psi.y * psi.y);
             }
             float gg;
-            lsum += wq * (M > 1 ? loss_term_nz(mag, p.target[di], p, gg) : loss_term(mag, p.target[di], p, gg));
+            const float term = M > 1 ? loss_term_nz(mag, p.target[di], p, gg) : loss_term(mag, p.target[di], p, gg);
+            lsum += drop ? 0.f : term;
             if (p.pred) p.pred[di] = mag;
-            gf[j] = wq * gg;
+            gf[j] = drop ? 0.f : gg;
         }
     }
     {

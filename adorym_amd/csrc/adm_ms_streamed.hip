@@ -215,7 +215,7 @@ __global__ __launch_bounds__(ST_COL_NT) void st_det_kernel(MsParams p, float2* _
             // far field: natural-order spectrum element (ky, kx) is the fftshifted detector pixel ((ky + Py/2) % Py, ...)
             const int my = far ? (ky + Py / 2) % Py : ky, mx = far ? (kx + Px / 2) % Px : kx;
             const size_t di = ((size_t)b * Py + my) * Px + mx;
-            const float wq = p.det_weight ? p.det_weight[my * Px + mx] : 1.f;
+            const bool drop = p.det_weight && p.det_weight[my * Px + mx] == 0.f;    // dropped, not weighted: the data there may be NaN
             float mag;
             if (M > 1) mag = sqrtf(gf[i]);
             else {
@@ -223,9 +223,10 @@ __global__ __launch_bounds__(ST_COL_NT) void st_det_kernel(MsParams p, float2* _
                 mag = sqrtf(psi.x * psi.x + psi.y * psi.y);
             }
             float gg;
-            lsum += wq * (M > 1 ? loss_term_nz(mag, p.target[di], p, gg) : loss_term(mag, p.target[di], p, gg));
+            const float term = M > 1 ? loss_term_nz(mag, p.target[di], p, gg) : loss_term(mag, p.target[di], p, gg);
+            lsum += drop ? 0.f : term;
             if (p.pred) p.pred[di] = mag;
-            gf[i] = wq * gg;
+            gf[i] = drop ? 0.f : gg;
         }
     }
     {

@@ -498,10 +498,11 @@ __global__ __launch_bounds__((Geo<N, R1, R2>::NT)) void ms_fwd_adj_kernel(MsPara
                     const cf psi = cscale(bb[k], p.det_scale);      // (conjugated when det_inverse; |.| unaffected)
                     const float mag = sqrtf(psi.x * psi.x + psi.y * psi.y);
                     float g;
-                    const float wq = p.det_weight ? p.det_weight[my * N + mx] : 1.f;     // beamstop mask (forward_model.py:128-136)
-                    lsum += wq * loss_term(mag, p.target[di], p, g);
+                    const bool drop = p.det_weight && p.det_weight[my * N + mx] == 0.f;  // beamstop mask (forward_model.py:128-136)
+                    const float term = loss_term(mag, p.target[di], p, g);
+                    lsum += drop ? 0.f : term;                       // dropped, not weighted: the data there may be NaN
                     if (p.pred) p.pred[di] = mag;
-                    bb[k] = cscale(psi, wq * g * p.det_scale);       // adjoint of (scale * F) is scale * F^H
+                    bb[k] = cscale(psi, (drop ? 0.f : g) * p.det_scale);     // adjoint of (scale * F) is scale * F^H
                 }
             }
         } else if (c.act1) {
@@ -510,10 +511,11 @@ __global__ __launch_bounds__((Geo<N, R1, R2>::NT)) void ms_fwd_adj_kernel(MsPara
                 const size_t di = ((size_t)b * N + c.line) * N + k * R2 + c.t;
                 const float mag = sqrtf(a[k].x * a[k].x + a[k].y * a[k].y);
                 float g;
-                const float wq = p.det_weight ? p.det_weight[c.line * N + k * R2 + c.t] : 1.f;
-                lsum += wq * loss_term(mag, p.target[di], p, g);
+                const bool drop = p.det_weight && p.det_weight[c.line * N + k * R2 + c.t] == 0.f;
+                const float term = loss_term(mag, p.target[di], p, g);
+                lsum += drop ? 0.f : term;
                 if (p.pred) p.pred[di] = mag;
-                a[k] = cscale(a[k], wq * g);
+                a[k] = cscale(a[k], drop ? 0.f : g);
             }
         }
         block_loss<N, R1, R2>(lsum, red, p.loss_sum + b, tid, wave, lane);
@@ -563,9 +565,10 @@ __global__ __launch_bounds__((Geo<N, R1, R2>::NT)) void ms_fwd_adj_kernel(MsPara
                     const int my = (c.t + R1 * k + N / 2) % N;
                     const size_t di = ((size_t)b * N + my) * N + mx;
                     const float mag = sqrtf(inten[k]);
-                    const float wq = p.det_weight ? p.det_weight[my * N + mx] : 1.f;
-                    lsum += wq * loss_term_nz(mag, p.target[di], p, gf[k]);
-                    gf[k] *= wq;
+                    const bool drop = p.det_weight && p.det_weight[my * N + mx] == 0.f;
+                    const float term = loss_term_nz(mag, p.target[di], p, gf[k]);
+                    lsum += drop ? 0.f : term;
+                    if (drop) gf[k] = 0.f;
                     if (p.pred) p.pred[di] = mag;
                 }
             }
@@ -574,9 +577,10 @@ __global__ __launch_bounds__((Geo<N, R1, R2>::NT)) void ms_fwd_adj_kernel(MsPara
             for (int k = 0; k < R1; ++k) {
                 const size_t di = ((size_t)b * N + c.line) * N + k * R2 + c.t;
                 const float mag = sqrtf(inten[k]);
-                const float wq = p.det_weight ? p.det_weight[c.line * N + k * R2 + c.t] : 1.f;
-                lsum += wq * loss_term_nz(mag, p.target[di], p, gf[k]);
-                gf[k] *= wq;
+                const bool drop = p.det_weight && p.det_weight[c.line * N + k * R2 + c.t] == 0.f;
+                const float term = loss_term_nz(mag, p.target[di], p, gf[k]);
+                lsum += drop ? 0.f : term;
+                if (drop) gf[k] = 0.f;
                 if (p.pred) p.pred[di] = mag;
             }
         }

@@ -215,7 +215,9 @@ int adm_plan_create_streamed(adm_ctx* ctx, const adm_plan_desc* desc, adm_plan**
 int adm_plan_destroy(adm_plan* plan);
 /* Beamstop (adorym/forward_model.py:128-136): host float [Py][Px] in the detector layout of the data; pixels with
  * mask >= 1e-5 take part in the loss, the others are dropped.  The per-position loss sums then run over the kept pixels only
- * and the caller's grad_scale / mean use their count.  NULL removes the mask. */
+ * and the caller's grad_scale / mean use their count.  Data at dropped pixels is never read into the result: it may be NaN, inf,
+ * negative or a saturation marker (what detector gaps and hot pixels commonly hold), and the loss and every gradient are, bit for
+ * bit, what they are with any other numbers there; pred at a dropped pixel is still the predicted magnitude.  NULL removes the mask. */
 int adm_plan_set_detector_mask(adm_plan* plan, const float* mask_host);
 /* Several detector-plane Fresnel kernels in one plan (det_mode ADM_DET_FRESNEL): multi-distance data divided into sub-tiles
  * propagates the SAME tiles to every distance (adorym/forward_model.py:999-1018, one multislice_propagate_batch per distance).
@@ -401,7 +403,11 @@ int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n);
  *   shifts       device float [n_entries][2] = (s_y, s_x) in pixels
  *   index        device int32 [batch]: position b uses entry index[b]; NULL = entry b
  *   grad_shifts  device float [n_entries][2], dL/ds ACCUMULATED into it (want_grad = 1), or NULL
- * The terms of every entry are summed in fp64 in a fixed order (no atomics): two calls give the same bits. */
+ * The terms of every entry are summed in fp64 in a fixed order (no atomics): two calls give the same bits.
+ * Offsets may be as large as alignment needs them, beyond the field included (it wraps): the argument of Phi is formed in fp64
+ * and reduced to one turn before the fp32 sine and cosine, so the result does not lose accuracy with |s|.  The per-position
+ * probe shifts of the one-workgroup kernels (adm_probe_shift*, fields up to 72 x 72) form it in fp32 as the reference does:
+ * at most 1e-5 rad of rounding at an offset of one field, inside their bars. */
 int adm_plan_set_exit_shift(adm_plan* plan, int on);
 int adm_multislice_fwd_adj_exit_shift(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
                                       const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,

@@ -105,10 +105,14 @@ def run_case(A, ctx, P, **kw):
 
 def oracle_case(P, S=5, B=11, n_modes=1, unknown_type='delta_beta', binning=1, transmission_cache=True, free_prop='inf',
                 sign_convention=1, normalize_fft=False, fresnel_approx=True, loss='lsq', raw_data_type='magnitude', poisson_multiplier=1.,
-                beamstop=False, pp=None, generic=False, margin=(9, 13), seed=0):
+                beamstop=False, pp=None, generic=False, margin=(9, 13), seed=0, obj_fn=None, meas_edit=None, shifts_fn=None, probe_edit=None):
     """The inputs of one minibatch and the oracle's results on them.  ``P``: size or (Py, Px); ``free_prop``: 'inf', 0, a distance
     in cm or a list of distances (position b uses distance b % n); ``pp``: None (one shared probe set), 'shifts' (Fourier-shifted per
     position, gradients w.r.t. the probe and the shifts) or 'probes' (a probe set per position handed over as it is).
+    ``beamstop``: True (a disc and the first row dropped) or a [Py, Px] mask of its own.  A case may supply its own numbers
+    (tests/value_matrix.py): ``obj_fn(r, Y, X, S) -> (obj, truth)`` in place of the weak object drawn here, ``meas_edit(meas,
+    beamstop) -> meas`` applied to the measured data, ``shifts_fn(n_entries) -> [n_entries, 2]`` in place of the shifts within
+    2.5 px, ``probe_edit(probes) -> probes`` applied to the shared probe set.  The defaults draw what they always drew, bit for bit.
     Returns a dict of the inputs and the oracle results (``*_o`` fp64, ``*_32`` fp32); run_engine adds the engine's (``*``)."""
     Py, Px = (P, P) if np.isscalar(P) else tuple(P)
     r = np.random.default_rng([Py, Px, S, B, n_modes, binning, seed])
@@ -119,16 +123,20 @@ def oracle_case(P, S=5, B=11, n_modes=1, unknown_type='delta_beta', binning=1, t
         mk = lambda c: np.stack([2e-3 * c * r.uniform(size=(Y, X, S)), 2e-4 * c * r.uniform(size=(Y, X, S))], -1)
     else:
         mk = lambda c: np.stack([1 + 1e-2 * c * r.standard_normal((Y, X, S)), 2e-2 * c * r.standard_normal((Y, X, S))], -1)
-    obj, truth = mk(1), mk(10)
+    obj, truth = (mk(1), mk(10)) if obj_fn is None else obj_fn(r, Y, X, S)
     pos = edge_positions(r, B, Y, X, Py, Px)
     M = n_modes
     rand_probes = lambda *lead: (0.5 + r.uniform(0, 1, lead + (Py, Px))) * np.exp(1j * r.uniform(-np.pi, np.pi, lead + (Py, Px)))
     probes = rand_probes(M)
+    if probe_edit is not None:
+        probes = probe_edit(probes)
     dists = list(free_prop) if isinstance(free_prop, (list, tuple)) else [free_prop]
     phys = [O.Physics((Py, Px), ENERGY_EV, PSIZE_CM, free_prop_cm=d, binning=binning, fresnel_approx=fresnel_approx,
                       sign_convention=sign_convention, normalize_fft=normalize_fft, unknown_type=unknown_type) for d in dists]
     bs = None
-    if beamstop:
+    if isinstance(beamstop, np.ndarray):
+        bs = beamstop
+    elif beamstop:
         yy, xx = np.meshgrid(np.arange(Py) - Py / 2, np.arange(Px) - Px / 2, indexing='ij')
         bs = np.where(yy ** 2 + xx ** 2 < (min(Py, Px) / 5) ** 2, 0., 1.)
         bs[0, :] = 1e-6                                     # below the 1e-5 threshold: out of the loss
@@ -139,6 +147,8 @@ def oracle_case(P, S=5, B=11, n_modes=1, unknown_type='delta_beta', binning=1, t
         shifts = r.uniform(-2.5, 2.5, (n_ent, 2))
         shifts[0] = (1.75, -2.25)
         shifts[1] = (-1.5, 0.6)
+        if shifts_fn is not None:
+            shifts = np.asarray(shifts_fn(n_ent), np.float64)
         idx = np.concatenate([np.arange(n_ent), r.integers(0, n_ent, B - n_ent)]).astype(np.int32)   # some entries twice
         pprobes = np.stack([O.fourier_shift(probes, shifts[e], 'float64') for e in idx])              # [B, M, Py, Px]
     elif pp == 'probes':
@@ -150,6 +160,8 @@ def oracle_case(P, S=5, B=11, n_modes=1, unknown_type='delta_beta', binning=1, t
     t_tiles, _ = O.extract_tiles(truth, pos, (Py, Px), unknown_type)
     mag = np.concatenate([O.predict(t_tiles[b:b + 1], pprobes[b], phys[b % len(phys)], 'float64')[0] for b in range(B)])
     meas = mag ** 2 if raw_data_type == 'intensity' else mag
+    if meas_edit is not None:
+        meas = meas_edit(meas, bs)
     if loss == 'lsq':
         target = O.target_magnitude(meas, raw_data_type)
     else:

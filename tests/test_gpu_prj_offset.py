@@ -154,9 +154,9 @@ def test_far_field_leaves_the_gradient_buffer_alone(A, ctx, F):
 
 
 # --------------------------------------------------------------------------------- 2. launch geometries (the restatement)
-def make_case(P, S=2, B=5, M=1, shared=False, unknown_type='delta_beta', free_prop=FREE_PROP_CM, sign_convention=1, seed=0):
+def make_case(P, S=2, B=5, M=1, shared=False, unknown_type='delta_beta', free_prop=FREE_PROP_CM, sign_convention=1, seed=0, shifts_fn=None):
     """Built like ms_matrix.oracle_case: positions hanging over all four edges, a truth with ten times the guess's contrast and
-    other offsets makes the data."""
+    other offsets makes the data.  ``shifts_fn(n) -> [n, 2]``: offsets in place of the ones drawn within 2 px."""
     Py, Px = (P, P) if np.isscalar(P) else tuple(P)
     r = np.random.default_rng([Py, Px, S, B, M, seed])
     Y, X = Py + 9, Px + 13
@@ -167,6 +167,8 @@ def make_case(P, S=2, B=5, M=1, shared=False, unknown_type='delta_beta', free_pr
     index = np.array([0, 1, 2, 1, 0][:B], np.int32) if shared else None
     n = 3 if shared else B
     shifts = r.uniform(-2, 2, (n, 2)).astype(np.float32)
+    if shifts_fn is not None:
+        shifts = np.asarray(shifts_fn(n), np.float32)
     phys = O.Physics((Py, Px), ENERGY_EV, PSIZE_CM, free_prop_cm=free_prop, sign_convention=sign_convention, unknown_type=unknown_type)
     tiles, _ = O.extract_tiles(truth.astype(np.float64), pos, (Py, Px), unknown_type)
     meas = PR.predict(tiles, probes.astype(np.complex128), phys, shifts.astype(np.float64) + r.uniform(-0.3, 0.3, (n, 2)), index)
