@@ -31,6 +31,11 @@ class HoloDesc(C.Structure):
                 ('unknown_type', C.c_int32), ('raw_intensity', C.c_int32), ('k1', C.c_float)]
 
 
+class CtfDesc(C.Structure):
+    _fields_ = [('ny', C.c_int32), ('nx', C.c_int32), ('n_dists', C.c_int32), ('raw_intensity', C.c_int32),
+                ('energy_ev', C.c_double), ('psize_cm', C.c_double)]
+
+
 class SmallParam(C.Structure):
     _fields_ = [('x', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('n', C.c_uint64), ('step_size', C.c_double),
                 ('center_cols', C.c_int32), ('zero_grad', C.c_int32), ('pin', C.c_void_p), ('pin_n', C.c_uint64)]
@@ -162,6 +167,9 @@ SIGNATURES = {
     'adm_holo_shift_targets': (_I, [_VP, _VP, _VP, _VP]),
     'adm_holo_set_registration': (_I, [_VP, _VP, C.c_int]),
     'adm_holo_shift_grad': (_I, [_VP, _VP, _VP, _VP, _VP]),
+    'adm_ctf_create': (_I, [_VP, C.POINTER(CtfDesc), C.POINTER(_VP)]),
+    'adm_ctf_destroy': (_I, [_VP]),
+    'adm_ctf_fwd_adj': (_I, [_VP, _VP, C.POINTER(_D), _VP, _VP, _I, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -710,6 +710,11 @@ class MultiDistModel(PtychographyModel):
     zones, one detector-plane Fresnel kernel per distance in the plan (adm_plan_set_detector_kernels), detector mask = the
     sub-hologram's window -- and a minibatch of tiles at all distances is ONE launch of the multislice kernel with one probe
     window per entry (adm_multislice_fwd_adj_pp); object gradient only.
+
+    ``common_vars_dict['forward_algorithm'] == 'ctf'`` (:1011-1014, modulate_and_get_ctf): the contrast-transfer-function model of
+    a weak, homogeneous object, I_d = 1 + Re IFFT2(2 (sin xi_d + cos xi_d / kappa) FFT2(delta)) with kappa = 10^ctf_lg_kappa[0].
+    ``common_vars_dict['ctf_engine']`` is an adorym_amd.CTFEngine; gradients w.r.t. obj (beta's is exactly zero) and ctf_lg_kappa
+    come from adm_ctf_fwd_adj.  Neither the probe nor beta enters the model; one undivided field of view only.
     """
 
     PROJECTION_MODEL = 'multi-distance data (MultiDistModel)'
@@ -720,17 +725,26 @@ class MultiDistModel(PtychographyModel):
                                              simulation_mode=simulation_mode, run_bfloat16=run_bfloat16, run_float64=run_float64)
         if loss_function_type != 'lsq':
             raise NotImplementedError('MultiDistModel: only the LSQ loss is on the accelerated path')
-        self.holo = common_vars_dict['holo_engine'] if common_vars_dict else None
         self.tile_engine = common_vars_dict.get('tile_engine') if common_vars_dict else None
+        self.ctf = common_vars_dict.get('ctf_engine') if common_vars_dict else None
+        self.is_ctf = bool(common_vars_dict) and common_vars_dict.get('forward_algorithm') == 'ctf'
+        self.holo = None if (self.is_ctf or not common_vars_dict) else common_vars_dict['holo_engine']
+        if self.is_ctf and self.ctf is None:
+            raise ValueError("MultiDistModel with forward_algorithm='ctf' needs common_vars_dict['ctf_engine'] (an adorym_amd.CTFEngine)")
         self._data_key = None
         self._data_dev = None
         self._small = {}
 
     def _check(self, safe_zone_width, ctf_lg_kappa, probe_pos_correction):
         cv = self.common_vars
-        for flag in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_prj_pos_offset', 'optimize_ctf_lg_kappa'):
+        for flag in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_prj_pos_offset'):
             if cv.get(flag):
                 raise NotImplementedError('%s with MultiDistModel is outside the accelerated path' % flag)
+        if self.is_ctf:
+            return self._check_ctf(safe_zone_width, ctf_lg_kappa)
+        if cv.get('optimize_ctf_lg_kappa'):
+            # (the reference threads kappa into multislice_propagate_batch there, forward_model.py:878, 1010)
+            raise NotImplementedError("optimize_ctf_lg_kappa with forward_algorithm='fresnel' is outside the accelerated path")
         if cv.get('optimize_all_probe_pos'):
             # one (sy, sx) per distance applied to the measured holograms (forward_model.py:1075-1085)
             if cv.get('optimize_prj_affine'):
@@ -749,6 +763,39 @@ class MultiDistModel(PtychographyModel):
                     raise NotImplementedError('%s with multi-distance data divided into sub-tiles is outside the accelerated path' % flag)
         elif safe_zone_width not in (0, None):
             raise NotImplementedError('safe_zone_width > 0 needs the tile engine (the driver builds it)')
+
+    # what the CTF model refuses by name: it has no probe, one slice, one undivided field of view, fixed distances and no registration
+    CTF_REFUSED_FLAGS = ('optimize_probe', 'optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos')
+
+    def _check_ctf(self, safe_zone_width, ctf_lg_kappa):
+        cv = self.common_vars
+        what = None
+        if cv.get('unknown_type', 'delta_beta') == 'real_imag':
+            what = "unknown_type='real_imag'"
+        elif int(cv.get('n_probe_modes') or 1) != 1:
+            what = 'n_probe_modes != 1'
+        elif not cv.get('two_d_mode'):
+            what = 'two_d_mode=False'
+        elif self.tile_engine is not None or safe_zone_width not in (0, None) or int(cv.get('safe_zone_width') or 0) > 0:
+            what = 'data divided into sub-tiles or safe_zone_width > 0'
+        elif self.loss_function_type != 'lsq':
+            what = "loss_function_type='%s'" % self.loss_function_type
+        for flag in self.CTF_REFUSED_FLAGS:
+            if what is None and cv.get(flag):
+                what = flag
+        if what is not None:
+            raise NotImplementedError("forward_algorithm='ctf' with %s is outside the accelerated path" % what)
+        if ctf_lg_kappa is None:
+            raise ValueError("forward_algorithm='ctf' needs ctf_lg_kappa")
+
+    def _run_ctf(self, obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad, grad_obj=None, grad_lg_kappa=None, want_pred=False,
+                 overwrite=False):
+        """One launch group of adm_ctf_fwd_adj.  The distances are not refined under this model: they go in as host doubles."""
+        nd = self.ctf.n_dists
+        dists = free_prop_cm.get() if isinstance(free_prop_cm, DeviceArray) else free_prop_cm
+        lgk = self._dev('ctf_lg_kappa', ctf_lg_kappa, (1,))
+        self.ctf.forward_adjoint(obj, np.asarray(dists, dtype=np.float64).reshape(nd), lgk, self._data(this_i_theta), want_grad=want_grad,
+                                 grad_obj=grad_obj, grad_lg_kappa=grad_lg_kappa, want_pred=want_pred, overwrite=overwrite)
 
     # ------------------------------------------------------------------ sub-tiles + safe zone (forward_model.py:884-1034)
     # One engine serves all distances: its plan holds the n_dists detector-plane kernels and a launch lists every tile of the
@@ -924,6 +971,9 @@ class MultiDistModel(PtychographyModel):
         """Detected magnitudes [n_dists, ny, nx] (host float32), adorym/forward_model.py:819-1034."""
         self._check(safe_zone_width, ctf_lg_kappa, probe_pos_correction)
         self.i_call += 1
+        if self.is_ctf:
+            self._run_ctf(obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad=False, want_pred=True)
+            return self.ctf.pred()
         if self.tile_engine is not None:
             return self._run_tiled(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, this_ind_batch, want_grad=False, want_pred=True)
         self._run(obj, probe_real, probe_imag, this_i_theta, free_prop_cm, prj_affine_ls, want_grad=False, want_pred=True,
@@ -935,6 +985,10 @@ class MultiDistModel(PtychographyModel):
                            probe_pos_correction, this_ind_batch, free_prop_cm, safe_zone_width, prj_affine_ls, ctf_lg_kappa,
                            prj_pos_offset):
             self._check(safe_zone_width, ctf_lg_kappa, probe_pos_correction)
+            if self.is_ctf:
+                self._run_ctf(obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad=False)
+                self.current_loss = float(self.ctf.loss() + self._regularize(obj, None))
+                return self.current_loss
             if self.tile_engine is not None:
                 datav = self._run_tiled(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, this_ind_batch, want_grad=False)
                 self.current_loss = float(datav() + self._regularize(obj, None))
@@ -955,6 +1009,23 @@ class MultiDistModel(PtychographyModel):
         self._check(safe_zone_width, ctf_lg_kappa, probe_pos_correction)
         if _side_hook is not None:
             _side_hook()
+        if self.is_ctf:
+            # as on the undivided Fresnel path below: '=' into a buffer that holds garbage, '+=' otherwise; the regulariser adds
+            i_k = self.get_argument_index('ctf_lg_kappa')
+            for i in opt_args_ls:
+                if i not in (0, i_k):
+                    raise NotImplementedError("forward_algorithm='ctf': the gradient w.r.t. '%s' is outside the accelerated path" % self.argument_ls[i])
+            gk = None
+            if i_k in opt_args_ls:
+                if getattr(self, '_gk', None) is None:
+                    self._gk = self.device.empty((1,))
+                gk = self._gk if _init_grad else self._gk.zero_()
+            self._run_ctf(obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad=True, grad_obj=grad_obj, grad_lg_kappa=gk,
+                          overwrite=bool(_init_grad))
+            regv = self._reg_value_async(self._regularize_launch(obj, grad_obj))
+            datav = self.ctf.loss_async()
+            self._loss_thunk = lambda: datav() + regv()
+            return tuple(grad_obj if i == 0 else gk for i in opt_args_ls)
         if self.tile_engine is not None:
             if list(opt_args_ls) != [0]:
                 raise NotImplementedError('multi-distance data divided into sub-tiles: only the object gradient is on the accelerated path')

@@ -124,3 +124,68 @@ class HolographyEngine(object):
 
     def pred(self):
         return self._pred.get()
+
+
+class CTFEngine(object):
+    """The contrast-transfer-function model of multi-distance holography (forward_algorithm='ctf'; adorym/propagate.py:467-476,
+    590-606) for one undivided field of view and one object slice in 'delta_beta'.  See include/adm.h (adm_ctf_*) and
+    csrc/adm_holo_ctf.hip.  No probe enters; the gradient w.r.t. beta is exactly zero."""
+
+    def __init__(self, ctx, field_size, n_dists, energy_ev, psize_cm, raw_data_type='intensity'):
+        from ._lib import CtfDesc
+        from .device import PinnedArray, Event
+        self.ctx = ctx
+        self.ny, self.nx = int(field_size[0]), int(field_size[1])
+        self.n_dists = int(n_dists)
+        desc = CtfDesc(ny=self.ny, nx=self.nx, n_dists=self.n_dists, raw_intensity=1 if raw_data_type == 'intensity' else 0,
+                       energy_ev=float(energy_ev), psize_cm=float(psize_cm))
+        h = C.c_void_p()
+        check(ctx.lib.adm_ctf_create(ctx.handle, C.byref(desc), C.byref(h)))
+        self.handle = h
+        # the per-distance loss sums go straight into page-locked host memory, two alternating slots (see HolographyEngine)
+        self._pinned = [PinnedArray(ctx, (max(self.n_dists, 16),)) for _ in range(2)]
+        self._events = [Event(ctx) for _ in range(2)]
+        self._slot = 0
+        self._pred = None
+
+    def __del__(self):
+        try:
+            if getattr(self, 'handle', None) and self.ctx.handle:
+                self.ctx.lib.adm_ctf_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def forward_adjoint(self, obj, dists_cm, lg_kappa, data, want_grad=True, grad_obj=None, grad_lg_kappa=None, want_pred=False,
+                        overwrite=False):
+        """obj [ny,nx,(1,)2], lg_kappa [1], data [n_dists,ny,nx] (raw) are DeviceArrays; dists_cm is a HOST sequence of n_dists
+        distances in cm.  grad_obj's delta channel and grad_lg_kappa are accumulated (+=; the beta channel is left alone), or
+        overwritten with ``overwrite=True`` (beta channel = 0)."""
+        d = np.ascontiguousarray(np.asarray(dists_cm, dtype=np.float64).reshape(-1))
+        if d.size != self.n_dists:
+            raise ValueError('CTFEngine: %d distances given, %d expected' % (d.size, self.n_dists))
+        if want_pred and self._pred is None:
+            self._pred = DeviceArray(self.ctx, (self.n_dists, self.ny, self.nx), np.float32)
+        p = lambda a: a.ptr if a is not None else None
+        self._slot ^= 1
+        check(self.ctx.lib.adm_ctf_fwd_adj(self.handle, obj.ptr, d.ctypes.data_as(C.POINTER(C.c_double)), lg_kappa.ptr, data.ptr,
+                                           (2 if overwrite else 1) if want_grad else 0, p(grad_obj), p(grad_lg_kappa),
+                                           self._pred.ptr if want_pred else None, self._pinned[self._slot].handle))
+
+    def loss(self):
+        """mean over (distance, pixel) of the squared residual of the last launch -- blocks."""
+        return self.loss_async()()
+
+    def loss_async(self):
+        """Record an event behind the last launch and return a callable that gives its loss (see HolographyEngine.loss_async)."""
+        k = self._slot
+        self._events[k].record()
+        norm = float(self.n_dists * self.ny * self.nx)
+
+        def value():
+            self._events[k].synchronize()
+            return float(self._pinned[k].array[:self.n_dists].astype(np.float64).sum() / norm)
+        return value
+
+    def pred(self):
+        return self._pred.get()

@@ -348,7 +348,9 @@ class _Run(object):
             _not_implemented(self.object_type != 'normal', "object_type='%s' with unknown_type='real_imag'" % self.object_type)
             _not_implemented(self.binning != 1, "binning > 1 with unknown_type='real_imag'")
         _not_implemented(self.multiscale_level != 1, 'multiscale_level > 1')
-        _not_implemented(self.forward_algorithm != 'fresnel', "forward_algorithm='%s'" % (self.forward_algorithm,))
+        # 'ctf' (the contrast-transfer-function model) serves multi-distance data only: read_data refuses it elsewhere
+        _not_implemented(self.forward_algorithm not in ('fresnel', 'ctf') or (self.forward_algorithm == 'ctf' and bool(self.pure_projection)),
+                         "forward_algorithm='%s'" % (self.forward_algorithm,))
         if self.pure_projection:
             # the projection approximation (ProjectionEngine): delta_beta unknowns summed along the beam, rotated inside the loop
             # (the ones that need the data's shape -- sparse multislice, multi-distance data: read_data)
@@ -364,8 +366,10 @@ class _Run(object):
         _not_implemented(self.shrink_cycle is not None, 'shrink-wrap mask updates')
         _not_implemented(self.initial_tilt is not None, 'initial_tilt')
         _not_implemented(self.interpolation != 'bilinear', "interpolation='%s'" % self.interpolation)
-        for nm in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_tilt', 'optimize_ctf_lg_kappa'):
+        for nm in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_tilt'):
             _not_implemented(getattr(self, nm), nm)
+        # (the reference threads kappa into multislice_propagate_batch there, forward_model.py:878, 1010: not built)
+        _not_implemented(bool(self.optimize_ctf_lg_kappa) and self.forward_algorithm != 'ctf', "optimize_ctf_lg_kappa with forward_algorithm='fresnel'")
         if self.update_scheme not in ('immediate', 'per angle'):
             raise ValueError("update_scheme must be 'immediate' or 'per angle'")
 
@@ -437,6 +441,8 @@ class _Run(object):
             if isinstance(self.free_prop_cm, str) and self.free_prop_cm == 'inf':
                 warnings.warn('optimize_prj_pos_offset with a far-field detector: the magnitude of a Fourier transform does not depend on a '
                               'shift of the exit wave, so the gradient is zero and the offsets cannot move.', UserWarning)
+        self.is_ctf = self.forward_algorithm == 'ctf'
+        _not_implemented(self.is_ctf and not self.is_multi_dist, "forward_algorithm='ctf'")
         self.holo_tiled = False
         if self.is_multi_dist:
             # one object slice; config 5 is one undivided field of view (n_blocks == 1) without a safe zone
@@ -445,10 +451,21 @@ class _Run(object):
             safe_zone_width = self.safe_zone_width = int(self.safe_zone_width or 0)
             if prj.shape[1] != n_dists * len(probe_pos):
                 raise ValueError('multi-distance data: prj.shape[1] = %d is not n_dists x n_blocks = %d x %d' % (prj.shape[1], n_dists, len(probe_pos)))
-            _not_implemented(not self.two_d_mode, 'multi-distance holography of a 3-D object')
-            _not_implemented(self.n_probe_modes != 1, 'several probe modes with multi-distance data')
-            _not_implemented(self.loss_function_type != 'lsq', 'Poisson loss with multi-distance data')
+            _not_implemented(not self.two_d_mode, "forward_algorithm='ctf' with two_d_mode=False" if self.forward_algorithm == 'ctf'
+                             else 'multi-distance holography of a 3-D object')
+            _not_implemented(self.n_probe_modes != 1, "forward_algorithm='ctf' with n_probe_modes != 1" if self.forward_algorithm == 'ctf'
+                             else 'several probe modes with multi-distance data')
+            _not_implemented(self.loss_function_type != 'lsq', "forward_algorithm='ctf' with loss_function_type='%s'" % self.loss_function_type
+                             if self.forward_algorithm == 'ctf' else 'Poisson loss with multi-distance data')
             self.holo_tiled = len(probe_pos) > 1 or safe_zone_width > 0
+            if self.is_ctf:
+                # modulate_and_get_ctf (adorym/propagate.py:467-476): no probe, one slice in delta/beta, one undivided field of view,
+                # fixed distances, no registration of the holograms
+                what = "forward_algorithm='ctf' with %s"
+                _not_implemented(self.unknown_type == 'real_imag', what % "unknown_type='real_imag'")
+                _not_implemented(self.holo_tiled, what % 'data divided into sub-tiles or safe_zone_width > 0')
+                for nm in ('optimize_probe', 'optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos'):
+                    _not_implemented(bool(getattr(self, nm)), what % nm)
             if self.holo_tiled:
                 # data divided into sub-tiles and / or a safe zone around every tile (adorym/forward_model.py:884-1034)
                 tile_size = self.tile_size = [int(v) + 2 * safe_zone_width for v in prj.shape[-2:]]
@@ -498,7 +515,7 @@ class _Run(object):
         self.h = get_kernel(voxel_nm[-1] * self.binning, self.lmbda_nm, voxel_nm, probe_size, fresnel_approx=self.fresnel_approx,
                             sign_convention=self.sign_convention) if not self.is_multi_dist else None
         self.probe_pos_int = np.round(self.probe_pos).astype(int)
-        self.holo_engine = self.tile_engine = None
+        self.holo_engine = self.tile_engine = self.ctf_engine = None
         common = dict(sign_convention=self.sign_convention, scale_ri_by_k=self.scale_ri_by_k, unknown_type=self.unknown_type)
         if self.holo_tiled:
             # one engine for all distances: tile = sub-hologram + 2 safe zones at (position - safe zone), every tile listed n_dists
@@ -512,9 +529,13 @@ class _Run(object):
                 ctx, obj_size, tile_size, np.repeat(self.probe_pos_int - szw, self.n_dists, axis=0), self.energy_ev, self.psize_cm,
                 free_prop_cm=self.free_prop_cm, max_batch=self.minibatch_size * self.n_dists, beamstop=window, **common)
         elif self.is_multi_dist:
-            from .holography import HolographyEngine
-            self.holo_engine = HolographyEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm, raw_data_type=self.raw_data_type,
-                                                **common)
+            if self.is_ctf:
+                from .holography import CTFEngine
+                self.ctf_engine = CTFEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm, raw_data_type=self.raw_data_type)
+            else:
+                from .holography import HolographyEngine
+                self.holo_engine = HolographyEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm,
+                                                    raw_data_type=self.raw_data_type, **common)
             # a minimal multislice plan is still created: it carries the object geometry for the regulariser kernels
             self.engine = MultisliceEngine(ctx, obj_size, (8, 8), np.zeros((1, 2), int), self.energy_ev, self.psize_cm, free_prop_cm=0,
                                            max_batch=1, unknown_type=self.unknown_type)
@@ -637,7 +658,8 @@ class _Run(object):
                            forward_algorithm=self.forward_algorithm, pure_projection=bool(self.pure_projection),
                            stdout_options=self.stdout_options, poisson_multiplier=self.poisson_multiplier,
                            common_probe_pos=self.common_probe_pos, binning=self.binning, prj=self.prj, engine=self.engine,
-                           holo_engine=self.holo_engine, tile_engine=self.tile_engine, safe_zone_width=self.safe_zone_width,
+                           holo_engine=self.holo_engine, tile_engine=self.tile_engine, ctf_engine=self.ctf_engine,
+                           safe_zone_width=self.safe_zone_width, optimize_probe=self.optimize_probe,
                            n_dp_batch=self.n_dp_batch, optimize_prj_affine=self.optimize_prj_affine, optimize_free_prop=self.optimize_free_prop,
                            optimize_ctf_lg_kappa=self.optimize_ctf_lg_kappa, rotation_tables=self.rotation_tables, two_d_mode=self.two_d_mode,
                            theta_downsample=self.theta_downsample, ds_level=self.ds_level, probe_size=self.probe_size,
@@ -762,6 +784,14 @@ class _Run(object):
         if self.is_sparse_multislice and self.optimize_slice_pos:
             # optimizers.py:891-903, 1051-1060: Adam on the slice positions (+ "prevent position drifting": subtract the first)
             self._add_small('slice_pos_cm_ls', self.optimizer_slice_pos, self.slice_pos_learning_rate, anchor=True)
+        if self.is_multi_dist and self.is_ctf:
+            # a [1] array like the reference's (ptychography.py:732-733; float32 here), on the device whether it is refined or not:
+            # the kernels read it there
+            params['ctf_lg_kappa'] = ctx.array(np.array([float(self.ctf_lg_kappa)]), np.float32)
+        if self.optimize_ctf_lg_kappa:
+            # optimizers.py:945-956, 1077-1083: plain Adam on the [1] array, no pin, no drift guard
+            self._add_small('ctf_lg_kappa', self.optimizer_ctf_lg_kappa, self.ctf_lg_kappa_learning_rate)
+        self.ctf_lg_kappa_history = None      # (return_state: the value after every update, copied on the device)
         self.slice_pos_history = None         # (return_state: the positions after every update, copied on the device)
         self.prj_pos_offset_history = None    # (likewise: the offsets after every update)
 
@@ -773,7 +803,7 @@ class _Run(object):
                     raise ValueError('checkpointed probe has shape %s, this run uses %s' % (pr_.shape[:-1], self.probe_dev.shape[:-1]))
                 self.probe_dev.set(pr_.astype(np.float32))
             for k_ in ('probe_pos_correction', 'free_prop_cm', 'prj_affine_ls', 'probe_defocus_mm', 'probe_pos_offset', 'prj_pos_offset',
-                       'tilt_ls', 'slice_pos_cm_ls'):
+                       'tilt_ls', 'slice_pos_cm_ls', 'ctf_lg_kappa'):
                 if k_ in restored and k_ in params:
                     if hasattr(params[k_], 'set'):
                         params[k_].set(np.asarray(restored[k_], dtype=np.float32).reshape(params[k_].shape))
@@ -1074,7 +1104,7 @@ class _Run(object):
         minibatch, no regulariser, constraint or mask on the object, plain Adam with common (b1, b2, eps) on the object and on
         whichever of free_prop_cm / prj_affine_ls are optimised: the steps run INSIDE the gradient launch group's last kernel
         (adm_holo_fwd_adj_adam; same arithmetic, same bits), no gradient is stored and no optimiser launch follows."""
-        if not (self.is_multi_dist and not self.holo_tiled and self.builtin_model and init_grad and self.update_scheme == 'immediate'
+        if not (self.is_multi_dist and not self.holo_tiled and not self.is_ctf and self.builtin_model and init_grad and self.update_scheme == 'immediate'
                 and self.optimize_object and self.n_ranks == 1 and self.flags == 0 and self.mask is None
                 and all(p.key in _HOLO_FUSED_SLOTS for p in self.small) and not self.forward_model.reg_list
                 and os.environ.get('ADM_HOLO_FUSED_ADAM', '1') == '1'):
@@ -1168,6 +1198,14 @@ class _Run(object):
                 if k < hist.shape[0]:
                     _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * z.size * k, z.ptr, z.nbytes))
                     self.slice_pos_history[1] = k + 1
+        if any(p.key == 'ctf_lg_kappa' for p in due) and self.return_state and self.n_epochs != 'auto':
+            x = self.optimizable_params['ctf_lg_kappa']
+            if self.ctf_lg_kappa_history is None:
+                self.ctf_lg_kappa_history = [self.ctx.zeros((int(self.n_epochs) * self.n_batch,)), 0]
+            hist, k = self.ctf_lg_kappa_history
+            if k < hist.shape[0]:
+                _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * k, x.ptr, x.nbytes))
+                self.ctf_lg_kappa_history[1] = k + 1
         if any(p.key == 'prj_pos_offset' for p in due) and self.return_state and self.n_epochs != 'auto':
             x = self.optimizable_params['prj_pos_offset']
             if self.prj_pos_offset_history is None:
@@ -1190,6 +1228,8 @@ class _Run(object):
                 continue
             d_ = os.path.join(folder, {'probe_pos_correction': 'probe_pos', 'prj_affine_ls': 'prj_affine'}.get(p.key, p.key))
             os.makedirs(d_, exist_ok=True)
+            if p.key == 'ctf_lg_kappa':
+                continue          # (the reference creates the folder, optimizers.py:1092-1109, and writes nothing into it, :1111-1160)
             v_ = np.asarray(_host(params[p.key]))
             if p.key == 'probe_pos_correction' and self.is_multi_dist:
                 np.savetxt(os.path.join(d_, 'probe_pos_correction_{}_{}.txt'.format(i_epoch, i_batch)), v_)
@@ -1234,6 +1274,9 @@ class _Run(object):
                 'prj_pos_offset': np.asarray(_host(params['prj_pos_offset'])),
                 'prj_pos_offset_history': (None if self.prj_pos_offset_history is None
                                            else self.prj_pos_offset_history[0].get()[:self.prj_pos_offset_history[1]]),
+                'ctf_lg_kappa': None if 'ctf_lg_kappa' not in params else np.asarray(_host(params['ctf_lg_kappa'])).reshape(-1),
+                'ctf_lg_kappa_history': (None if self.ctf_lg_kappa_history is None
+                                         else self.ctf_lg_kappa_history[0].get()[:self.ctf_lg_kappa_history[1]]),
                 'losses': self.loss_history, 'output_folder': self.output_folder,
                 # which multislice path served the run
                 'engine_streamed': bool(self.engine.streamed), 'engine_probe_shift': bool(self.engine.probe_shift)}

@@ -613,6 +613,34 @@ int adm_holo_data_spectrum(adm_holo* h, const float* data, float* spectrum);
 int adm_holo_shift_targets(adm_holo* h, const float* spectrum, const float* shifts, float* targets);
 int adm_holo_set_registration(adm_holo* h, float* cot_out, int direct);
 int adm_holo_shift_grad(adm_holo* h, const float* cot, const float* spectrum, const float* shifts, float* grad_shifts);
+/* ---- f1  the contrast-transfer-function model of multi-distance holography ---------------
+ * MultiDistModel with forward_algorithm='ctf' (adorym/forward_model.py:1011-1014; modulate_and_get_ctf / pure_phase_ctf,
+ * adorym/propagate.py:467-476, 590-606) for one undivided field of view and one object slice, unknown_type 'delta_beta'.
+ * With D = delta[:, :, 0], n = ny*nx, kappa = 10^lg_kappa, lambda_nm = 1240 / energy_ev and (u, v) = gen_freq_mesh:
+ *     xi_d = PI lambda_nm dist_nm_d (u^2 + v^2);   osc_d = 2 (sin xi_d + cos xi_d / kappa)
+ *     I_d = 1 + Re IFFT2(osc_d FFT2(D));   pred_d = sqrt(max(I_d, 0));   loss = mean_{d,pixels}(pred_d - t_d)^2
+ * with t_d as adm_holo_fwd_adj defines it (no registration).  Neither beta nor a probe enters: dL/dbeta = 0 exactly.
+ * Deviation from the reference: a pixel with I_d <= 0 predicts 0 and contributes to no gradient (the reference's autograd returns
+ * NaN for every gradient as soon as one I_d < 0: INTEGRATION.md).
+ * Sides are powers of two in [16, 2048], 1 <= n_dists <= 64; anything else is ADM_ERR_UNSUPPORTED. */
+typedef struct adm_ctf adm_ctf;
+typedef struct adm_ctf_desc {
+    int32_t ny, nx, n_dists;
+    int32_t raw_intensity;            /* raw_data_type: 0 'magnitude', 1 'intensity' */
+    double  energy_ev, psize_cm;
+} adm_ctf_desc;
+int adm_ctf_create(adm_ctx* ctx, const adm_ctf_desc* desc, adm_ctf** out);
+int adm_ctf_destroy(adm_ctf* h);
+/* obj [ny][nx][2] (delta, beta), data / pred [n_dists][ny][nx], lg_kappa [1]: device pointers.  dists_cm: HOST doubles [n_dists]
+ * (each enters as fl32(PI lambda_nm dist_nm_d), rounded once, as the reference's Python double meets its float32 tensors).
+ * loss_sum follows adm_holo_fwd_adj: [n_dists] (overwritten) = per-distance sums of squared residuals, loss = sum / (n_dists*ny*nx);
+ * may be page-locked host memory.
+ * want_grad = 0: forward only, no gradient buffer is touched.
+ * want_grad = 1: grad_obj [ny][nx][2]: delta channel += dL/ddelta, beta channel untouched; grad_lg_kappa [1] += dL/dlg_kappa.
+ * want_grad = 2: delta channel = dL/ddelta, beta channel = +0; grad_lg_kappa [1] = dL/dlg_kappa.
+ * grad_lg_kappa, pred, loss_sum: NULL where not wanted (grad_obj too when want_grad = 0).  Two launches give the same bits. */
+int adm_ctf_fwd_adj(adm_ctf* h, const float* obj, const double* dists_cm, const float* lg_kappa, const float* data,
+                    int want_grad, float* grad_obj, float* grad_lg_kappa, float* pred, float* loss_sum);
 
 /* y[i] += a * x[i]  (gradient accumulation, adorym/ptychography.py:1063-1066) */
 int adm_axpy(adm_ctx* ctx, float* y, const float* x, float a, size_t n);
