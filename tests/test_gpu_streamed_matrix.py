@@ -62,22 +62,34 @@ def sparse_case(name):
 
 # ------------------------------------------------------------------------------------------------------------ band-wise bars
 def _band_sums(a, axis, bands, shift):
-    """Sums of the non-negative [Py, Px] array ``a`` over every band of ``axis``.  ``shift``: the bands are intervals of the
-    natural-order spectrum index k, which the far-field detector shows at pixel (k + N/2) % N."""
-    line = a.sum(1 - axis)
-    if shift:
-        line = np.roll(line, -(len(line) // 2))               # line[k] <- detector pixel (k + N/2) % N
+    """Sums of the non-negative [Py, Px] array ``a`` over every band of ``axis`` (None: the bands are intervals of the flattened
+    index ky * Px + kx).  ``shift``: the bands are intervals of the natural-order spectrum index k, which the far-field detector
+    shows at pixel (k + N/2) % N."""
+    if axis is None:
+        if shift:
+            a = np.roll(a, (-(a.shape[0] // 2), -(a.shape[1] // 2)), (0, 1))      # a[ky, kx] <- detector pixel ((ky + Py/2) % Py, ...)
+        line = a.reshape(-1)
+    else:
+        line = a.sum(1 - axis)
+        if shift:
+            line = np.roll(line, -(len(line) // 2))           # line[k] <- detector pixel (k + N/2) % N
     return np.add.reduceat(line, [lo for lo, _ in bands])
 
 
-def band_errors(x, x64, x32, shape, shifted):
-    """Per band (row groups, then column groups): the relative distance of ``x`` and of the oracle's fp32 run from the fp64
-    oracle, and which bands carry enough signal to be judged.  Arrays are [..., Py, Px]."""
+def geometry_bands(shape):
+    """The band sets of the streamed path: (name, axis, bands) of the row workgroups' rows and the column workgroups' columns."""
+    return (('row', 0, SM.row_bands(*shape)), ('col', 1, SM.col_bands(*shape)))
+
+
+def band_errors(x, x64, x32, shape, shifted, band_sets=None):
+    """Per band set (default: row groups, then column groups): the relative distance of ``x`` and of the oracle's fp32 run from
+    the fp64 oracle on every band, and which bands carry enough signal to be judged.  Arrays are [..., Py, Px]; ``band_sets``
+    holds (name, axis, bands), the bands tiling the axis (axis None: the flattened field) from 0 to its end."""
     Py, Px = shape
     sq = lambda d: (np.abs(d) ** 2).reshape(-1, Py, Px).sum(0)
     d, d32, n64 = sq(np.asarray(x) - x64), sq(np.asarray(x32) - x64), sq(x64)
     out = []
-    for axis, bands in ((0, SM.row_bands(Py, Px)), (1, SM.col_bands(Py, Px))):
+    for _, axis, bands in (geometry_bands(shape) if band_sets is None else band_sets):
         n = _band_sums(n64, axis, bands, shifted)
         judged = n >= 1e-6 * n.max()                              # norm >= 1e-3 of the largest band's
         with np.errstate(divide='ignore', invalid='ignore'):
@@ -87,21 +99,33 @@ def band_errors(x, x64, x32, shape, shifted):
     return out
 
 
-def check_bands(res, what):
-    """The 3x rule on every band: prediction (floor GENERIC['pred']) and probe gradient (floor GENERIC['grad_abs'], and below
-    GENERIC['grad'])."""
+def check_bands(res, what, band_sets=None, bars=BARS, without_signal=0.05, each=False):
+    """The 3x rule on every band: prediction (floor bars['pred']) and probe gradient (floor bars['grad_abs'], and below
+    bars['grad']).  ``band_sets``: as for band_errors; ``without_signal``: the share of a set's bands that may be without signal;
+    ``each``: every position's prediction and every mode's probe gradient on its own instead of their sums."""
     shape, far = res['kw']['shape'], res['kw']['free_prop'] == 'inf'
+    sets = geometry_bands(shape) if band_sets is None else band_sets
     worst = {}
-    for name, floor, cap, shifted in (('pred', BARS['pred'], None, far), ('gprobe', BARS['grad_abs'], BARS['grad'], False)):
-        for axis, (e, e32, judged) in zip(('row', 'col'), band_errors(res[name], res[name + '_o'], res[name + '_32'], shape, shifted)):
-            assert (~judged).sum() <= 0.05 * len(judged), (what, name, axis, 'bands without signal', int((~judged).sum()), len(judged))
-            margin = np.where(judged, e - (3 * e32 + floor), -np.inf)
-            k = int(np.argmax(margin))
-            worst[name, axis] = (k, len(e), float(e[k]), float(e32[k]))
-            print('%s %s %s bands: worst %d of %d: %.2e (fp32 oracle %.2e)' % ((what, name, axis) + worst[name, axis]))
-            assert margin[k] <= 0, (what, name, axis, 'band %d of %d' % (k, len(e)), e[k], e32[k])
-            if cap is not None:
-                assert e[judged].max() < cap, (what, name, axis, e[judged].max())
+    for name, floor, cap, shifted in (('pred', bars['pred'], None, far), ('gprobe', bars['grad_abs'], bars['grad'], False)):
+        if res.get(name) is None:
+            continue                                              # (per-position probes: no probe gradient is formed)
+        arrays = [res[name], res[name + '_o'], res[name + '_32']]
+        items = [(name, arrays)] if not each else [('%s[%d]' % (name, k), [a[k] for a in arrays]) for k in range(len(arrays[0]))]
+        for item, (x, x64, x32) in items:
+            for (axis, _, _), (e, e32, judged) in zip(sets, band_errors(x, x64, x32, shape, shifted, sets)):
+                assert (~judged).sum() <= without_signal * len(judged), (what, item, axis, 'bands without signal', int((~judged).sum()), len(judged))
+                margin = np.where(judged, e - (3 * e32 + floor), -np.inf)
+                k = int(np.argmax(margin))
+                if (name, axis) not in worst or e[k] - 3 * e32[k] > worst[name, axis][2] - 3 * worst[name, axis][3]:
+                    worst[name, axis] = (k, len(e), float(e[k]), float(e32[k]))
+                if not each:
+                    print('%s %s %s bands: worst %d of %d: %.2e (fp32 oracle %.2e)' % ((what, name, axis) + worst[name, axis]))
+                assert margin[k] <= 0, (what, item, axis, 'band %d of %d' % (k, len(e)), e[k], e32[k])
+                if cap is not None:
+                    assert e[judged].max() < cap, (what, item, axis, e[judged].max())
+    if each:
+        for (name, axis), w in worst.items():
+            print('%s %s %s bands: worst %d of %d: %.2e (fp32 oracle %.2e)' % ((what, name, axis) + w))
     return worst
 
 
