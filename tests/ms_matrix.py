@@ -105,15 +105,19 @@ def run_case(A, ctx, P, **kw):
 
 def oracle_case(P, S=5, B=11, n_modes=1, unknown_type='delta_beta', binning=1, transmission_cache=True, free_prop='inf',
                 sign_convention=1, normalize_fft=False, fresnel_approx=True, loss='lsq', raw_data_type='magnitude', poisson_multiplier=1.,
-                beamstop=False, pp=None, generic=False, margin=(9, 13), seed=0, obj_fn=None, meas_edit=None, shifts_fn=None, probe_edit=None):
+                beamstop=False, pp=None, generic=False, margin=(9, 13), seed=0, obj_fn=None, meas_edit=None, shifts_fn=None, probe_edit=None,
+                index_fn=None):
     """The inputs of one minibatch and the oracle's results on them.  ``P``: size or (Py, Px); ``free_prop``: 'inf', 0, a distance
     in cm or a list of distances (position b uses distance b % n); ``pp``: None (one shared probe set), 'shifts' (Fourier-shifted per
     position, gradients w.r.t. the probe and the shifts) or 'probes' (a probe set per position handed over as it is).
     ``beamstop``: True (a disc and the first row dropped) or a [Py, Px] mask of its own.  A case may supply its own numbers
     (tests/value_matrix.py): ``obj_fn(r, Y, X, S) -> (obj, truth)`` in place of the weak object drawn here, ``meas_edit(meas,
     beamstop) -> meas`` applied to the measured data, ``shifts_fn(n_entries) -> [n_entries, 2]`` in place of the shifts within
-    2.5 px, ``probe_edit(probes) -> probes`` applied to the shared probe set.  The defaults draw what they always drew, bit for bit.
-    Returns a dict of the inputs and the oracle results (``*_o`` fp64, ``*_32`` fp32); run_engine adds the engine's (``*``)."""
+    2.5 px, ``probe_edit(probes) -> probes`` applied to the shared probe set, ``index_fn(B) -> (n_entries, index [B] or None)`` in
+    place of the max(2, B - 4) shift entries of which some are used twice (tests/count_matrix.py; an index of None: B entries,
+    position b uses entry b and the engine gets no index).  The defaults draw what they always drew, bit for bit.
+    Returns a dict of the inputs and the oracle results (``*_o`` fp64, ``*_32`` fp32; ``loss_b_*``: every position's own loss, which
+    times ``n_det`` is the engine's loss sum of that position); run_engine adds the engine's (``*``)."""
     Py, Px = (P, P) if np.isscalar(P) else tuple(P)
     r = np.random.default_rng([Py, Px, S, B, n_modes, binning, seed])
     Y, X = Py + margin[0], Px + margin[1]
@@ -143,13 +147,16 @@ def oracle_case(P, S=5, B=11, n_modes=1, unknown_type='delta_beta', binning=1, t
         bs[-1, :] = 3e-5                                    # above it: in, with weight 1
     shifts = idx = None
     if pp == 'shifts':
-        n_ent = max(2, B - 4)
+        n_ent, idx = (max(2, B - 4), None) if index_fn is None else index_fn(B)
         shifts = r.uniform(-2.5, 2.5, (n_ent, 2))
         shifts[0] = (1.75, -2.25)
         shifts[1] = (-1.5, 0.6)
         if shifts_fn is not None:
             shifts = np.asarray(shifts_fn(n_ent), np.float64)
-        idx = np.concatenate([np.arange(n_ent), r.integers(0, n_ent, B - n_ent)]).astype(np.int32)   # some entries twice
+        if index_fn is None:
+            idx = np.concatenate([np.arange(n_ent), r.integers(0, n_ent, B - n_ent)]).astype(np.int32)   # some entries twice
+        no_index = idx is None
+        idx = np.arange(B, dtype=np.int32) if no_index else np.asarray(idx, np.int32)
         pprobes = np.stack([O.fourier_shift(probes, shifts[e], 'float64') for e in idx])              # [B, M, Py, Px]
     elif pp == 'probes':
         pprobes = rand_probes(B, M)
@@ -172,7 +179,7 @@ def oracle_case(P, S=5, B=11, n_modes=1, unknown_type='delta_beta', binning=1, t
     out = {}
     for dt, sfx in (('float64', '_o'), ('float32', '_32')):
         tiles, _ = O.extract_tiles(obj.astype(dt), pos, (Py, Px), unknown_type)
-        lsum, preds, gts = 0., [], []
+        lsum, lpos, preds, gts = 0., [], [], []
         gp = np.zeros((M, Py, Px), complex)
         gpb = np.zeros((B, M, Py, Px), complex)
         gs = np.zeros((0 if shifts is None else len(shifts), 2))
@@ -187,16 +194,21 @@ def oracle_case(P, S=5, B=11, n_modes=1, unknown_type='delta_beta', binning=1, t
                 l, pr, gt, g = O.forward_adjoint_tiles(tiles[b:b + 1], pprobes[b], mb, ph, dt, **lkw)
                 gp += g
             lsum += l
+            lpos.append(l)
             preds.append(pr)
             gts.append(gt)
         out['loss' + sfx] = lsum / B
+        out['loss_b' + sfx] = np.array(lpos, np.float64)     # every position's own loss (a mean over its judged detector pixels)
         out['pred' + sfx] = np.concatenate(preds)
         out['grad' + sfx] = O.scatter_tiles_adj(np.concatenate(gts), pos, obj.shape) / B
         out['gprobe' + sfx] = gp / B
         out['gprobe_b' + sfx] = gpb / B
         out['gshift' + sfx] = gs / B
 
-    out.update(obj=obj, pos=pos, probes=probes, pprobes=pprobes, target=target, beamstop=bs, shifts=shifts, idx=idx,
+    if pp == 'shifts' and no_index:
+        idx = None
+    out.update(obj=obj, pos=pos, probes=probes, pprobes=pprobes, target=target, beamstop=bs, shifts=shifts, idx=idx, meas=meas,
+               n_det=Py * Px if bs is None else int((np.asarray(bs) >= 1e-5).sum()),
                kw=dict(S=S, B=B, n_modes=M, unknown_type=unknown_type, binning=binning, transmission_cache=transmission_cache,
                        free_prop=free_prop, sign_convention=sign_convention, normalize_fft=normalize_fft, fresnel_approx=fresnel_approx,
                        loss=loss, poisson_multiplier=poisson_multiplier, pp=pp, generic=generic, shape=(Py, Px)))
@@ -221,7 +233,7 @@ def run_engine(A, ctx, case):
     eng.rotate(ctx.array(obj, np.float32), None)
     if pp == 'shifts':
         d_gs = ctx.zeros(shifts.shape)
-        d_shifts, d_idx = ctx.array(shifts, np.float32), ctx.array(idx)
+        d_shifts, d_idx = ctx.array(shifts, np.float32), ctx.array(idx) if idx is not None else None
         eng.multislice(d_probe, grad_probe=d_gp, want_pred=True, shifts=d_shifts, shift_index=d_idx, grad_shifts=d_gs)
         out['gshift'] = d_gs.get()
         out['gprobe_b'] = cplx(eng._gprobes_b.get()[:B])          # the per-position probe gradients, before the shift adjoint
