@@ -370,6 +370,7 @@ extern "C" int adm_plan_destroy(adm_plan* plan) {
     if (plan->det_weight_dev) adm_free(plan->ctx, plan->det_weight_dev);
     if (plan->sp_hs_dev) adm_free(plan->ctx, plan->sp_hs_dev);
     if (plan->sp_a_dev) adm_free(plan->ctx, plan->sp_a_dev);
+    if (plan->fan_hs_dev) adm_free(plan->ctx, plan->fan_hs_dev);
     delete plan;
     return ADM_OK;
 }
@@ -422,6 +423,39 @@ extern "C" int adm_plan_set_detector_kernels(adm_plan* plan, int n, const float*
     return ADM_OK;
 }
 
+extern "C" int adm_plan_set_detector_fanout(adm_plan* plan, int n, const float* hfree_re, const float* hfree_im) {
+    if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_fanout: null plan");
+    if (!plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_fanout: a detector fan-out needs a streamed plan (adm_plan_create_streamed); "
+                                         "the one-workgroup kernels take several distances through adm_plan_set_detector_kernels");
+    if (plan->d.det_mode != ADM_DET_FRESNEL) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_fanout: the plan's det_mode is not ADM_DET_FRESNEL");
+    if (n != 0 && plan->exit_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_fanout: a detector fan-out on a plan with exit-wave shifts "
+                                         "(adm_plan_set_exit_shift) is not implemented");
+    if (n != 0 && plan->probe_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_fanout: a detector fan-out on a plan with probe shifts "
+                                         "(adm_plan_set_probe_shift) is not implemented");
+    if (n != 0 && plan->n_zpos > 0)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_fanout: a detector fan-out on a plan with slice positions "
+                                         "(sparse multislice) is not implemented");
+    if (n < 0 || n > 64) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_fanout: n must be in [1, 64] (0 switches the fan-out off)");
+    float2* hs = nullptr;
+    if (n > 0) {
+        if (!hfree_re || !hfree_im) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_fanout: null kernels");
+        const size_t npx = (size_t)plan->d.probe_y * plan->d.probe_x, tot = npx * (size_t)n;
+        std::vector<float> re(tot), im(tot);      // H_d / (Py*Px), one rounding per element, as plan_create forms hfree_s
+        for (size_t i = 0; i < tot; ++i) { re[i] = (float)((double)hfree_re[i] / (double)npx); im[i] = (float)((double)hfree_im[i] / (double)npx); }
+        const int rc = upload_c(plan->ctx, re.data(), im.data(), tot, &hs);
+        if (rc) return rc;
+    }
+    // (launches already queued on the plan's stream may still read the old kernels: free them behind those launches)
+    (void)hipStreamSynchronize(plan->ctx->stream);
+    if (plan->fan_hs_dev) adm_free(plan->ctx, plan->fan_hs_dev);
+    plan->fan_hs_dev = hs;
+    plan->n_fan = n;
+    return ADM_OK;
+}
+
 extern "C" size_t adm_plan_rot_elems(const adm_plan* plan) {
     if (!plan) return 0;
     return (size_t)plan->d.obj_z * plan->Yp * plan->Xp * 2;
@@ -452,7 +486,9 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     const size_t n_conv = sparse ? (size_t)plan->n_zpos - 1 : 0;
     const bool xshift = plan->streamed && plan->exit_shift;
     const bool pshift = plan->streamed && plan->probe_shift;
-    const bool dbl = sparse || xshift || pshift;       // the layout holds doubles
+    const bool fan = plan->streamed && plan->n_fan > 0;
+    const bool dbl = sparse || xshift || pshift || fan;       // the layout holds doubles (a fan-out: fields) behind the loss partials
+    const size_t E = fan ? B * (size_t)plan->n_fan : B;     // detector entries
     WsLayout w;
     size_t at = 0;
     auto take = [&at](size_t bytes) { const size_t off = at; at += bytes; return off; };
@@ -460,13 +496,13 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     w.gtile = take(B * pos);
     w.cover = take(lists);
     w.overflow = take(64);
-    w.det = take(B * M * det);
+    w.det = take(E * M * det);
     w.gprobe = take(B * M * fld);
     w.field = take(plan->streamed ? B * M * fld : 0);
     // The doubles of dd_part need 8-byte alignment, and MultisliceEngine.round_cap needs a total that is linear in the batch.
     // Every section is a multiple of 8 bytes per position except the loss partials, rounded up here on sparse plans, and the
     // cover lists, 0 or 4 mod 8 whatever the batch, made up for by a pad that does not depend on the batch either.
-    w.loss_part = take(B * (dbl ? (cg * sizeof(float) + 7) & ~(size_t)7 : cg * sizeof(float)));
+    w.loss_part = take(E * (dbl ? (cg * sizeof(float) + 7) & ~(size_t)7 : cg * sizeof(float)));
     if (dbl && lists % 8) at += 4;
     w.keep = take(n_conv * B * M * fld);
     w.dd_part = take(n_conv * B * M * cg * sizeof(double));
@@ -474,6 +510,8 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     w.xs_part = take(xshift ? B * M * cg * 2 * sizeof(double) : 0);
     w.ps_phat = take(pshift ? M * fld : 0);
     w.ps_part = take(pshift ? B * M * cg * 2 * sizeof(double) : 0);
+    w.fan_field = take(fan ? E * M * fld : 0);
+    w.fan_pos = take(fan ? E * sizeof(int2) : 0);
     w.total = at;
     return w;
 }
@@ -533,6 +571,9 @@ extern "C" int adm_plan_set_slice_positions(adm_plan* plan, const float* z_cm_de
     if (n != 0 && plan->probe_shift)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions together with probe shifts "
                                          "(adm_plan_set_probe_shift) are not implemented");
+    if (n != 0 && plan->n_fan > 0)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions together with a detector fan-out "
+                                         "(adm_plan_set_detector_fanout) are not implemented");
     if (n == 0) {
         plan->zpos_dev = nullptr;
         plan->n_zpos = 0;
@@ -573,6 +614,15 @@ extern "C" int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n) 
 // first if the slice positions changed), the kept spectra and the dL/dd partials.
 static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* ws, const WsLayout& w, float* grad_slice_pos,
                            const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift) {
+    StFanoutLaunch fo;
+    const bool fan = plan->n_fan > 0;
+    if (fan) {
+        fo.n = plan->n_fan; fo.hs = plan->fan_hs_dev;
+        fo.fld = (float2*)(ws + w.fan_field);
+        fo.det = (float2*)(ws + w.det);
+        fo.pos = (const int2*)(ws + w.fan_pos);
+        ADM_HIP(hipMemsetAsync(ws + w.fan_pos, 0, (size_t)batch * fo.n * sizeof(int2), plan->ctx->stream));
+    }
     StProbeShiftLaunch ps;
     if (pshift) {
         ps = *pshift;
@@ -604,7 +654,7 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
         sp.grad_z = grad_slice_pos;
     }
     ADM_HIP(ms_streamed_launch(p, batch, (float2*)(ws + w.field), (float*)(ws + w.loss_part), plan->ctx->stream, sparse ? &sp : nullptr,
-                               shift ? &xs : nullptr, pshift ? &ps : nullptr));
+                               shift ? &xs : nullptr, fan ? &fo : nullptr, pshift ? &ps : nullptr));
     return ADM_OK;
 }
 
@@ -741,6 +791,9 @@ extern "C" int adm_plan_set_exit_shift(adm_plan* plan, int on) {
                                          "are not implemented");
     if (on && plan->n_hfree > 1)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with several detector kernels are not implemented");
+    if (on && plan->n_fan > 0)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with a detector fan-out "
+                                         "(adm_plan_set_detector_fanout) are not implemented");
     if (on && plan->probe_shift)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with probe shifts (adm_plan_set_probe_shift) "
                                          "are not implemented");
@@ -776,6 +829,9 @@ extern "C" int adm_plan_set_probe_shift(adm_plan* plan, int on) {
                                          "are not implemented");
     if (on && plan->n_hfree > 1)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with several detector kernels are not implemented");
+    if (on && plan->n_fan > 0)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with a detector fan-out "
+                                         "(adm_plan_set_detector_fanout) are not implemented");
     plan->probe_shift = on != 0;
     return ADM_OK;
 }

@@ -54,6 +54,8 @@ struct adm_plan {
     float* sp_a_dev = nullptr;       // [Py] then [Px]: a_yx = sp_a[y] + sp_a[Py + x], the phase of H per nm
     bool exit_shift = false;         // adm_plan_set_exit_shift (streamed plans): the workspace holds the kept spectrum and the dL/ds partials
     bool probe_shift = false;        // adm_plan_set_probe_shift (streamed plans): the workspace holds FFT2(probe) and the dL/ds partials
+    int n_fan = 0;                   // adm_plan_set_detector_fanout (streamed plans): detector planes per position, 0 = off
+    float2* fan_hs_dev = nullptr;    // [n_fan][Py*Px] H_d / (Py*Px), one rounding per element
     // adm_tile_cover_build: the cover lists in workspace `ws` are current for (pos, batch, window); a few entries, so that every
     // round of a batch launched in parts can have its lists built ahead
     struct CoverKey { const void* ws; const void* pos; int batch, row0, nrows; unsigned long long fp; } cover_keys[4] = {};
@@ -70,22 +72,25 @@ int ms_r2_for(int n);
 size_t ms_row_elems(const adm_plan* plan);
 
 // The one description of a multislice workspace of `batch` positions: the byte offset of every section, in this order, and the
-// size of the whole.  M = n_modes, row = ms_row_elems float2, S = n_zpos, cg = ms_streamed_col_groups.
+// size of the whole.  M = n_modes, row = ms_row_elems float2, S = n_zpos, cg = ms_streamed_col_groups.  E = detector entries:
+// B, or B * n_fan on a plan with a detector fan-out.
 struct WsLayout {
     size_t stash;       // [B][M][n_steps][row] post-modulation wavefields
     size_t gtile;       // [B][n_steps][row] per-position tile gradients
     size_t cover;       // [Yp*Xp][1 + ADM_MAXCOVER] u32 cover lists of the overlap-add ...
     size_t overflow;    // ... and 64 bytes behind them whose first int is the overflow flag
-    size_t det;         // [B][M][G*NT or Py*Px] parked detector-plane fields (M > 1)
+    size_t det;         // [E][M][G*NT or Py*Px] parked detector-plane fields (M > 1)
     size_t gprobe;      // [B][M][Py][Px] per-position probe-gradient slots
     size_t field;       // streamed plans: [B][M][Py][Px] fields
-    size_t loss_part;   // streamed plans: [B][cg] float loss partials
+    size_t loss_part;   // streamed plans: [E][cg] float loss partials
     size_t keep;        // sparse plans (streamed, S >= 2): [B][M][S-1][Py][Px] kept spectra
     size_t dd_part;     // sparse plans: [S-1][B*M*cg] double dL/dd partials
     size_t xs_keep;     // plans with exit-wave shifts (streamed): [B][M][Py][Px] kept detector-step spectra
     size_t xs_part;     // plans with exit-wave shifts: [B*M*cg][2] double dL/ds partials
     size_t ps_phat;     // plans with probe shifts (streamed): [M][Py][Px] FFT2 of the probe modes
     size_t ps_part;     // plans with probe shifts: [B*M*cg][2] double dL/ds partials
+    size_t fan_field;   // plans with a detector fan-out (streamed): [E][M][Py][Px] detector-plane fields
+    size_t fan_pos;     // plans with a detector fan-out: [E] int2 zeros, the positions of the row launches over the detector fields
     size_t total;
 };
 WsLayout ws_layout(const adm_plan* plan, int batch);
@@ -94,6 +99,7 @@ hipError_t probe_grad_reduce(const float2* part, int batch, size_t n, float2* ou
 hipError_t probe_grad_reduce_large(float2* part, int batch, size_t n, float2* out, hipStream_t st);   // two levels, `part` is scratch
 hipError_t ms_launch(int n, const MsParams& p, int batch, hipStream_t st);
 struct StExitShiftLaunch;
+struct StFanoutLaunch;
 struct StProbeShiftLaunch;
 // adm_multislice_fwd_adj's body (per_position: one probe set per position)
 int multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch, const float* target,
@@ -153,11 +159,29 @@ struct StProbeShiftLaunch {
 };
 hipError_t ms_probeshift_spectrum_launch(const MsParams& p, float2* phat, hipStream_t st);
 hipError_t ms_probeshift_col_launch(const MsParams& p, int batch, float2* fld, bool conj, const StProbeShift& q, hipStream_t st);
+// one exit wave to several detector planes on streamed plans (adm_plan_set_detector_fanout, adm_ms_multidist.hip): the detector
+// step's column launches fan the B*M sweep fields out to B*D*M detector fields and back in
+struct StFanout {              // kernel argument
+    const float2* hs;          // [D][Py][Px] H_d / (Py*Px)
+    float2* dfld;              // [B][D][M][Py][Px] detector-plane fields
+    int n;                     // D
+};
+struct StFanoutLaunch {
+    int n; const float2* hs;
+    float2* fld;               // [B*D][M][Py][Px] detector-plane fields
+    float2* det;               // [B*D][M][Py][Px] the detector kernel's parked fields (M > 1), or nullptr
+    const int2* pos;           // [B*D] zeros
+    // (a distance gradient would add: float* grad_dists and a [B*M*column groups][D] partials buffer)
+};
+hipError_t ms_multidist_fanout_launch(const MsParams& p, int batch, const float2* fld, const StFanoutLaunch& fo, hipStream_t st);
+hipError_t ms_multidist_fanin_launch(const MsParams& p, int batch, float2* fld, const StFanoutLaunch& fo, hipStream_t st);
 // the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials;
 // sp: the tables of a sparse plan, or nullptr; xs: the exit-wave shifts of a plan with adm_plan_set_exit_shift, or nullptr; ps:
-// the probe shifts of a plan with adm_plan_set_probe_shift, or nullptr
+// the probe shifts of a plan with adm_plan_set_probe_shift, or nullptr; fo: the detector fan-out of a plan with
+// adm_plan_set_detector_fanout, or nullptr (part is then [B*D][col groups] and p.target / p.pred / p.loss_sum hold B*D entries)
 hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp = nullptr,
-                              const StExitShiftLaunch* xs = nullptr, const StProbeShiftLaunch* ps = nullptr);
+                              const StExitShiftLaunch* xs = nullptr, const StFanoutLaunch* fo = nullptr,
+                              const StProbeShiftLaunch* ps = nullptr);
 hipError_t shift_launch(int n, const ShiftParams& q, int batch, bool adjoint, hipStream_t st);
 inline int stream_grid(size_t n) {      // blocks of 256 threads for a grid-stride pass over n elements
     size_t b = (n + 255) / 256;

@@ -24,13 +24,14 @@
 //             col:     the conj(H) convolution between the steps
 //   then probe_grad_reduce sums the slots (adm_api.hip).
 // A plan with probe shifts (adm_plan_set_probe_shift) puts three launches in front of the sweep and up to three behind it
-// (adm_ms_probeshift.hip lists them).
+// (adm_ms_probeshift.hip lists them).  A plan with a detector fan-out (adm_plan_set_detector_fanout) replaces the Fresnel detector's
+// two column launches and runs the detector step over D entries per position (adm_ms_multidist.hip).
 //
 // Row launches: one workgroup per (position, group of whole rows), all modes in turn (the slice factors are loaded once and the
 // tile gradient of the modes is summed in registers).  Column launches: one workgroup per (position, mode, 8 adjacent columns;
 // 4 beyond Py = 1024): every row of the group is a 64-byte (32-byte) run.  Workspace rows (stash, tile gradients) are pixel-major [Py][Px] like the generic
 // kernel's, so the cover lists and the overlap-add (TileGeom::pixel_major) serve both.  What a column workgroup is made of (st_cw,
-// its threads and LDS, the load / store / transform helpers) is in adm_ms_col.h, shared with the two shift files.
+// its threads and LDS, the load / store / transform helpers) is in adm_ms_col.h, shared with the two shift files and adm_ms_multidist.hip.
 #include <hip/hip_runtime.h>
 #include "adm_host.h"
 #include "adm_ms_col.h"
@@ -417,7 +418,7 @@ hipError_t ms_sparse_anchor_launch(float* z, int n, hipStream_t st) {
 int ms_sparse_max_slices() { return ST_MAX_SLICES; }
 
 hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp,
-                              const StExitShiftLaunch* xs, const StProbeShiftLaunch* ps) {
+                              const StExitShiftLaunch* xs, const StFanoutLaunch* fo, const StProbeShiftLaunch* ps) {
     const int Py = p.gen_py, Px = p.gen_px, S = p.n_steps, M = p.n_modes;
     if (!ms_streamed_supported(Py, Px)) return hipErrorInvalidValue;
     // exit-wave shifts (adm_ms_exitshift.hip): a far-field magnitude does not see them; an exit-wave detector takes the Fresnel
@@ -467,6 +468,24 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         else hipLaunchKernelGGL(st_col_conv_sparse_kernel<false>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h, q);
         return hipGetLastError();
     };
+    // detector fan-out (adm_ms_multidist.hip): the detector step sends every sweep field to fo->n planes; the row launches around
+    // the detector kernel, that kernel and the loss reduction then run over the batch * fo->n detector entries
+    MsParams pd = p;
+    if (fo) { pd.pos = fo->pos; pd.det = fo->det; }
+    auto det_row_only = [&](int pre) {
+        StRow r;
+        r.rows = rows; r.step = 0; r.mode = 0; r.pre = pre; r.post = 0; r.from_probe = 0; r.to_gprobe = 0;
+        hipLaunchKernelGGL(st_row_kernel, dim3(batch * fo->n * ngr), dim3(ST_ROW_NT), 0, st, pd, r, fo->fld);
+        return hipGetLastError();
+    };
+    // (p, batch, fld: the sweep's own, or -- with a fan-out -- the detector entries'; the names of the outer ones on purpose)
+    auto detect = [&](const MsParams& p, int batch, float2* fld) {
+        hipLaunchKernelGGL(st_det_kernel, dim3(batch * ncg), dim3(cnt), clds + (size_t)Py * cg.cw * sizeof(float), st, p, fld, part);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(st_loss_reduce_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, part, ncg, batch, p.loss_sum);
+        return hipGetLastError();
+    };
     auto det_col = [&](bool conj) { return xs ? ms_exitshift_col_launch(p, batch, fld, hfree_s, conj, *xs, st) : col(hfree_s, conj); };
     hipError_t e = hipSuccess;
     // sub-pixel probe positions: Phat = FFT2(probe) once, then the fields of every (position, mode) up to their row IFFT, which
@@ -488,19 +507,17 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         if (e == hipSuccess && s < S - 1) e = conv(s, false);
     }
     if (e == hipSuccess && fresnel) {
-        e = det_col(false);
-        if (e == hipSuccess) e = row(0, 0, 2, 0, 0, 0);
+        e = fo ? ms_multidist_fanout_launch(p, batch, fld, *fo, st) : det_col(false);
+        if (e == hipSuccess) e = fo ? det_row_only(2) : row(0, 0, 2, 0, 0, 0);
     }
     if (e != hipSuccess) return e;
     // ---------------- detector, loss ----------------
-    hipLaunchKernelGGL(st_det_kernel, dim3(batch * ncg), dim3(cnt), clds + (size_t)Py * cg.cw * sizeof(float), st, p, fld, part);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(st_loss_reduce_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, part, ncg, batch, p.loss_sum);
-    if ((e = hipGetLastError()) != hipSuccess || !p.want_grad) return e;
+    e = fo ? detect(pd, batch * fo->n, fo->fld) : detect(p, batch, fld);
+    if (e != hipSuccess || !p.want_grad) return e;
     // ---------------- adjoint ----------------
     if (fresnel) {
-        e = row(0, 0, 1, 0, 0, 0);
-        if (e == hipSuccess) e = det_col(true);
+        e = fo ? det_row_only(1) : row(0, 0, 1, 0, 0, 0);
+        if (e == hipSuccess) e = fo ? ms_multidist_fanin_launch(p, batch, fld, *fo, st) : det_col(true);
     }
     const int adj_row = far ? (p.det_inverse ? 1 : 2) : (fresnel ? 2 : 0);
     // (probe shifts: the last row launch ends with the row FFT of the shift's adjoint and leaves the field in the buffer)

@@ -402,7 +402,8 @@ class PtychographyModel(ForwardModel):
                 self._grad_offset_dev = self.device.empty(offs.shape)
             goff = self._grad_offset_dev.zero_()
         mb = B // self.batch_group
-        gs = 2.0 / (mb * eng.n_det)     # each reference minibatch is a mean over ITS positions (and the kept detector pixels)
+        # each reference minibatch is a mean over ITS positions (their detector planes, with a fan-out) and the kept detector pixels
+        gs = 2.0 / (mb * eng.det_per_pos * eng.n_det)
         if want_grad and shifts is None and B > eng.N_CU and gz is None and offs is None:
             # no join here: the overlapped launch forks again, and the side stream is in order, so its overlap-adds queue
             # behind the regulariser kernel while the first round of workgroups already runs beside it
@@ -715,6 +716,12 @@ class MultiDistModel(PtychographyModel):
     a weak, homogeneous object, I_d = 1 + Re IFFT2(2 (sin xi_d + cos xi_d / kappa) FFT2(delta)) with kappa = 10^ctf_lg_kappa[0].
     ``common_vars_dict['ctf_engine']`` is an adorym_amd.CTFEngine; gradients w.r.t. obj (beta's is exactly zero) and ctf_lg_kappa
     come from adm_ctf_fwd_adj.  Neither the probe nor beta enters the model; one undivided field of view only.
+
+    A 3-D object (``two_d_mode=False``: holotomography, :905-914, 971-1019), one undivided field of view without a safe zone,
+    ``forward_algorithm='fresnel'``: ``common_vars_dict['engine']`` is a MultisliceEngine built with ``detector_fanout=True`` for
+    the sequence of distances and the whole field as its one position (0, 0).  The object is rotated with the angle's table as
+    PtychographyModel does, ONE launch runs the slice sweep once and sends the exit wave to every distance
+    (adm_plan_set_detector_fanout), and the rotation adjoint takes the gradient back; gradients w.r.t. obj and the probe.
     """
 
     PROJECTION_MODEL = 'multi-distance data (MultiDistModel)'
@@ -734,6 +741,8 @@ class MultiDistModel(PtychographyModel):
         self._data_key = None
         self._data_dev = None
         self._small = {}
+        # a 3-D object: the engine fans every exit wave out to all distances
+        self.fanout = bool(common_vars_dict) and not self.is_ctf and bool(getattr(self.engine, 'detector_fanout', False))
 
     def _check(self, safe_zone_width, ctf_lg_kappa, probe_pos_correction):
         cv = self.common_vars
@@ -754,7 +763,9 @@ class MultiDistModel(PtychographyModel):
             if probe_pos_correction is None:
                 raise ValueError('optimize_all_probe_pos needs probe_pos_correction [n_dists, 2]')
         if not cv.get('two_d_mode'):
-            raise NotImplementedError('MultiDistModel is accelerated for two_d_mode (one object slice) only')
+            return self._check_3d(safe_zone_width)
+        if self.fanout:
+            raise ValueError('MultiDistModel in two_d_mode takes a HolographyEngine (holo_engine), not an engine with detector_fanout')
         if self.tile_engine is not None:
             if int(safe_zone_width or 0) != int(cv.get('safe_zone_width') or 0):
                 raise ValueError('safe_zone_width differs from the width the tile engine was built for')
@@ -763,6 +774,32 @@ class MultiDistModel(PtychographyModel):
                     raise NotImplementedError('%s with multi-distance data divided into sub-tiles is outside the accelerated path' % flag)
         elif safe_zone_width not in (0, None):
             raise NotImplementedError('safe_zone_width > 0 needs the tile engine (the driver builds it)')
+
+    # what a 3-D object refuses by name: distances and registration are fixed, the field of view is undivided
+    REFUSED_3D_FLAGS = ('optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos', 'rotate_out_of_loop')
+
+    def _check_3d(self, safe_zone_width):
+        cv = self.common_vars
+        what = None
+        if self.tile_engine is not None or safe_zone_width not in (0, None) or int(cv.get('safe_zone_width') or 0) > 0:
+            what = 'data divided into sub-tiles or safe_zone_width > 0'
+        elif cv.get('unknown_type', 'delta_beta') == 'real_imag':
+            what = "unknown_type='real_imag'"
+        for flag in self.REFUSED_3D_FLAGS:
+            if what is None and cv.get(flag):
+                what = flag
+        if what is not None:
+            raise NotImplementedError('multi-distance holography of a 3-D object with %s is outside the accelerated path' % what)
+        if not self.fanout:
+            raise ValueError('MultiDistModel with two_d_mode=False needs common_vars_dict[\'engine\'] built with detector_fanout=True '
+                             '(an adorym_amd.MultisliceEngine for the sequence of distances)')
+
+    def _run_3d(self, obj, probe_real, probe_imag, this_i_theta, target, want_grad, **kw):
+        """PtychographyModel._run on the whole field as the one position (0, 0): rotate, one fan-out launch, rotation adjoint.
+        ``target`` None: this angle's holograms [n_dists, Y, X] (resident datasets: a view of the device copy)."""
+        if target is None:
+            target = self._target(this_i_theta, np.arange(self.engine.n_dists))
+        return PtychographyModel._run(self, obj, probe_real, probe_imag, this_i_theta, np.zeros((1, 2), int), target, want_grad, **kw)
 
     # what the CTF model refuses by name: it has no probe, one slice, one undivided field of view, fixed distances and no registration
     CTF_REFUSED_FLAGS = ('optimize_probe', 'optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos')
@@ -974,6 +1011,11 @@ class MultiDistModel(PtychographyModel):
         if self.is_ctf:
             self._run_ctf(obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad=False, want_pred=True)
             return self.ctf.pred()
+        if self.fanout:
+            # (distance-major like the reference's; for one block that is the launch's order)
+            zeros = np.zeros((self.engine.n_dists,) + tuple(self.engine.probe_size), np.float32)
+            self._run_3d(obj, probe_real, probe_imag, this_i_theta, zeros, want_grad=False, want_pred=True, regularize=False)
+            return self.engine.pred()
         if self.tile_engine is not None:
             return self._run_tiled(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, this_ind_batch, want_grad=False, want_pred=True)
         self._run(obj, probe_real, probe_imag, this_i_theta, free_prop_cm, prj_affine_ls, want_grad=False, want_pred=True,
@@ -988,6 +1030,10 @@ class MultiDistModel(PtychographyModel):
             if self.is_ctf:
                 self._run_ctf(obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad=False)
                 self.current_loss = float(self.ctf.loss() + self._regularize(obj, None))
+                return self.current_loss
+            if self.fanout:
+                self._run_3d(obj, probe_real, probe_imag, this_i_theta, None, want_grad=False)
+                self._queue_loss()
                 return self.current_loss
             if self.tile_engine is not None:
                 datav = self._run_tiled(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, this_ind_batch, want_grad=False)
@@ -1007,6 +1053,17 @@ class MultiDistModel(PtychographyModel):
         grad_obj (accumulated in place), probe_real/probe_imag -> one interleaved DeviceArray, free_prop_cm -> DeviceArray
         [n_dists], prj_affine_ls -> DeviceArray [n_dists,2,3]."""
         self._check(safe_zone_width, ctf_lg_kappa, probe_pos_correction)
+        if self.fanout:
+            i_pr, i_pi = self.get_argument_index('probe_real'), self.get_argument_index('probe_imag')
+            for i in opt_args_ls:
+                if i not in (0, i_pr, i_pi):
+                    raise NotImplementedError("multi-distance holography of a 3-D object: the gradient w.r.t. '%s' is outside the "
+                                              "accelerated path" % self.argument_ls[i])
+            gp, _ = self._run_3d(obj, probe_real, probe_imag, this_i_theta, None, want_grad=True, grad_obj=grad_obj,
+                                 want_probe_grad=(i_pr in opt_args_ls) or (i_pi in opt_args_ls), side_hook=_side_hook, init_grad=_init_grad)
+            self._queue_loss()          # self.current_loss fetches it on first access
+            # (probe_real and probe_imag reference ONE interleaved device array [1,Py,Px,2])
+            return tuple(grad_obj if i == 0 else gp for i in opt_args_ls)
         if _side_hook is not None:
             _side_hook()
         if self.is_ctf:

@@ -130,7 +130,7 @@ class MultisliceEngine(object):
                  fresnel_approx=True, sign_convention=1, normalize_fft=False, kernel=None, scale_ri_by_k=True,
                  n_probe_modes=1, max_batch=None, loss_function_type='lsq', poisson_multiplier=1., unknown_type='delta_beta',
                  beamstop=None, generic=False, transmission_cache=True, transmissions_only=False, streamed=False,
-                 workspace_budget=4 << 30, slice_pos_cm=None, exit_shift=False, probe_shift=False):
+                 workspace_budget=4 << 30, slice_pos_cm=None, exit_shift=False, probe_shift=False, detector_fanout=False):
         """``free_prop_cm``: 0 / None (exit wave), 'inf' (far field), a distance in cm (Fresnel propagation to the detector), or
         a SEQUENCE of n distances: position b of every launch is propagated to distance b % n (multi-distance data divided into
         sub-tiles, adorym/forward_model.py:999-1018 -- the caller lists every tile n times in a row, ``n_dists`` = n).
@@ -140,7 +140,8 @@ class MultisliceEngine(object):
         probe size, else the latter.  ``self.streamed`` tells which.  A streamed engine runs a batch in rounds whose workspace
         fits ``workspace_budget`` bytes (a position keeps n_steps * Py * Px complex numbers per mode: 134 MB at 256 x 256 and
         256 slices); each round is overlap-added before the next reuses the workspace.  Streamed engines take one probe set
-        shared by all positions: no ``probes_b``, no multi-distance sequence, and ``shifts`` only with ``probe_shift``.
+        shared by all positions: no ``probes_b``, a multi-distance sequence only with ``detector_fanout``, and ``shifts`` only with
+        ``probe_shift``.
 
         ``probe_shift``: a streamed engine applies ``multislice(shifts=...)`` inside its sweep (adm_plan_set_probe_shift).  It does
         not change which plan 'auto' picks: on a one-workgroup plan it does nothing and adm_probe_shift serves ``shifts`` as
@@ -153,7 +154,13 @@ class MultisliceEngine(object):
 
         ``exit_shift``: the engine takes one sub-pixel offset per position for the field behind the last slice (per-angle
         projection alignment, adorym/propagate.py:260-261: ``multislice(exit_shifts=...)``).  Always the streamed plan, whatever
-        the probe size; not together with ``slice_pos_cm`` or a sequence of detector distances."""
+        the probe size; not together with ``slice_pos_cm`` or a sequence of detector distances.
+
+        ``detector_fanout``: with a sequence of D detector distances, EVERY position is propagated to all D of them behind ONE
+        slice sweep (multi-distance holography of a 3-D object, adorym/forward_model.py:971-1019; adm_plan_set_detector_fanout).
+        ``set_batch(pos, targets)`` then takes targets [B*D, Py, Px], position-major (entry b*D + d), predictions and loss sums
+        come back in that order, and the loss is the mean over all B*D entries.  Always the streamed plan; not together with
+        ``exit_shift``, ``probe_shift``, ``slice_pos_cm``, ``probes_b`` or ``shifts``."""
         self.ctx = ctx
         self.obj_size = tuple(int(v) for v in obj_size)
         self.probe_size = tuple(int(v) for v in probe_size)
@@ -186,6 +193,18 @@ class MultisliceEngine(object):
                                 sign_convention=sign_convention)
         if streamed not in (False, True, 'auto'):
             raise ValueError("streamed must be False, True or 'auto', got %r" % (streamed,))
+        self.detector_fanout = bool(detector_fanout)
+        if self.detector_fanout:
+            for flag, name in ((exit_shift, 'exit_shift'), (probe_shift, 'probe_shift'), (slice_pos_cm is not None, 'slice_pos_cm')):
+                if flag:
+                    raise NotImplementedError('detector_fanout together with %s is not implemented' % name)
+            if not dists or len(dists) < 2:
+                raise ValueError('detector_fanout needs a sequence of at least two detector distances in free_prop_cm, got %r'
+                                 % (free_prop_cm,))
+            if streamed is False:
+                raise NotImplementedError('detector_fanout needs the streamed plan (streamed=True)')
+            streamed = True                   # (the one path whose detector step is a launch of its own)
+        self.det_per_pos = self.n_dists if self.detector_fanout else 1      # detector entries (targets, predictions, loss sums) per position
         if slice_pos_cm is not None:
             slice_pos_cm = np.asarray(slice_pos_cm, dtype=np.float64).reshape(-1)
             if len(slice_pos_cm) != self.obj_size[2]:
@@ -233,8 +252,11 @@ class MultisliceEngine(object):
         if self.probe_shift:
             check(ctx.lib.adm_plan_set_probe_shift(self.plan.handle, 1))
         if dists and len(dists) > 1:
-            self.plan.set_detector_kernels([get_kernel(d_ * 1e7, lmbda_nm, voxel_nm, self.probe_size, sign_convention=sign_convention)
-                                            for d_ in dists])
+            kernels = [get_kernel(d_ * 1e7, lmbda_nm, voxel_nm, self.probe_size, sign_convention=sign_convention) for d_ in dists]
+            if self.detector_fanout:
+                self.plan.set_detector_fanout(kernels)
+            else:
+                self.plan.set_detector_kernels(kernels)
         if generic and not self.streamed:
             self.plan.set_generic(True)       # the any-size kernel even where a tuned one exists (tests, A/B timing)
         # slice transmissions cached per rotated-frame voxel by rotate() (include/adm.h: adm_plan_set_transmission_cache)
@@ -312,21 +334,22 @@ class MultisliceEngine(object):
         ws_batch = min(batch, self.round_cap()) if self.streamed else batch      # streamed: one round's workspace
         self._ws = DeviceArray(self.ctx, (self.plan.workspace_bytes(ws_batch),), np.uint8)
         self._pos = DeviceArray(self.ctx, (batch, 2), np.int32)
-        self._target = DeviceArray(self.ctx, (batch, Py, Px), np.float32)
-        self._pred = DeviceArray(self.ctx, (batch, Py, Px), np.float32)
+        ent = batch * self.det_per_pos
+        self._target = DeviceArray(self.ctx, (ent, Py, Px), np.float32)
+        self._pred = DeviceArray(self.ctx, (ent, Py, Px), np.float32)
         # The per-position loss sums are written by the kernel straight into page-locked HOST memory (MappedArray): no
         # device-to-host copy is ever queued (the 4.5 us blit kernel and its dependency gap sat in every minibatch of the
         # launch-bound paths).  Two buffers, written alternately by successive launches, each with an event that is recorded
         # LATER -- beside launch k+1, see loss_async -- and tells the host that launch k's sums have arrived.
         from .device import MappedArray, Event
-        self._loss_pair = [MappedArray(self.ctx, (batch,), np.float32) for _ in range(2)]
+        self._loss_pair = [MappedArray(self.ctx, (ent,), np.float32) for _ in range(2)]
         self._loss_events = [Event(self.ctx) for _ in range(2)]
         self._loss_tokens = [None, None]
         self._loss_k = 0
         self._loss = self._loss_pair[0]
         self._deferred_loss = None
         # pinned staging for the per-minibatch uploads (targets, positions): asynchronous, the host never drains the stream
-        self._ring = UploadRing(self.ctx, batch * Py * Px * 4, n_slots=4)
+        self._ring = UploadRing(self.ctx, ent * Py * Px * 4, n_slots=4)
         self.max_batch = batch
 
     def cacheless_plan(self):
@@ -366,7 +389,7 @@ class MultisliceEngine(object):
 
     def set_batch(self, pos_batch, target):
         """Upload the probe positions [B,2] and target magnitudes [B,Py,Px] of the next minibatch
-        (target may already be a DeviceArray)."""
+        (target may already be a DeviceArray).  With ``detector_fanout``: targets [B*D,Py,Px], position-major."""
         pos = np.ascontiguousarray(np.round(np.asarray(pos_batch)).astype(np.int32).reshape(-1, 2))
         B = len(pos)
         self._reserve(B)
@@ -397,8 +420,11 @@ class MultisliceEngine(object):
         if isinstance(target, DeviceArray):
             self._cur_target = target
         else:
-            self._cur_target = self._target.view(0, (B,) + self.probe_size)
-            self._ring.upload(self._cur_target, np.asarray(target, dtype=np.float32))
+            self._cur_target = self._target.view(0, (B * self.det_per_pos,) + self.probe_size)
+            host = np.asarray(target, dtype=np.float32)
+            if host.size != self._cur_target.size:
+                raise ValueError('set_batch: targets must hold %d x %d x %d values, got %d' % ((B * self.det_per_pos,) + self.probe_size + (host.size,)))
+            self._ring.upload(self._cur_target, host)
         self._B = B
         return B
 
@@ -449,8 +475,12 @@ class MultisliceEngine(object):
         B = self._B
         Py, Px = self.probe_size
         if grad_scale is None:
-            grad_scale = 2.0 / (B * self.n_det)       # d mean((pred-target)^2) / d pred
+            grad_scale = 2.0 / (B * self.det_per_pos * self.n_det)       # d mean((pred-target)^2) / d pred
         lib = self.ctx.lib
+        if self.detector_fanout:
+            for other, name in ((shifts, 'shifts'), (probes_b, 'probes_b'), (exit_shifts, 'exit_shifts')):
+                if other is not None:
+                    raise NotImplementedError('detector_fanout together with %s is not implemented' % name)
         xs = None
         if exit_shifts is not None:
             for other, name in ((shifts, 'shifts'), (probes_b, 'probes_b'), (self.slice_pos, 'slice_pos_cm')):
@@ -525,10 +555,11 @@ class MultisliceEngine(object):
 
     def _ms_args(self, probe, grad_probe, want_grad, want_pred, grad_scale, o, n, ws):
         """The arguments of adm_multislice_fwd_adj[_pp] for positions [o, o + n) of the batch, launched into workspace ``ws``."""
-        px = 4 * o * self.probe_size[0] * self.probe_size[1]
+        e = o * self.det_per_pos              # the first detector entry of position o
+        px = 4 * e * self.probe_size[0] * self.probe_size[1]
         return (self.plan.handle, self.obj_rot.ptr, probe.ptr, self._cur_pos.ptr + 8 * o, n, self._cur_target.ptr + px,
                 1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
-                self._pred.ptr + px if want_pred else None, self._loss.ptr + 4 * o, float(grad_scale), ws.ptr, ws.nbytes)
+                self._pred.ptr + px if want_pred else None, self._loss.ptr + 4 * e, float(grad_scale), ws.ptr, ws.nbytes)
 
     def _launch(self, args, grad_slice_pos=None, xs=None, o=0, ps=None):
         """``xs``: (exit_shifts, exit_shift_index, grad_exit_shifts) of the whole batch, ``ps``: (shifts, shift_index, grad_shifts) of
@@ -680,7 +711,7 @@ class MultisliceEngine(object):
     def loss(self, last=None):
         """mean of the per-pixel loss terms over the batch (adorym/forward_model.py:88-103) -- blocks.
         ``last=n``: over the last n positions only (the final minibatch of a fused 'per angle' group)."""
-        B = self._B
+        B, last = self._B * self.det_per_pos, None if last is None else last * self.det_per_pos
         self._check_overflow()
         sums = self._loss.view(0, (B,)).get().astype(np.float64)
         if last is not None:
@@ -708,7 +739,8 @@ class MultisliceEngine(object):
         whichever comes first."""
         if self._deferred_loss is not None:
             self.flush_loss_copy()
-        token = {'k': self._loss_k, 'B': self._B, 'last': last, 'sums': None, 'recorded': False,
+        per = self.det_per_pos                # (the token counts detector entries)
+        token = {'k': self._loss_k, 'B': self._B * per, 'last': None if last is None else last * per, 'sums': None, 'recorded': False,
                  'buf': self._loss, 'ev': self._loss_events[self._loss_k]}      # (its own buffer and event: _reserve may replace the pair)
         self._loss_tokens[self._loss_k] = token
         self._deferred_loss = token
@@ -741,11 +773,11 @@ class MultisliceEngine(object):
         return float(sums.sum() / (len(sums) * self.n_det))
 
     def loss_sums(self, n):
-        """The first n per-position sums of the last launch (blocks)."""
+        """The first n per-entry sums of the last launch (blocks)."""
         return self._loss.view(0, (n,)).get().astype(np.float64)
 
     def pred(self):
-        return self._pred.view(0, (self._B,) + self.probe_size).get()
+        return self._pred.view(0, (self._B * self.det_per_pos,) + self.probe_size).get()
 
     # -------------------------------------------------------------------------------- whole step
     def loss_and_grad(self, obj, grad_obj, coords, probe, pos_batch, target, grad_probe=None, footprint=True):

@@ -443,16 +443,25 @@ class _Run(object):
                               'shift of the exit wave, so the gradient is zero and the offsets cannot move.', UserWarning)
         self.is_ctf = self.forward_algorithm == 'ctf'
         _not_implemented(self.is_ctf and not self.is_multi_dist, "forward_algorithm='ctf'")
-        self.holo_tiled = False
+        self.holo_tiled = self.holo_3d = False
         if self.is_multi_dist:
-            # one object slice; config 5 is one undivided field of view (n_blocks == 1) without a safe zone
+            # config 5 is one object slice and one undivided field of view (n_blocks == 1) without a safe zone
             free_prop_cm = self.free_prop_cm = np.asarray(self.free_prop_cm, dtype=float).reshape(-1)
             n_dists = self.n_dists = len(free_prop_cm)
             safe_zone_width = self.safe_zone_width = int(self.safe_zone_width or 0)
             if prj.shape[1] != n_dists * len(probe_pos):
                 raise ValueError('multi-distance data: prj.shape[1] = %d is not n_dists x n_blocks = %d x %d' % (prj.shape[1], n_dists, len(probe_pos)))
-            _not_implemented(not self.two_d_mode, "forward_algorithm='ctf' with two_d_mode=False" if self.forward_algorithm == 'ctf'
-                             else 'multi-distance holography of a 3-D object')
+            _not_implemented(not self.two_d_mode and self.forward_algorithm == 'ctf', "forward_algorithm='ctf' with two_d_mode=False")
+            # a 3-D object (holotomography, adorym/forward_model.py:905-914, 971-1019): rotate, ONE slice sweep, the exit wave to
+            # every distance (MultisliceEngine(detector_fanout=True)); one undivided field of view, fixed distances, no registration
+            self.holo_3d = not self.two_d_mode
+            if self.holo_3d:
+                what = 'multi-distance holography of a 3-D object with %s'
+                _not_implemented(len(probe_pos) > 1 or safe_zone_width > 0, what % 'data divided into sub-tiles or safe_zone_width > 0')
+                for nm in ('optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos', 'rotate_out_of_loop'):
+                    _not_implemented(bool(getattr(self, nm)), what % nm)
+                _not_implemented(self.unknown_type == 'real_imag', what % "unknown_type='real_imag'")
+                _not_implemented(self.n_ranks > 1, what % 'more than one rank')
             _not_implemented(self.n_probe_modes != 1, "forward_algorithm='ctf' with n_probe_modes != 1" if self.forward_algorithm == 'ctf'
                              else 'several probe modes with multi-distance data')
             _not_implemented(self.loss_function_type != 'lsq', "forward_algorithm='ctf' with loss_function_type='%s'" % self.loss_function_type
@@ -513,7 +522,7 @@ class _Run(object):
         voxel_nm = np.array([self.psize_cm] * 3) * 1.e7 * self.ds_level
         self.lmbda_nm = 1240. / self.energy_ev
         self.h = get_kernel(voxel_nm[-1] * self.binning, self.lmbda_nm, voxel_nm, probe_size, fresnel_approx=self.fresnel_approx,
-                            sign_convention=self.sign_convention) if not self.is_multi_dist else None
+                            sign_convention=self.sign_convention) if (self.holo_3d or not self.is_multi_dist) else None
         self.probe_pos_int = np.round(self.probe_pos).astype(int)
         self.holo_engine = self.tile_engine = self.ctf_engine = None
         common = dict(sign_convention=self.sign_convention, scale_ri_by_k=self.scale_ri_by_k, unknown_type=self.unknown_type)
@@ -528,6 +537,12 @@ class _Run(object):
             self.engine = self.tile_engine = MultisliceEngine(
                 ctx, obj_size, tile_size, np.repeat(self.probe_pos_int - szw, self.n_dists, axis=0), self.energy_ev, self.psize_cm,
                 free_prop_cm=self.free_prop_cm, max_batch=self.minibatch_size * self.n_dists, beamstop=window, **common)
+        elif self.holo_3d:
+            # the whole field is the one position; the streamed plan's detector step fans the exit wave out to every distance
+            self.engine = MultisliceEngine(
+                ctx, obj_size, probe_size, self.probe_pos_int, self.energy_ev, self.psize_cm, free_prop_cm=self.free_prop_cm,
+                binning=self.binning, fresnel_approx=self.fresnel_approx, kernel=self.h, max_batch=1, beamstop=self.beamstop,
+                transmissions_only=self.forward_model == 'auto', streamed=True, detector_fanout=True, **common)
         elif self.is_multi_dist:
             if self.is_ctf:
                 from .holography import CTFEngine
@@ -1104,7 +1119,7 @@ class _Run(object):
         minibatch, no regulariser, constraint or mask on the object, plain Adam with common (b1, b2, eps) on the object and on
         whichever of free_prop_cm / prj_affine_ls are optimised: the steps run INSIDE the gradient launch group's last kernel
         (adm_holo_fwd_adj_adam; same arithmetic, same bits), no gradient is stored and no optimiser launch follows."""
-        if not (self.is_multi_dist and not self.holo_tiled and not self.is_ctf and self.builtin_model and init_grad and self.update_scheme == 'immediate'
+        if not (self.is_multi_dist and not self.holo_tiled and not self.holo_3d and not self.is_ctf and self.builtin_model and init_grad and self.update_scheme == 'immediate'
                 and self.optimize_object and self.n_ranks == 1 and self.flags == 0 and self.mask is None
                 and all(p.key in _HOLO_FUSED_SLOTS for p in self.small) and not self.forward_model.reg_list
                 and os.environ.get('ADM_HOLO_FUSED_ADAM', '1') == '1'):

@@ -437,6 +437,24 @@ int adm_multislice_fwd_adj_probe_shift(adm_plan* plan, const float* obj_rot, con
                                        float grad_scale, void* workspace, size_t workspace_bytes, const float* shifts,
                                        const int32_t* index, float* grad_shifts);
 
+/* ---- one exit wave to several detector planes (streamed plans) --------------------------
+ * Multi-distance holography of a 3-D object (adorym/forward_model.py:971-1019): the field behind the last slice is
+ * Fresnel-propagated to n detector planes, Psi_d = IFFT2( H_d * FFT2(Psi_S) ), and the slice sweep runs ONCE per position whatever
+ * n is, forward and adjoint (adm_plan_set_detector_kernels, by contrast, runs one whole sweep per detector entry).
+ * adm_plan_set_detector_fanout(plan, n, hfree_re, hfree_im): host [n][Py*Px], kernel d as adm_plan_desc.hfree_* would hold it
+ * for distance d; 1 <= n <= 64, and n = 0 (kernels may be NULL) switches the fan-out off.  The plan must be STREAMED
+ * (ADM_ERR_UNSUPPORTED otherwise) with det_mode ADM_DET_FRESNEL (ADM_ERR_INVALID otherwise), whose own hfree_* is then unused;
+ * plans with exit-wave shifts, probe shifts or slice positions are refused with ADM_ERR_UNSUPPORTED, and those setters refuse a
+ * plan with a fan-out.  Call it before the workspace is sized: adm_plan_workspace_bytes grows by the batch * n * n_modes
+ * detector-plane fields (and, with several modes, by the detector kernel's parked fields of the same size).
+ * On such a plan adm_multislice_fwd_adj takes `batch` positions and yields n consecutive detector entries per position:
+ *   target, pred  [batch * n][Py][Px], entry b * n + d = position b at distance d
+ *   loss_sum      [batch * n], the same order
+ * grad_scale multiplies every entry's loss gradient as always (the mean over batch * n * pixels is the caller's).  The adjoint is
+ * g_S = sum_d IFFT2( conj(H_d) FFT2(dL/dPsi_d) ), d ascending, no atomics: two calls give the same bits.  Tile gradients,
+ * grad_probe, the detector mask and the cover build are those of `batch` positions, unchanged. */
+int adm_plan_set_detector_fanout(adm_plan* plan, int n, const float* hfree_re, const float* hfree_im);
+
 /* ---- f2  sub-pixel probe positions -----------------------------------------------------
  * realign_image_fourier (adorym/util.py:380-397) applied to every probe mode for every position of a minibatch:
  *   probes_out[b][m] = IFFT2( exp(-2 PI i (fx*sx_b + fy*sy_b)) * FFT2(probe[m]) ),  PI = 3.14159265359, f = fftfreq.
