@@ -116,6 +116,8 @@ SIGNATURES = {
     'adm_plan_set_detector_mask': (_I, [_VP, _VP]),
     'adm_plan_set_detector_kernels': (_I, [_VP, C.c_int, _VP, _VP]),
     'adm_plan_set_detector_fanout': (_I, [_VP, C.c_int, _VP, _VP]),
+    'adm_plan_set_fanout_distances': (_I, [_VP, _VP, _I, _D, _D, _D]),
+    'adm_multislice_fwd_adj_fanout_dist': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _SZ, _VP]),
     'adm_plan_rot_elems': (_SZ, [_VP]),
     'adm_plan_workspace_bytes': (_SZ, [_VP, _I]),
     'adm_rotate_fwd': (_I, [_VP, _VP, _VP, _VP, _I, _I]),

@@ -371,6 +371,7 @@ extern "C" int adm_plan_destroy(adm_plan* plan) {
     if (plan->sp_hs_dev) adm_free(plan->ctx, plan->sp_hs_dev);
     if (plan->sp_a_dev) adm_free(plan->ctx, plan->sp_a_dev);
     if (plan->fan_hs_dev) adm_free(plan->ctx, plan->fan_hs_dev);
+    if (plan->fan_a_dev) adm_free(plan->ctx, plan->fan_a_dev);
     delete plan;
     return ADM_OK;
 }
@@ -453,6 +454,50 @@ extern "C" int adm_plan_set_detector_fanout(adm_plan* plan, int n, const float* 
     if (plan->fan_hs_dev) adm_free(plan->ctx, plan->fan_hs_dev);
     plan->fan_hs_dev = hs;
     plan->n_fan = n;
+    plan->fan_dists_dev = nullptr;      // (host-built kernels: the plan no longer follows a device array of distances)
+    plan->fan_dists_dirty = false;
+    return ADM_OK;
+}
+
+extern "C" int adm_plan_set_fanout_distances(adm_plan* plan, const float* dists_cm_dev, int n, double lambda_nm, double voxel_nm_y,
+                                             double voxel_nm_x) {
+    if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: null plan");
+    if (!plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_fanout_distances: a detector fan-out needs a streamed plan (adm_plan_create_streamed)");
+    if (plan->d.det_mode != ADM_DET_FRESNEL) return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: the plan's det_mode is not ADM_DET_FRESNEL");
+    if (plan->exit_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_fanout_distances: a detector fan-out on a plan with exit-wave shifts "
+                                         "(adm_plan_set_exit_shift) is not implemented");
+    if (plan->probe_shift)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_fanout_distances: a detector fan-out on a plan with probe shifts "
+                                         "(adm_plan_set_probe_shift) is not implemented");
+    if (plan->n_zpos > 0)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_fanout_distances: a detector fan-out on a plan with slice positions "
+                                         "(sparse multislice) is not implemented");
+    if (n < 1 || n > 64) return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: n must be in [1, 64]");
+    if (!dists_cm_dev) return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: null distances");
+    if (!(lambda_nm > 0) || !(voxel_nm_y > 0) || !(voxel_nm_x > 0))
+        return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: wavelength and voxel sizes must be positive");
+    if (!plan->fan_a_dev) {
+        const int rc = adm_malloc(plan->ctx, (size_t)(plan->d.probe_y + plan->d.probe_x) * sizeof(float), (void**)&plan->fan_a_dev);
+        if (rc) return rc;
+    }
+    if (n != plan->n_fan || !plan->fan_hs_dev) {       // (the table of another number of planes, or none yet)
+        const size_t npx = (size_t)plan->d.probe_y * plan->d.probe_x;
+        float2* hs = nullptr;
+        const int rc = adm_malloc(plan->ctx, (size_t)n * npx * sizeof(float2), (void**)&hs);
+        if (rc) return rc;
+        // (launches already queued on the plan's stream may still read the old table: free it behind those launches)
+        (void)hipStreamSynchronize(plan->ctx->stream);
+        if (plan->fan_hs_dev) adm_free(plan->ctx, plan->fan_hs_dev);
+        plan->fan_hs_dev = hs;
+    }
+    plan->n_fan = n;
+    plan->fan_dists_dev = dists_cm_dev;
+    plan->fd_lambda_nm = lambda_nm;
+    plan->fd_voxel_nm_y = voxel_nm_y;
+    plan->fd_voxel_nm_x = voxel_nm_x;
+    plan->fan_dists_dirty = true;
     return ADM_OK;
 }
 
@@ -512,6 +557,9 @@ WsLayout ws_layout(const adm_plan* plan, int batch) {
     w.ps_part = take(pshift ? B * M * cg * 2 * sizeof(double) : 0);
     w.fan_field = take(fan ? E * M * fld : 0);
     w.fan_pos = take(fan ? E * sizeof(int2) : 0);
+    const bool refine = fan && plan->fan_dists_dev;     // the distances are parameters: the kept spectra and the dL/dd partials
+    w.fan_keep = take(refine ? B * M * fld : 0);
+    w.fan_part = take(refine ? (size_t)plan->n_fan * B * M * cg * sizeof(double) : 0);
     w.total = at;
     return w;
 }
@@ -613,7 +661,7 @@ extern "C" int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n) 
 // The launch of a streamed plan: fields and loss partials from the layout; on a sparse plan also the tables of the gaps (rebuilt
 // first if the slice positions changed), the kept spectra and the dL/dd partials.
 static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* ws, const WsLayout& w, float* grad_slice_pos,
-                           const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift) {
+                           const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift, float* grad_dists) {
     StFanoutLaunch fo;
     const bool fan = plan->n_fan > 0;
     if (fan) {
@@ -622,6 +670,23 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
         fo.det = (float2*)(ws + w.det);
         fo.pos = (const int2*)(ws + w.fan_pos);
         ADM_HIP(hipMemsetAsync(ws + w.fan_pos, 0, (size_t)batch * fo.n * sizeof(int2), plan->ctx->stream));
+        if (plan->fan_dists_dev) {      // the distances live on the device: the table follows them, the gradient can be formed
+            if (plan->fan_dists_dirty) {
+                StDistGeom q;
+                q.py = plan->d.probe_y; q.px = plan->d.probe_x; q.n = plan->n_fan; q.sigma = (double)plan->d.sign_convention;
+                q.lambda_nm = plan->fd_lambda_nm; q.voxel_nm_y = plan->fd_voxel_nm_y; q.voxel_nm_x = plan->fd_voxel_nm_x;
+                ADM_HIP(ms_distgrad_table_launch(q, plan->fan_dists_dev, plan->fan_hs_dev, plan->fan_a_dev, plan->fan_a_dev + q.py,
+                                                 plan->ctx->stream));
+            }
+            plan->fan_dists_dirty = false;
+            if (grad_dists && p.want_grad) {
+                fo.grad_dists = grad_dists;
+                fo.keep = (float2*)(ws + w.fan_keep);
+                fo.part = (double*)(ws + w.fan_part);
+                fo.ay = plan->fan_a_dev;
+                fo.ax = plan->fan_a_dev + plan->d.probe_y;
+            }
+        }
     }
     StProbeShiftLaunch ps;
     if (pshift) {
@@ -661,7 +726,7 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
 int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
                          const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
                          float grad_scale, void* workspace, size_t workspace_bytes, bool per_position, float* grad_slice_pos,
-                         const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift) {
+                         const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift, float* grad_dists) {
     if (!plan || !obj_rot || !probe || !pos || !target || !loss_sum)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: null argument");
     if (batch <= 0) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: batch must be positive");
@@ -739,7 +804,7 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         for (int i = 0; i < 8; ++i) { p.gen_rx[i] = plan->gen_rx[i]; p.gen_ry[i] = plan->gen_ry[i]; }
         p.gen_twid_y = plan->twid_y_dev; p.gen_hs = plan->hs_dev; p.gen_hfree_s = plan->hfree_s_dev;
         if (plan->streamed) {
-            const int rc = streamed_launch(plan, p, batch, ws, w, grad_slice_pos, shift, pshift);
+            const int rc = streamed_launch(plan, p, batch, ws, w, grad_slice_pos, shift, pshift, grad_dists);
             if (rc) return rc;
         } else {
             ADM_HIP(ms_generic_launch(p, batch, plan->ctx->stream));
@@ -779,6 +844,18 @@ extern "C" int adm_multislice_fwd_adj_sparse(adm_plan* plan, const float* obj_ro
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_sparse: the plan has no slice positions (adm_plan_set_slice_positions)");
     return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
                            workspace_bytes, false, grad_slice_pos);
+}
+
+extern "C" int adm_multislice_fwd_adj_fanout_dist(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
+                                                  const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
+                                                  float grad_scale, void* workspace, size_t workspace_bytes, float* grad_dists_dev) {
+    if (plan && !plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, "adm_multislice_fwd_adj_fanout_dist: a detector fan-out needs a streamed plan "
+                                         "(adm_plan_create_streamed)");
+    if (plan && !(plan->n_fan > 0 && plan->fan_dists_dev))
+        return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_fanout_dist: the plan has no fan-out distances (adm_plan_set_fanout_distances)");
+    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
+                           workspace_bytes, false, nullptr, nullptr, nullptr, grad_dists_dev);
 }
 
 extern "C" int adm_plan_set_exit_shift(adm_plan* plan, int on) {

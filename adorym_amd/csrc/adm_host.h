@@ -56,6 +56,11 @@ struct adm_plan {
     bool probe_shift = false;        // adm_plan_set_probe_shift (streamed plans): the workspace holds FFT2(probe) and the dL/ds partials
     int n_fan = 0;                   // adm_plan_set_detector_fanout (streamed plans): detector planes per position, 0 = off
     float2* fan_hs_dev = nullptr;    // [n_fan][Py*Px] H_d / (Py*Px), one rounding per element
+    // adm_plan_set_fanout_distances: the distances of the fan-out are parameters that live on the device
+    const float* fan_dists_dev = nullptr;   // [n_fan] distances in cm, the CALLER's device buffer; nullptr = host-built kernels (above)
+    bool fan_dists_dirty = false;    // fan_hs_dev has to be rebuilt from fan_dists_dev before the next launch
+    double fd_lambda_nm = 0, fd_voxel_nm_y = 0, fd_voxel_nm_x = 0;
+    float* fan_a_dev = nullptr;      // [Py] then [Px]: a_yx = fan_a[y] + fan_a[Py + x], the phase of H_d per nm
     // adm_tile_cover_build: the cover lists in workspace `ws` are current for (pos, batch, window); a few entries, so that every
     // round of a batch launched in parts can have its lists built ahead
     struct CoverKey { const void* ws; const void* pos; int batch, row0, nrows; unsigned long long fp; } cover_keys[4] = {};
@@ -91,6 +96,8 @@ struct WsLayout {
     size_t ps_part;     // plans with probe shifts: [B*M*cg][2] double dL/ds partials
     size_t fan_field;   // plans with a detector fan-out (streamed): [E][M][Py][Px] detector-plane fields
     size_t fan_pos;     // plans with a detector fan-out: [E] int2 zeros, the positions of the row launches over the detector fields
+    size_t fan_keep;    // plans whose fan-out distances are refined (adm_plan_set_fanout_distances): [B][M][Py][Px] kept exit-wave spectra
+    size_t fan_part;    // plans whose fan-out distances are refined: [D][B*M*cg] double dL/dd partials
     size_t total;
 };
 WsLayout ws_layout(const adm_plan* plan, int batch);
@@ -105,7 +112,7 @@ struct StProbeShiftLaunch;
 int multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch, const float* target,
                     int want_grad, float* grad_probe, float* pred, float* loss_sum, float grad_scale, void* workspace,
                     size_t workspace_bytes, bool per_position, float* grad_slice_pos = nullptr,
-                    const StExitShiftLaunch* shift = nullptr, const StProbeShiftLaunch* pshift = nullptr);
+                    const StExitShiftLaunch* shift = nullptr, const StProbeShiftLaunch* pshift = nullptr, float* grad_dists = nullptr);
 bool ms_generic_supported(int py, int px);
 int ms_generic_threads(int py, int px);
 hipError_t ms_generic_launch(const MsParams& p, int batch, hipStream_t st);
@@ -171,10 +178,27 @@ struct StFanoutLaunch {
     float2* fld;               // [B*D][M][Py][Px] detector-plane fields
     float2* det;               // [B*D][M][Py][Px] the detector kernel's parked fields (M > 1), or nullptr
     const int2* pos;           // [B*D] zeros
-    // (a distance gradient would add: float* grad_dists and a [B*M*column groups][D] partials buffer)
+    // the distance gradient (adm_ms_distgrad.hip); grad_dists set = requested: the two launchers below hand over to that file
+    float* grad_dists = nullptr;      // [D] += dL/d distance (per cm), or nullptr
+    float2* keep = nullptr;    // [B][M][Py][Px] column-transformed spectra of the exit waves
+    double* part = nullptr;    // [D][B*M*column groups] dL/dd partials
+    const float* ay = nullptr; // [Py], [Px]: a_yx = ay[y] + ax[x]
+    const float* ax = nullptr;
 };
 hipError_t ms_multidist_fanout_launch(const MsParams& p, int batch, const float2* fld, const StFanoutLaunch& fo, hipStream_t st);
 hipError_t ms_multidist_fanin_launch(const MsParams& p, int batch, float2* fld, const StFanoutLaunch& fo, hipStream_t st);
+// the fan-out with the distances as parameters on the device (adm_plan_set_fanout_distances, adm_ms_distgrad.hip)
+struct StDistGeom { int py, px, n; double sigma, lambda_nm, voxel_nm_y, voxel_nm_x; };
+struct StDistGrad {            // kernel argument, beside StFanout
+    float2* keep;              // [B][M][Py][Px]
+    double* part;              // [D][B*M*column groups]
+    const float* ay;
+    const float* ax;
+};
+hipError_t ms_distgrad_table_launch(const StDistGeom& q, const float* dists_cm, float2* hs, float* ay, float* ax, hipStream_t st);
+hipError_t ms_distgrad_fanout_launch(const MsParams& p, int batch, const float2* fld, const StFanoutLaunch& fo, hipStream_t st);
+hipError_t ms_distgrad_fanin_launch(const MsParams& p, int batch, float2* fld, const StFanoutLaunch& fo, hipStream_t st);
+hipError_t ms_distgrad_sum_launch(const MsParams& p, int batch, const StFanoutLaunch& fo, hipStream_t st);
 // the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials;
 // sp: the tables of a sparse plan, or nullptr; xs: the exit-wave shifts of a plan with adm_plan_set_exit_shift, or nullptr; ps:
 // the probe shifts of a plan with adm_plan_set_probe_shift, or nullptr; fo: the detector fan-out of a plan with

@@ -1,5 +1,5 @@
 // The column workgroups of the streamed multislice path, defined once for the translation units that launch them
-// (adm_ms_streamed.hip, adm_ms_exitshift.hip, adm_ms_probeshift.hip, adm_ms_multidist.hip): how many adjacent columns a workgroup takes, its threads and
+// (adm_ms_streamed.hip, adm_ms_exitshift.hip, adm_ms_probeshift.hip, adm_ms_multidist.hip, adm_ms_distgrad.hip): how many adjacent columns a workgroup takes, its threads and
 // its LDS (st_col_geom, the one place where the launch geometry is computed), the LDS context and the load / store / transform
 // helpers of the kernels, fftfreq, and the fp64 workgroup sum of the gradient partials.
 #pragma once

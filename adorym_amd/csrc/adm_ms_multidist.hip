@@ -10,8 +10,8 @@
 //   fan-in   md_fanin_kernel: per d, ascending: column FFT of G_d's group (after the row FFT over the detector fields),
 //            acc += conj(H_d / (Py*Px)) * spectrum per element in registers; then one column IFFT, stored into sweep field (b, m):
 //            g_S = sum_d IFFT2( conj(H_d) FFT2(G_d) ).  A fixed order, no atomics.
-// At D = 1 both do exactly st_col_conv_kernel's arithmetic.  (dL/dd_d = -sum_k a_k Im(conj(Ghat_d,k) kept_d,k) would be formed
-// in md_fanin_kernel from the spectrum md_fanout_kernel holds; not built.)  The column-workgroup helpers: adm_ms_col.h.
+// At D = 1 both do exactly st_col_conv_kernel's arithmetic.  (dL/dd_d = -sum_k a_k Im(conj(Ghat_d,k) kept_d,k): the twins of these
+// kernels in adm_ms_distgrad.hip, to which the two launchers hand over when the gradient is requested.)  The helpers: adm_ms_col.h.
 #include <hip/hip_runtime.h>
 #include "adm_host.h"
 #include "adm_ms_col.h"
@@ -97,6 +97,7 @@ static hipError_t md_raise_lds() {
 }
 
 hipError_t ms_multidist_fanout_launch(const MsParams& p, int batch, const float2* fld, const StFanoutLaunch& fo, hipStream_t st) {
+    if (fo.grad_dists) return ms_distgrad_fanout_launch(p, batch, fld, fo, st);
     const StColGeom cg = st_col_geom(p.gen_py, p.gen_px);
     hipError_t e = md_raise_lds();
     if (e != hipSuccess) return e;
@@ -107,6 +108,7 @@ hipError_t ms_multidist_fanout_launch(const MsParams& p, int batch, const float2
 }
 
 hipError_t ms_multidist_fanin_launch(const MsParams& p, int batch, float2* fld, const StFanoutLaunch& fo, hipStream_t st) {
+    if (fo.grad_dists) return ms_distgrad_fanin_launch(p, batch, fld, fo, st);
     const StColGeom cg = st_col_geom(p.gen_py, p.gen_px);
     hipError_t e = md_raise_lds();
     if (e != hipSuccess) return e;

@@ -25,7 +25,8 @@
 //   then probe_grad_reduce sums the slots (adm_api.hip).
 // A plan with probe shifts (adm_plan_set_probe_shift) puts three launches in front of the sweep and up to three behind it
 // (adm_ms_probeshift.hip lists them).  A plan with a detector fan-out (adm_plan_set_detector_fanout) replaces the Fresnel detector's
-// two column launches and runs the detector step over D entries per position (adm_ms_multidist.hip).
+// two column launches and runs the detector step over D entries per position (adm_ms_multidist.hip; with the gradient w.r.t. the
+// distances requested: adm_ms_distgrad.hip, and one reduce launch at the end).
 //
 // Row launches: one workgroup per (position, group of whole rows), all modes in turn (the slice factors are loaded once and the
 // tile gradient of the modes is summed in registers).  Column launches: one workgroup per (position, mode, 8 adjacent columns;
@@ -539,6 +540,7 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         hipLaunchKernelGGL(st_sparse_reduce_kernel, dim3(1), dim3(256), 0, st, sp->part, batch * M * ncg, S - 1, sp->grad_z);
         e = hipGetLastError();
     }
+    if (e == hipSuccess && fo && fo->grad_dists) e = ms_distgrad_sum_launch(p, batch, *fo, st);
     if (e == hipSuccess && xs && xs->grad_shifts) {
         hipLaunchKernelGGL(st_shift_reduce_kernel, dim3(batch), dim3(256), 0, st, xs->part, batch, M * ncg, xs->index, xs->grad_shifts);
         e = hipGetLastError();

@@ -316,7 +316,8 @@ class PtychographyModel(ForwardModel):
 
     def _run(self, obj, probe_real, probe_imag, this_i_theta, this_pos_batch, target, want_grad, grad_obj=None,
              want_probe_grad=False, want_pred=False, probe_pos_correction=None, this_ind_batch=None, want_shift_grad=False,
-             side_hook=None, regularize=True, init_grad=False, want_slice_pos_grad=False, prj_pos_offset=None, want_offset_grad=False):
+             side_hook=None, regularize=True, init_grad=False, want_slice_pos_grad=False, prj_pos_offset=None, want_offset_grad=False,
+             want_dist_grad=False):
         """One evaluation.  Stream plan (same as bench.py): rotation on the main stream; then, on the context's side
         stream, ``side_hook()`` (the driver zeroes the gradient buffer / finishes the previous update there) and the
         regulariser gradient -- they only need the object -- while the multislice chain, which occupies `minibatch` of
@@ -393,6 +394,11 @@ class PtychographyModel(ForwardModel):
             if getattr(self, '_grad_slice_pos_dev', None) is None:
                 self._grad_slice_pos_dev = self.device.empty(eng.slice_pos.shape)
             gz = self._grad_slice_pos_dev.zero_()
+        gd = None
+        if want_dist_grad:              # (MultiDistModel, 3-D object: dL/d free_prop_cm, left in self._grad_dists_dev)
+            if getattr(self, '_grad_dists_dev', None) is None:
+                self._grad_dists_dev = self.device.empty(eng.dists.shape)
+            gd = self._grad_dists_dev.zero_()
         offs, oidx = self._offset_args(prj_pos_offset, this_i_theta, B)
         goff = None
         if want_offset_grad:            # (dL/d prj_pos_offset, dense [n_theta, 2], left in self._grad_offset_dev)
@@ -404,14 +410,14 @@ class PtychographyModel(ForwardModel):
         mb = B // self.batch_group
         # each reference minibatch is a mean over ITS positions (their detector planes, with a fan-out) and the kept detector pixels
         gs = 2.0 / (mb * eng.det_per_pos * eng.n_det)
-        if want_grad and shifts is None and B > eng.N_CU and gz is None and offs is None:
+        if want_grad and shifts is None and B > eng.N_CU and gz is None and offs is None and gd is None:
             # no join here: the overlapped launch forks again, and the side stream is in order, so its overlap-adds queue
             # behind the regulariser kernel while the first round of workgroups already runs beside it
             eng.multislice_overlapped(probe, grad_probe=gp, grad_scale=gs, want_pred=want_pred)
         else:
             eng.multislice(probe, grad_probe=gp, want_grad=want_grad, want_pred=want_pred, grad_scale=gs, shifts=shifts,
                            shift_index=idx, grad_shifts=gsh, accumulate=False, grad_slice_pos=gz, exit_shifts=offs,
-                           exit_shift_index=oidx, grad_exit_shifts=goff)
+                           exit_shift_index=oidx, grad_exit_shifts=goff, **({} if gd is None else dict(grad_dists=gd)))
             ctx.join()              # (the side stream's work is a fraction of the kernel's time: the join does not wait)
             if want_grad:
                 eng.accumulate_tiles()
@@ -721,7 +727,9 @@ class MultiDistModel(PtychographyModel):
     ``forward_algorithm='fresnel'``: ``common_vars_dict['engine']`` is a MultisliceEngine built with ``detector_fanout=True`` for
     the sequence of distances and the whole field as its one position (0, 0).  The object is rotated with the angle's table as
     PtychographyModel does, ONE launch runs the slice sweep once and sends the exit wave to every distance
-    (adm_plan_set_detector_fanout), and the rotation adjoint takes the gradient back; gradients w.r.t. obj and the probe.
+    (adm_plan_set_detector_fanout), and the rotation adjoint takes the gradient back; gradients w.r.t. obj and the probe.  An engine
+    built with ``refine_distances=True`` also serves ``optimize_free_prop``: ``free_prop_cm`` is then the engine's device array
+    ``engine.dists`` (the kernels follow it, adm_plan_set_fanout_distances) and the gradient w.r.t. it comes from the same launch.
     """
 
     PROJECTION_MODEL = 'multi-distance data (MultiDistModel)'
@@ -743,6 +751,8 @@ class MultiDistModel(PtychographyModel):
         self._small = {}
         # a 3-D object: the engine fans every exit wave out to all distances
         self.fanout = bool(common_vars_dict) and not self.is_ctf and bool(getattr(self.engine, 'detector_fanout', False))
+        # ... and holds them as parameters on the device (what the engine can do decides, not a flag of its own)
+        self.refine_3d = self.fanout and bool(getattr(self.engine, 'refine_distances', False))
 
     def _check(self, safe_zone_width, ctf_lg_kappa, probe_pos_correction):
         cv = self.common_vars
@@ -786,7 +796,7 @@ class MultiDistModel(PtychographyModel):
         elif cv.get('unknown_type', 'delta_beta') == 'real_imag':
             what = "unknown_type='real_imag'"
         for flag in self.REFUSED_3D_FLAGS:
-            if what is None and cv.get(flag):
+            if what is None and cv.get(flag) and not (flag == 'optimize_free_prop' and self.refine_3d):
                 what = flag
         if what is not None:
             raise NotImplementedError('multi-distance holography of a 3-D object with %s is outside the accelerated path' % what)
@@ -799,6 +809,10 @@ class MultiDistModel(PtychographyModel):
         ``target`` None: this angle's holograms [n_dists, Y, X] (resident datasets: a view of the device copy)."""
         if target is None:
             target = self._target(this_i_theta, np.arange(self.engine.n_dists))
+        fp = kw.pop('free_prop_cm', None)
+        if self.refine_3d and isinstance(fp, DeviceArray) and fp.ptr != self.engine.dists.ptr:
+            raise ValueError('multi-distance holography of a 3-D object with refined distances: free_prop_cm on the device must be '
+                             'the engine\'s own array (engine.dists)')
         return PtychographyModel._run(self, obj, probe_real, probe_imag, this_i_theta, np.zeros((1, 2), int), target, want_grad, **kw)
 
     # what the CTF model refuses by name: it has no probe, one slice, one undivided field of view, fixed distances and no registration
@@ -1014,7 +1028,8 @@ class MultiDistModel(PtychographyModel):
         if self.fanout:
             # (distance-major like the reference's; for one block that is the launch's order)
             zeros = np.zeros((self.engine.n_dists,) + tuple(self.engine.probe_size), np.float32)
-            self._run_3d(obj, probe_real, probe_imag, this_i_theta, zeros, want_grad=False, want_pred=True, regularize=False)
+            self._run_3d(obj, probe_real, probe_imag, this_i_theta, zeros, want_grad=False, want_pred=True, regularize=False,
+                         free_prop_cm=free_prop_cm)
             return self.engine.pred()
         if self.tile_engine is not None:
             return self._run_tiled(obj, probe_real, probe_imag, this_i_theta, this_pos_batch, this_ind_batch, want_grad=False, want_pred=True)
@@ -1032,7 +1047,7 @@ class MultiDistModel(PtychographyModel):
                 self.current_loss = float(self.ctf.loss() + self._regularize(obj, None))
                 return self.current_loss
             if self.fanout:
-                self._run_3d(obj, probe_real, probe_imag, this_i_theta, None, want_grad=False)
+                self._run_3d(obj, probe_real, probe_imag, this_i_theta, None, want_grad=False, free_prop_cm=free_prop_cm)
                 self._queue_loss()
                 return self.current_loss
             if self.tile_engine is not None:
@@ -1055,15 +1070,17 @@ class MultiDistModel(PtychographyModel):
         self._check(safe_zone_width, ctf_lg_kappa, probe_pos_correction)
         if self.fanout:
             i_pr, i_pi = self.get_argument_index('probe_real'), self.get_argument_index('probe_imag')
+            i_fp = self.get_argument_index('free_prop_cm')
             for i in opt_args_ls:
-                if i not in (0, i_pr, i_pi):
+                if i not in (0, i_pr, i_pi) and not (i == i_fp and self.refine_3d):
                     raise NotImplementedError("multi-distance holography of a 3-D object: the gradient w.r.t. '%s' is outside the "
                                               "accelerated path" % self.argument_ls[i])
             gp, _ = self._run_3d(obj, probe_real, probe_imag, this_i_theta, None, want_grad=True, grad_obj=grad_obj,
-                                 want_probe_grad=(i_pr in opt_args_ls) or (i_pi in opt_args_ls), side_hook=_side_hook, init_grad=_init_grad)
+                                 want_probe_grad=(i_pr in opt_args_ls) or (i_pi in opt_args_ls), side_hook=_side_hook, init_grad=_init_grad,
+                                 want_dist_grad=i_fp in opt_args_ls, free_prop_cm=free_prop_cm)
             self._queue_loss()          # self.current_loss fetches it on first access
-            # (probe_real and probe_imag reference ONE interleaved device array [1,Py,Px,2])
-            return tuple(grad_obj if i == 0 else gp for i in opt_args_ls)
+            # (probe_real and probe_imag reference ONE interleaved device array [1,Py,Px,2]; free_prop_cm: DeviceArray [n_dists])
+            return tuple(grad_obj if i == 0 else self._grad_dists_dev if i == i_fp else gp for i in opt_args_ls)
         if _side_hook is not None:
             _side_hook()
         if self.is_ctf:

@@ -130,7 +130,8 @@ class MultisliceEngine(object):
                  fresnel_approx=True, sign_convention=1, normalize_fft=False, kernel=None, scale_ri_by_k=True,
                  n_probe_modes=1, max_batch=None, loss_function_type='lsq', poisson_multiplier=1., unknown_type='delta_beta',
                  beamstop=None, generic=False, transmission_cache=True, transmissions_only=False, streamed=False,
-                 workspace_budget=4 << 30, slice_pos_cm=None, exit_shift=False, probe_shift=False, detector_fanout=False):
+                 workspace_budget=4 << 30, slice_pos_cm=None, exit_shift=False, probe_shift=False, detector_fanout=False,
+                 refine_distances=False):
         """``free_prop_cm``: 0 / None (exit wave), 'inf' (far field), a distance in cm (Fresnel propagation to the detector), or
         a SEQUENCE of n distances: position b of every launch is propagated to distance b % n (multi-distance data divided into
         sub-tiles, adorym/forward_model.py:999-1018 -- the caller lists every tile n times in a row, ``n_dists`` = n).
@@ -160,7 +161,13 @@ class MultisliceEngine(object):
         slice sweep (multi-distance holography of a 3-D object, adorym/forward_model.py:971-1019; adm_plan_set_detector_fanout).
         ``set_batch(pos, targets)`` then takes targets [B*D, Py, Px], position-major (entry b*D + d), predictions and loss sums
         come back in that order, and the loss is the mean over all B*D entries.  Always the streamed plan; not together with
-        ``exit_shift``, ``probe_shift``, ``slice_pos_cm``, ``probes_b`` or ``shifts``."""
+        ``exit_shift``, ``probe_shift``, ``slice_pos_cm``, ``probes_b`` or ``shifts``.
+
+        ``refine_distances`` (with ``detector_fanout`` only): the D distances are parameters (the reference's optimize_free_prop,
+        adorym/propagate.py:274-277, 556-568).  ``self.dists`` (DeviceArray float32 [D], cm) is the parameter itself; the Fresnel
+        kernels are built on the device from it (adm_plan_set_fanout_distances), whoever changes it in place calls
+        ``dists_changed()``, and ``multislice(grad_dists=...)`` accumulates dL/d dists.  Without it the kernels are built on the
+        host once, as always."""
         self.ctx = ctx
         self.obj_size = tuple(int(v) for v in obj_size)
         self.probe_size = tuple(int(v) for v in probe_size)
@@ -204,6 +211,9 @@ class MultisliceEngine(object):
             if streamed is False:
                 raise NotImplementedError('detector_fanout needs the streamed plan (streamed=True)')
             streamed = True                   # (the one path whose detector step is a launch of its own)
+        self.refine_distances = bool(refine_distances)
+        if self.refine_distances and not self.detector_fanout:
+            raise ValueError('refine_distances needs detector_fanout=True (a sequence of detector distances behind one slice sweep)')
         self.det_per_pos = self.n_dists if self.detector_fanout else 1      # detector entries (targets, predictions, loss sums) per position
         if slice_pos_cm is not None:
             slice_pos_cm = np.asarray(slice_pos_cm, dtype=np.float64).reshape(-1)
@@ -251,7 +261,12 @@ class MultisliceEngine(object):
         self.probe_shift = bool(probe_shift) and self.streamed
         if self.probe_shift:
             check(ctx.lib.adm_plan_set_probe_shift(self.plan.handle, 1))
-        if dists and len(dists) > 1:
+        self.dists = self._dist_args = None
+        if self.refine_distances:
+            self.dists = ctx.array(np.asarray(dists, dtype=np.float32))
+            self._dist_args = (float(lmbda_nm), float(voxel_nm[0]), float(voxel_nm[1]))
+            self.dists_changed()
+        elif dists and len(dists) > 1:
             kernels = [get_kernel(d_ * 1e7, lmbda_nm, voxel_nm, self.probe_size, sign_convention=sign_convention) for d_ in dists]
             if self.detector_fanout:
                 self.plan.set_detector_fanout(kernels)
@@ -310,6 +325,13 @@ class MultisliceEngine(object):
         if self.slice_pos is None:
             raise ValueError('slice_pos_changed: the engine has no slice positions')
         check(self.ctx.lib.adm_plan_set_slice_positions(self.plan.handle, self.slice_pos.ptr, self.slice_pos.size, *self._sparse_args))
+
+    def dists_changed(self):
+        """The values of ``dists`` were changed on the device: the Fresnel kernels of the detector planes are rebuilt from them in
+        front of the next launch (and kept until the next call)."""
+        if self.dists is None:
+            raise ValueError('dists_changed: the engine was built without refine_distances=True')
+        check(self.ctx.lib.adm_plan_set_fanout_distances(self.plan.handle, self.dists.ptr, self.dists.size, *self._dist_args))
 
     def anchor_slice_pos(self):
         """slice_pos <- slice_pos - slice_pos[0] on the device (adorym/optimizers.py:1059); the gaps do not change."""
@@ -452,7 +474,7 @@ class MultisliceEngine(object):
 
     def multislice(self, probe, grad_probe=None, want_grad=True, want_pred=False, grad_scale=None, accumulate=True,
                    shifts=None, shift_index=None, grad_shifts=None, probes_b=None, grad_slice_pos=None,
-                   exit_shifts=None, exit_shift_index=None, grad_exit_shifts=None):
+                   exit_shifts=None, exit_shift_index=None, grad_exit_shifts=None, grad_dists=None):
         """Launch the fused kernel on the batch given to set_batch().  Returns nothing; read
         results with loss() / pred().
 
@@ -471,7 +493,9 @@ class MultisliceEngine(object):
         ``exit_shifts`` (DeviceArray float32 [n_entries, 2] = (sy, sx); engines with ``exit_shift`` only): the field behind the
         last slice of position b is Fourier-shifted by entry ``exit_shift_index[b]`` (DeviceArray int32 [B]; None = b) before the
         detector step; ``grad_exit_shifts`` (float32 [n_entries, 2], +=) receives dL/d exit_shifts.  A far-field detector does
-        not see the shift: the gradient buffer is left as it is."""
+        not see the shift: the gradient buffer is left as it is.
+
+        ``grad_dists`` (DeviceArray float32 [D], +=; engines with ``refine_distances`` only): dL/d dists in 1/cm."""
         B = self._B
         Py, Px = self.probe_size
         if grad_scale is None:
@@ -481,6 +505,11 @@ class MultisliceEngine(object):
             for other, name in ((shifts, 'shifts'), (probes_b, 'probes_b'), (exit_shifts, 'exit_shifts')):
                 if other is not None:
                     raise NotImplementedError('detector_fanout together with %s is not implemented' % name)
+        if grad_dists is not None:
+            if self.dists is None:
+                raise ValueError('grad_dists: the engine was built without refine_distances=True')
+            if grad_dists.size != self.dists.size or grad_dists.dtype != np.float32:
+                raise ValueError('grad_dists must be float32 [%d]' % self.dists.size)
         xs = None
         if exit_shifts is not None:
             for other, name in ((shifts, 'shifts'), (probes_b, 'probes_b'), (self.slice_pos, 'slice_pos_cm')):
@@ -523,7 +552,7 @@ class MultisliceEngine(object):
         self._acc_done = False
         self._next_loss_buffer()
         if self.streamed and len(self.rounds(B)) > 1:
-            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos, xs, ps)
+            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos, xs, ps, grad_dists)
             return
         args = lambda pr_, gp_: self._ms_args(pr_, gp_, want_grad, want_pred, grad_scale, 0, B, self._ws)      # (the whole batch)
         if probes_b is not None:
@@ -533,7 +562,7 @@ class MultisliceEngine(object):
                 raise ValueError('probes_b must be [%d, %d, %d, %d, 2], got %r' % (B, self.n_probe_modes, Py, Px, tuple(probes_b.shape)))
             check(lib.adm_multislice_fwd_adj_pp(*args(probes_b, None)))
         elif shifts is None or ps is not None:
-            self._launch(args(probe, grad_probe), grad_slice_pos, xs, ps=ps)
+            self._launch(args(probe, grad_probe), grad_slice_pos, xs, ps=ps, grad_dists=grad_dists)
         else:
             M = self.n_probe_modes
             if self._probes_b is None or self._probes_b.shape[0] < B:
@@ -561,7 +590,7 @@ class MultisliceEngine(object):
                 1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
                 self._pred.ptr + px if want_pred else None, self._loss.ptr + 4 * e, float(grad_scale), ws.ptr, ws.nbytes)
 
-    def _launch(self, args, grad_slice_pos=None, xs=None, o=0, ps=None):
+    def _launch(self, args, grad_slice_pos=None, xs=None, o=0, ps=None, grad_dists=None):
         """``xs``: (exit_shifts, exit_shift_index, grad_exit_shifts) of the whole batch, ``ps``: (shifts, shift_index, grad_shifts) of
         a streamed engine with ``probe_shift``; the launch starts at position ``o`` of the batch."""
         if xs is not None or ps is not None:
@@ -572,6 +601,8 @@ class MultisliceEngine(object):
             check(fn(*(args + (s.ptr + so, idx.ptr + 4 * o if idx is not None else None, g.ptr + so if g is not None else None))))
         elif grad_slice_pos is not None:
             check(self.ctx.lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
+        elif grad_dists is not None:
+            check(self.ctx.lib.adm_multislice_fwd_adj_fanout_dist(*(args + (grad_dists.ptr,))))
         else:
             check(self.ctx.lib.adm_multislice_fwd_adj(*args))
 
@@ -587,16 +618,17 @@ class MultisliceEngine(object):
         for lo in range(0, n, self.MAX_COVER):
             check(lib.adm_tile_grad_accumulate_range(*(head + (lo, min(lo + self.MAX_COVER, n), 1 if add or lo else 0))))
 
-    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None, xs=None, ps=None):
+    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None, xs=None, ps=None,
+                           grad_dists=None):
         """A streamed engine's batch that does not fit the workspace budget: one launch per round into the same workspace, each
         round's tile gradients overlap-added into grad_rot (zeroed first) before the next round overwrites them.  Losses,
         predictions and the probe gradient are those of one launch; the object gradient too, up to the order of the additions.
-        Every round adds its share to ``grad_slice_pos`` and to the gradient of the exit-wave shifts ``xs`` or the probe shifts
-        ``ps``."""
+        Every round adds its share to ``grad_slice_pos``, to ``grad_dists`` and to the gradient of the exit-wave shifts ``xs`` or
+        the probe shifts ``ps``."""
         if want_grad:
             check(self.ctx.lib.adm_memset(self.ctx.handle, self.grad_rot.ptr, 0, self.grad_rot.nbytes))
         for o, n in self.rounds(self._B):
-            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), grad_slice_pos, xs, o, ps)
+            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), grad_slice_pos, xs, o, ps, grad_dists)
             if want_grad:
                 self._overlap_add(self._ws, o, n, 1, passes=self._check_cover(self._pos_host[o:o + n]) > self.MAX_COVER)
         # (every overlap-add above saw at most MAX_COVER tiles per pixel: nothing to check afterwards)

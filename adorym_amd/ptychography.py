@@ -322,6 +322,8 @@ class _Run(object):
         self.fuse_per_angle = kwargs.pop('fuse_per_angle', True)
         # sub-pixel probe positions on the streamed path (probes beyond 128 x 128): applied inside the sweep on request
         self.streamed_probe_shift = bool(kwargs.pop('streamed_probe_shift', False))
+        # optimize_free_prop for multi-distance data of a 3-D object (holotomography): the distances refined on the device, on request
+        self.fanout_free_prop = bool(kwargs.pop('fanout_free_prop', False))
         self.ops = kwargs.pop('ops', None)
         kwargs.pop('probe_size', None)
         self.kwargs = kwargs
@@ -459,7 +461,8 @@ class _Run(object):
                 what = 'multi-distance holography of a 3-D object with %s'
                 _not_implemented(len(probe_pos) > 1 or safe_zone_width > 0, what % 'data divided into sub-tiles or safe_zone_width > 0')
                 for nm in ('optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos', 'rotate_out_of_loop'):
-                    _not_implemented(bool(getattr(self, nm)), what % nm)
+                    # (fanout_free_prop=True: the engine holds the distances as parameters, MultisliceEngine(refine_distances=True))
+                    _not_implemented(bool(getattr(self, nm)) and not (nm == 'optimize_free_prop' and self.fanout_free_prop), what % nm)
                 _not_implemented(self.unknown_type == 'real_imag', what % "unknown_type='real_imag'")
                 _not_implemented(self.n_ranks > 1, what % 'more than one rank')
             _not_implemented(self.n_probe_modes != 1, "forward_algorithm='ctf' with n_probe_modes != 1" if self.forward_algorithm == 'ctf'
@@ -542,7 +545,8 @@ class _Run(object):
             self.engine = MultisliceEngine(
                 ctx, obj_size, probe_size, self.probe_pos_int, self.energy_ev, self.psize_cm, free_prop_cm=self.free_prop_cm,
                 binning=self.binning, fresnel_approx=self.fresnel_approx, kernel=self.h, max_batch=1, beamstop=self.beamstop,
-                transmissions_only=self.forward_model == 'auto', streamed=True, detector_fanout=True, **common)
+                transmissions_only=self.forward_model == 'auto', streamed=True, detector_fanout=True,
+                refine_distances=bool(self.optimize_free_prop and self.fanout_free_prop), **common)
         elif self.is_multi_dist:
             if self.is_ctf:
                 from .holography import CTFEngine
@@ -775,6 +779,10 @@ class _Run(object):
         if self.is_sparse_multislice:
             # ptychography.py:718-719.  The engine's device array IS the parameter: the optimiser updates it in place
             params['slice_pos_cm_ls'] = self.engine.slice_pos
+        self.refine_3d_dists = bool(self.holo_3d and getattr(self.engine, 'refine_distances', False))
+        if self.refine_3d_dists:
+            # likewise: the engine's distances are the parameter (plain Adam, no pin, no drift guard: optimizers.py:906-917)
+            params['free_prop_cm'] = self.engine.dists
         # The optimised ones, in the order of the gradient tuple; one entry each (+ its gradient in the forward model)
         self.small, self.opt_args_ls = [], [0]
         if self.optimize_probe:
@@ -809,6 +817,7 @@ class _Run(object):
         self.ctf_lg_kappa_history = None      # (return_state: the value after every update, copied on the device)
         self.slice_pos_history = None         # (return_state: the positions after every update, copied on the device)
         self.prj_pos_offset_history = None    # (likewise: the offsets after every update)
+        self.free_prop_cm_history = None      # (likewise: the distances of a 3-D object after every update)
 
         restored = self.restored_params
         if restored is not None:
@@ -826,6 +835,12 @@ class _Run(object):
                         params[k_] = restored[k_]
             if self.is_sparse_multislice:
                 self.engine.slice_pos_changed()
+            if self.refine_3d_dists:
+                self.engine.dists_changed()
+                mom_ = self._small_moments('free_prop_cm')
+                if mom_ is not None and 'free_prop_cm_moments' in restored:
+                    for m_, h_ in zip(mom_, restored['free_prop_cm_moments']):
+                        m_.set(np.asarray(h_, dtype=np.float32).reshape(m_.shape))
 
         self.diff = Differentiator()
         self.diff.create_loss_node(self.forward_model.get_loss_function(), self.opt_args_ls)
@@ -853,7 +868,21 @@ class _Run(object):
         for k_, v_ in self.optimizable_params.items():
             if k_ not in out_:
                 out_[k_] = _host(v_)
+        if self.refine_3d_dists:
+            # (not part of the reference's format: the moments of the distances' optimiser, so that a resumed run continues the
+            # uninterrupted one -- the reference restarts them at zero)
+            mom_ = self._small_moments('free_prop_cm')
+            if mom_ is not None:
+                out_['free_prop_cm_moments'] = [m_.get() for m_ in mom_]
         return out_
+
+    def _small_moments(self, key):
+        """(m, v) of the built-in Adam that refines optimizable_params[key], or None (not refined, or the caller's optimiser)."""
+        for p in self.small:
+            d_ = getattr(p.opt, 'params_whole_array_dict', None) if p.key == key else None
+            if d_ and isinstance(d_.get('m'), DeviceArray) and isinstance(d_.get('v'), DeviceArray):
+                return d_['m'], d_['v']
+        return None
 
     def run_epochs(self):
         """The convergence log and summary.txt, then the epoch loop (ptychography.py:783-1295) with the outputs of every epoch."""
@@ -1213,6 +1242,16 @@ class _Run(object):
                 if k < hist.shape[0]:
                     _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * z.size * k, z.ptr, z.nbytes))
                     self.slice_pos_history[1] = k + 1
+        if self.refine_3d_dists and any(p.key == 'free_prop_cm' for p in due):
+            self.engine.dists_changed()           # the detector planes' kernels are rebuilt in front of the next launch
+            if self.return_state and self.n_epochs != 'auto':
+                x = self.engine.dists
+                if self.free_prop_cm_history is None:
+                    self.free_prop_cm_history = [self.ctx.zeros((int(self.n_epochs) * self.n_batch, x.size)), 0]
+                hist, k = self.free_prop_cm_history
+                if k < hist.shape[0]:
+                    _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * x.size * k, x.ptr, x.nbytes))
+                    self.free_prop_cm_history[1] = k + 1
         if any(p.key == 'ctf_lg_kappa' for p in due) and self.return_state and self.n_epochs != 'auto':
             x = self.optimizable_params['ctf_lg_kappa']
             if self.ctf_lg_kappa_history is None:
@@ -1284,6 +1323,8 @@ class _Run(object):
         return {'delta': arr[..., 0], 'beta': arr[..., 1], 'probe_real': pa[..., 0], 'probe_imag': pa[..., 1],
                 'probe_pos_correction': np.asarray(_host(params['probe_pos_correction'])),
                 'free_prop_cm': _host(params.get('free_prop_cm', self.free_prop_cm)), 'prj_affine_ls': _host(params.get('prj_affine_ls')),
+                'free_prop_cm_history': (None if self.free_prop_cm_history is None
+                                         else self.free_prop_cm_history[0].get()[:self.free_prop_cm_history[1]]),
                 'slice_pos_cm_ls': _host(params.get('slice_pos_cm_ls')),
                 'slice_pos_history': None if self.slice_pos_history is None else self.slice_pos_history[0].get()[:self.slice_pos_history[1]],
                 'prj_pos_offset': np.asarray(_host(params['prj_pos_offset'])),

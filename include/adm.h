@@ -455,6 +455,27 @@ int adm_multislice_fwd_adj_probe_shift(adm_plan* plan, const float* obj_rot, con
  * grad_probe, the detector mask and the cover build are those of `batch` positions, unchanged. */
 int adm_plan_set_detector_fanout(adm_plan* plan, int n, const float* hfree_re, const float* hfree_im);
 
+/* ---- the distances of the fan-out as parameters (streamed plans) ------------------------
+ * optimize_free_prop for a 3-D object (adorym/propagate.py:274-277, 556-568: fresnel_propagate_wrapped): the n distances live on
+ * the device and are refined together with the object.  H_d = exp(i a d_d), a = -sign_convention PI lambda (u^2 + v^2) per nm,
+ * PI = 3.14159265359, d_d = dists_cm[d] * 1e7 nm.
+ * adm_plan_set_fanout_distances hands the plan dists_cm_dev: DEVICE float [n], 1 <= n <= 64; the buffer stays the caller's and
+ * must outlive its use.  It switches the fan-out on like adm_plan_set_detector_fanout (same refusals, same launch semantics, same
+ * workspace growth) with the table of the H_d / (Py*Px) built on the device, on the context's stream, in front of the next launch
+ * (phase in fp64, reduced to one turn, sin / cos in fp32).  Whoever changes the values afterwards -- an optimiser step -- calls it
+ * again (same arguments) so that the table is rebuilt; without that call it is kept.  Call it before the workspace is sized:
+ * adm_plan_workspace_bytes also grows by batch * n_modes kept spectra and the dL/dd partials.  adm_plan_set_detector_fanout on
+ * such a plan puts it back on host-built kernels.
+ * adm_multislice_fwd_adj_fanout_dist is adm_multislice_fwd_adj on such a plan with grad_dists_dev: device float [n],
+ * dL/d dists_cm in 1/cm ACCUMULATED into it (want_grad = 1; may be NULL: the launch is then adm_multislice_fwd_adj's, kernel for
+ * kernel).  With it, pred, loss, tile gradients and grad_probe keep their bits; the terms are summed in a fixed order (no atomics):
+ * two calls give the same bits. */
+int adm_plan_set_fanout_distances(adm_plan* plan, const float* dists_cm_dev, int n, double lambda_nm, double voxel_nm_y,
+                                  double voxel_nm_x);
+int adm_multislice_fwd_adj_fanout_dist(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
+                                       const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
+                                       float grad_scale, void* workspace, size_t workspace_bytes, float* grad_dists_dev);
+
 /* ---- f2  sub-pixel probe positions -----------------------------------------------------
  * realign_image_fourier (adorym/util.py:380-397) applied to every probe mode for every position of a minibatch:
  *   probes_out[b][m] = IFFT2( exp(-2 PI i (fx*sx_b + fy*sy_b)) * FFT2(probe[m]) ),  PI = 3.14159265359, f = fftfreq.
