@@ -173,6 +173,10 @@ SIGNATURES = {
     'adm_ctf_create': (_I, [_VP, C.POINTER(CtfDesc), C.POINTER(_VP)]),
     'adm_ctf_destroy': (_I, [_VP]),
     'adm_ctf_fwd_adj': (_I, [_VP, _VP, C.POINTER(_D), _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    'adm_register_create': (_I, [_VP, _I, _I, _I, _I, C.POINTER(_VP)]),
+    'adm_register_destroy': (_I, [_VP]),
+    'adm_register_targets': (_I, [_VP, _VP, _VP, _VP]),
+    'adm_register_grad': (_I, [_VP, _VP, _VP, _VP, _F, _VP]),
 }
 
 _lib = None

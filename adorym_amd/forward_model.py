@@ -730,6 +730,9 @@ class MultiDistModel(PtychographyModel):
     (adm_plan_set_detector_fanout), and the rotation adjoint takes the gradient back; gradients w.r.t. obj and the probe.  An engine
     built with ``refine_distances=True`` also serves ``optimize_free_prop``: ``free_prop_cm`` is then the engine's device array
     ``engine.dists`` (the kernels follow it, adm_plan_set_fanout_distances) and the gradient w.r.t. it comes from the same launch.
+    ``common_vars_dict['hologram_registration']`` (an adorym_amd.HologramRegistration) also serves ``optimize_prj_affine``: the raw
+    holograms registered by ``prj_affine_ls`` are the launch's target (adm_register_targets) and the gradient w.r.t. the matrices is
+    formed from the launch's predictions (adm_register_grad).
     """
 
     PROJECTION_MODEL = 'multi-distance data (MultiDistModel)'
@@ -753,6 +756,9 @@ class MultiDistModel(PtychographyModel):
         self.fanout = bool(common_vars_dict) and not self.is_ctf and bool(getattr(self.engine, 'detector_fanout', False))
         # ... and holds them as parameters on the device (what the engine can do decides, not a flag of its own)
         self.refine_3d = self.fanout and bool(getattr(self.engine, 'refine_distances', False))
+        # ... and the holograms are registered by kernels of their own when the caller brought that engine (likewise)
+        self.registration = common_vars_dict.get('hologram_registration') if self.fanout else None
+        self.register_3d = self.registration is not None
 
     def _check(self, safe_zone_width, ctf_lg_kappa, probe_pos_correction):
         cv = self.common_vars
@@ -796,24 +802,51 @@ class MultiDistModel(PtychographyModel):
         elif cv.get('unknown_type', 'delta_beta') == 'real_imag':
             what = "unknown_type='real_imag'"
         for flag in self.REFUSED_3D_FLAGS:
-            if what is None and cv.get(flag) and not (flag == 'optimize_free_prop' and self.refine_3d):
+            served = (flag == 'optimize_free_prop' and self.refine_3d) or (flag == 'optimize_prj_affine' and self.register_3d)
+            if what is None and cv.get(flag) and not served:
                 what = flag
         if what is not None:
             raise NotImplementedError('multi-distance holography of a 3-D object with %s is outside the accelerated path' % what)
         if not self.fanout:
             raise ValueError('MultiDistModel with two_d_mode=False needs common_vars_dict[\'engine\'] built with detector_fanout=True '
                              '(an adorym_amd.MultisliceEngine for the sequence of distances)')
+        if self.register_3d and cv.get('optimize_prj_affine'):
+            reg, eng = self.registration, self.engine
+            if (reg.n_dists, reg.ny, reg.nx) != (eng.n_dists,) + tuple(eng.probe_size) or reg.raw_data_type != self.raw_data_type:
+                raise ValueError('MultiDistModel: hologram_registration was built for another field, number of distances or raw_data_type')
+            if eng.n_det != eng.probe_size[0] * eng.probe_size[1]:
+                raise NotImplementedError('multi-distance holography of a 3-D object with optimize_prj_affine and a beamstop is outside '
+                                          'the accelerated path')
 
     def _run_3d(self, obj, probe_real, probe_imag, this_i_theta, target, want_grad, **kw):
         """PtychographyModel._run on the whole field as the one position (0, 0): rotate, one fan-out launch, rotation adjoint.
         ``target`` None: this angle's holograms [n_dists, Y, X] (resident datasets: a view of the device copy)."""
+        aff, want_aff = kw.pop('prj_affine_ls', None), kw.pop('want_affine_grad', False)
+        data = None
+        if target is None and self.register_3d and self.common_vars.get('optimize_prj_affine'):
+            # forward_model.py:1066-1072: the raw holograms of this angle (cached on the device) registered by prj_affine_ls are the
+            # launch's target.  On the main stream, in front of the rotation: the side stream is joined BEHIND the launch, which
+            # would not wait for a target made there.
+            data = self._data(this_i_theta)
+            aff = self._dev('prj_affine_ls', aff, (self.engine.n_dists, 2, 3))
+            target = self.registration.targets(data, aff)
+            if want_aff:
+                kw['want_pred'] = True          # (the predictions stay on the device: engine.pred_device())
+        elif want_aff:
+            raise RuntimeError('gradient w.r.t. prj_affine_ls requested but the model registers no holograms')
         if target is None:
             target = self._target(this_i_theta, np.arange(self.engine.n_dists))
         fp = kw.pop('free_prop_cm', None)
         if self.refine_3d and isinstance(fp, DeviceArray) and fp.ptr != self.engine.dists.ptr:
             raise ValueError('multi-distance holography of a 3-D object with refined distances: free_prop_cm on the device must be '
                              'the engine\'s own array (engine.dists)')
-        return PtychographyModel._run(self, obj, probe_real, probe_imag, this_i_theta, np.zeros((1, 2), int), target, want_grad, **kw)
+        out = PtychographyModel._run(self, obj, probe_real, probe_imag, this_i_theta, np.zeros((1, 2), int), target, want_grad, **kw)
+        if want_aff:
+            # dL/d prj_affine_ls, left in self._grad_affine_dev; the launch's grad_scale is 2 / (D Py Px), the kernel's own factor
+            if getattr(self, '_grad_affine_dev', None) is None:
+                self._grad_affine_dev = self.device.empty((self.engine.n_dists, 2, 3))
+            self.registration.grad(data, aff, self.engine.pred_device(), self._grad_affine_dev.zero_())
+        return out
 
     # what the CTF model refuses by name: it has no probe, one slice, one undivided field of view, fixed distances and no registration
     CTF_REFUSED_FLAGS = ('optimize_probe', 'optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos')
@@ -1047,7 +1080,8 @@ class MultiDistModel(PtychographyModel):
                 self.current_loss = float(self.ctf.loss() + self._regularize(obj, None))
                 return self.current_loss
             if self.fanout:
-                self._run_3d(obj, probe_real, probe_imag, this_i_theta, None, want_grad=False, free_prop_cm=free_prop_cm)
+                self._run_3d(obj, probe_real, probe_imag, this_i_theta, None, want_grad=False, free_prop_cm=free_prop_cm,
+                             prj_affine_ls=prj_affine_ls)
                 self._queue_loss()
                 return self.current_loss
             if self.tile_engine is not None:
@@ -1070,17 +1104,20 @@ class MultiDistModel(PtychographyModel):
         self._check(safe_zone_width, ctf_lg_kappa, probe_pos_correction)
         if self.fanout:
             i_pr, i_pi = self.get_argument_index('probe_real'), self.get_argument_index('probe_imag')
-            i_fp = self.get_argument_index('free_prop_cm')
+            i_fp, i_af = self.get_argument_index('free_prop_cm'), self.get_argument_index('prj_affine_ls')
             for i in opt_args_ls:
-                if i not in (0, i_pr, i_pi) and not (i == i_fp and self.refine_3d):
+                if i not in (0, i_pr, i_pi) and not (i == i_fp and self.refine_3d) and not (i == i_af and self.register_3d):
                     raise NotImplementedError("multi-distance holography of a 3-D object: the gradient w.r.t. '%s' is outside the "
                                               "accelerated path" % self.argument_ls[i])
             gp, _ = self._run_3d(obj, probe_real, probe_imag, this_i_theta, None, want_grad=True, grad_obj=grad_obj,
                                  want_probe_grad=(i_pr in opt_args_ls) or (i_pi in opt_args_ls), side_hook=_side_hook, init_grad=_init_grad,
-                                 want_dist_grad=i_fp in opt_args_ls, free_prop_cm=free_prop_cm)
+                                 want_dist_grad=i_fp in opt_args_ls, free_prop_cm=free_prop_cm, prj_affine_ls=prj_affine_ls,
+                                 want_affine_grad=i_af in opt_args_ls)
             self._queue_loss()          # self.current_loss fetches it on first access
-            # (probe_real and probe_imag reference ONE interleaved device array [1,Py,Px,2]; free_prop_cm: DeviceArray [n_dists])
-            return tuple(grad_obj if i == 0 else self._grad_dists_dev if i == i_fp else gp for i in opt_args_ls)
+            # (probe_real and probe_imag reference ONE interleaved device array [1,Py,Px,2]; free_prop_cm: DeviceArray [n_dists];
+            # prj_affine_ls: DeviceArray [n_dists,2,3])
+            return tuple(grad_obj if i == 0 else self._grad_dists_dev if i == i_fp else self._grad_affine_dev if i == i_af else gp
+                         for i in opt_args_ls)
         if _side_hook is not None:
             _side_hook()
         if self.is_ctf:

@@ -189,3 +189,54 @@ class CTFEngine(object):
 
     def pred(self):
         return self._pred.get()
+
+
+class HologramRegistration(object):
+    """The affine registration of measured holograms as kernels of its own (optimize_prj_affine, adorym/forward_model.py:1066-1072;
+    w.affine_transform, wrappers.py:1159-1174) for forward models that are not HolographyEngine's: multi-distance holography of a
+    3-D object, where the registered holograms are the ``target`` of the fan-out launch and its predictions feed the gradient
+    w.r.t. the matrices.  See include/adm.h (adm_register_*) and csrc/adm_register.hip.  Any field from 2 x 2 to 2048 x 2048,
+    1 to 64 distances."""
+
+    def __init__(self, ctx, n_dists, field_size, raw_data_type='magnitude'):
+        if raw_data_type not in ('magnitude', 'intensity'):
+            raise ValueError("raw_data_type must be 'magnitude' or 'intensity'")
+        self.ctx = ctx
+        self.n_dists = int(n_dists)
+        self.ny, self.nx = int(field_size[0]), int(field_size[1])
+        self.raw_data_type = raw_data_type
+        h = C.c_void_p()
+        check(ctx.lib.adm_register_create(ctx.handle, self.n_dists, self.ny, self.nx, 1 if raw_data_type == 'intensity' else 0, C.byref(h)))
+        self.handle = h
+        self._target = DeviceArray(ctx, (self.n_dists, self.ny, self.nx), np.float32)
+
+    def __del__(self):
+        try:
+            if getattr(self, 'handle', None) and self.ctx.handle:
+                self.ctx.lib.adm_register_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def _checked(self, a, shape, name):
+        if not isinstance(a, DeviceArray):
+            raise TypeError('HologramRegistration: %s must be a DeviceArray' % name)
+        if a.dtype != np.float32 or a.size != int(np.prod(shape)):
+            raise ValueError('HologramRegistration: %s must be float32 %r, got %s %r' % (name, list(shape), np.dtype(a.dtype).name, list(a.shape)))
+        return a.ptr
+
+    def targets(self, data, affine):
+        """data [D, Py, Px] raw holograms (taken as |data|), affine [D, 2, 3]: DeviceArrays.  Returns the engine's own DeviceArray
+        [D, Py, Px] of registered magnitudes, overwritten by the next call; queued on the stream the context is enqueuing on."""
+        shape = (self.n_dists, self.ny, self.nx)
+        check(self.ctx.lib.adm_register_targets(self.handle, self._checked(data, shape, 'data'),
+                                                self._checked(affine, (self.n_dists, 2, 3), 'affine'), self._target.ptr))
+        return self._target
+
+    def grad(self, data, affine, pred, grad_affine, grad_scale=1.):
+        """grad_affine [D, 2, 3] += grad_scale * dL/d affine of L = mean (pred - target)^2 over all D * Py * Px values, with ``pred``
+        [D, Py, Px] the predicted magnitudes on the device (MultisliceEngine.pred_device())."""
+        shape = (self.n_dists, self.ny, self.nx)
+        check(self.ctx.lib.adm_register_grad(self.handle, self._checked(data, shape, 'data'), self._checked(affine, (self.n_dists, 2, 3), 'affine'),
+                                             self._checked(pred, shape, 'pred'), float(grad_scale),
+                                             self._checked(grad_affine, (self.n_dists, 2, 3), 'grad_affine')))

@@ -808,6 +808,11 @@ class MultisliceEngine(object):
         """The first n per-entry sums of the last launch (blocks)."""
         return self._loss.view(0, (n,)).get().astype(np.float64)
 
+    def pred_device(self):
+        """The predictions of the last launch with ``want_pred`` where the kernel left them: the view of the device buffer that
+        ``pred()`` downloads, [B * det_per_pos, Py, Px]."""
+        return self._pred.view(0, (self._B * self.det_per_pos,) + self.probe_size)
+
     def pred(self):
         return self._pred.view(0, (self._B * self.det_per_pos,) + self.probe_size).get()
 

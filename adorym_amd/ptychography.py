@@ -324,6 +324,8 @@ class _Run(object):
         self.streamed_probe_shift = bool(kwargs.pop('streamed_probe_shift', False))
         # optimize_free_prop for multi-distance data of a 3-D object (holotomography): the distances refined on the device, on request
         self.fanout_free_prop = bool(kwargs.pop('fanout_free_prop', False))
+        # optimize_prj_affine for the same data: the holograms registered by kernels of their own (HologramRegistration), on request
+        self.fanout_prj_affine = bool(kwargs.pop('fanout_prj_affine', False))
         self.ops = kwargs.pop('ops', None)
         kwargs.pop('probe_size', None)
         self.kwargs = kwargs
@@ -462,7 +464,9 @@ class _Run(object):
                 _not_implemented(len(probe_pos) > 1 or safe_zone_width > 0, what % 'data divided into sub-tiles or safe_zone_width > 0')
                 for nm in ('optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos', 'rotate_out_of_loop'):
                     # (fanout_free_prop=True: the engine holds the distances as parameters, MultisliceEngine(refine_distances=True))
-                    _not_implemented(bool(getattr(self, nm)) and not (nm == 'optimize_free_prop' and self.fanout_free_prop), what % nm)
+                    # (fanout_prj_affine=True: the holograms are registered in front of the launch, HologramRegistration)
+                    served = (nm == 'optimize_free_prop' and self.fanout_free_prop) or (nm == 'optimize_prj_affine' and self.fanout_prj_affine)
+                    _not_implemented(bool(getattr(self, nm)) and not served, what % nm)
                 _not_implemented(self.unknown_type == 'real_imag', what % "unknown_type='real_imag'")
                 _not_implemented(self.n_ranks > 1, what % 'more than one rank')
             _not_implemented(self.n_probe_modes != 1, "forward_algorithm='ctf' with n_probe_modes != 1" if self.forward_algorithm == 'ctf'
@@ -527,7 +531,7 @@ class _Run(object):
         self.h = get_kernel(voxel_nm[-1] * self.binning, self.lmbda_nm, voxel_nm, probe_size, fresnel_approx=self.fresnel_approx,
                             sign_convention=self.sign_convention) if (self.holo_3d or not self.is_multi_dist) else None
         self.probe_pos_int = np.round(self.probe_pos).astype(int)
-        self.holo_engine = self.tile_engine = self.ctf_engine = None
+        self.holo_engine = self.tile_engine = self.ctf_engine = self.registration = None
         common = dict(sign_convention=self.sign_convention, scale_ri_by_k=self.scale_ri_by_k, unknown_type=self.unknown_type)
         if self.holo_tiled:
             # one engine for all distances: tile = sub-hologram + 2 safe zones at (position - safe zone), every tile listed n_dists
@@ -547,6 +551,10 @@ class _Run(object):
                 binning=self.binning, fresnel_approx=self.fresnel_approx, kernel=self.h, max_batch=1, beamstop=self.beamstop,
                 transmissions_only=self.forward_model == 'auto', streamed=True, detector_fanout=True,
                 refine_distances=bool(self.optimize_free_prop and self.fanout_free_prop), **common)
+            if self.optimize_prj_affine and self.fanout_prj_affine:
+                from .holography import HologramRegistration
+                _not_implemented(self.beamstop is not None, 'multi-distance holography of a 3-D object with optimize_prj_affine and a beamstop')
+                self.registration = HologramRegistration(ctx, self.n_dists, probe_size, self.raw_data_type)
         elif self.is_multi_dist:
             if self.is_ctf:
                 from .holography import CTFEngine
@@ -688,6 +696,8 @@ class _Run(object):
                            optimize_probe_pos_offset=False, optimize_prj_pos_offset=bool(self.optimize_prj_pos_offset),
                            optimize_all_probe_pos=self.optimize_all_probe_pos,
                            optimize_tilt=False, output_folder=self.output_folder, debug=self.debug)
+        if self.registration is not None:
+            common_vars['hologram_registration'] = self.registration
         fm_args = dict(loss_function_type=self.loss_function_type, distribution_mode=self.distribution_mode, device=ctx,
                        common_vars_dict=common_vars, raw_data_type=self.raw_data_type, run_bfloat16=self.run_bfloat16,
                        run_float64=self.run_float64)
@@ -818,6 +828,8 @@ class _Run(object):
         self.slice_pos_history = None         # (return_state: the positions after every update, copied on the device)
         self.prj_pos_offset_history = None    # (likewise: the offsets after every update)
         self.free_prop_cm_history = None      # (likewise: the distances of a 3-D object after every update)
+        self.register_3d = bool(self.holo_3d and self.registration is not None)
+        self.prj_affine_history = None        # (likewise: the registration matrices of a 3-D object after every update)
 
         restored = self.restored_params
         if restored is not None:
@@ -840,6 +852,11 @@ class _Run(object):
                 mom_ = self._small_moments('free_prop_cm')
                 if mom_ is not None and 'free_prop_cm_moments' in restored:
                     for m_, h_ in zip(mom_, restored['free_prop_cm_moments']):
+                        m_.set(np.asarray(h_, dtype=np.float32).reshape(m_.shape))
+            if self.register_3d:
+                mom_ = self._small_moments('prj_affine_ls')
+                if mom_ is not None and 'prj_affine_ls_moments' in restored:
+                    for m_, h_ in zip(mom_, restored['prj_affine_ls_moments']):
                         m_.set(np.asarray(h_, dtype=np.float32).reshape(m_.shape))
 
         self.diff = Differentiator()
@@ -874,6 +891,10 @@ class _Run(object):
             mom_ = self._small_moments('free_prop_cm')
             if mom_ is not None:
                 out_['free_prop_cm_moments'] = [m_.get() for m_ in mom_]
+        if self.register_3d:
+            mom_ = self._small_moments('prj_affine_ls')       # (likewise)
+            if mom_ is not None:
+                out_['prj_affine_ls_moments'] = [m_.get() for m_ in mom_]
         return out_
 
     def _small_moments(self, key):
@@ -1252,6 +1273,14 @@ class _Run(object):
                 if k < hist.shape[0]:
                     _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * x.size * k, x.ptr, x.nbytes))
                     self.free_prop_cm_history[1] = k + 1
+        if self.register_3d and any(p.key == 'prj_affine_ls' for p in due) and self.return_state and self.n_epochs != 'auto':
+            x = self.optimizable_params['prj_affine_ls']
+            if self.prj_affine_history is None:
+                self.prj_affine_history = [self.ctx.zeros((int(self.n_epochs) * self.n_batch,) + tuple(x.shape)), 0]
+            hist, k = self.prj_affine_history
+            if k < hist.shape[0]:
+                _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * x.size * k, x.ptr, x.nbytes))
+                self.prj_affine_history[1] = k + 1
         if any(p.key == 'ctf_lg_kappa' for p in due) and self.return_state and self.n_epochs != 'auto':
             x = self.optimizable_params['ctf_lg_kappa']
             if self.ctf_lg_kappa_history is None:
@@ -1325,6 +1354,7 @@ class _Run(object):
                 'free_prop_cm': _host(params.get('free_prop_cm', self.free_prop_cm)), 'prj_affine_ls': _host(params.get('prj_affine_ls')),
                 'free_prop_cm_history': (None if self.free_prop_cm_history is None
                                          else self.free_prop_cm_history[0].get()[:self.free_prop_cm_history[1]]),
+                'prj_affine_history': None if self.prj_affine_history is None else self.prj_affine_history[0].get()[:self.prj_affine_history[1]],
                 'slice_pos_cm_ls': _host(params.get('slice_pos_cm_ls')),
                 'slice_pos_history': None if self.slice_pos_history is None else self.slice_pos_history[0].get()[:self.slice_pos_history[1]],
                 'prj_pos_offset': np.asarray(_host(params['prj_pos_offset'])),

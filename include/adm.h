@@ -681,6 +681,28 @@ int adm_ctf_destroy(adm_ctf* h);
 int adm_ctf_fwd_adj(adm_ctf* h, const float* obj, const double* dists_cm, const float* lg_kappa, const float* data,
                     int want_grad, float* grad_obj, float* grad_lg_kappa, float* pred, float* loss_sum);
 
+/* ---- f1  affine registration of measured holograms, on its own --------------------------
+ * optimize_prj_affine (adorym/forward_model.py:1066-1072; w.affine_transform, wrappers.py:1159-1174 = F.affine_grid +
+ * F.grid_sample, bilinear, padding_mode='border', align_corners=False) for forward models other than adm_holo_fwd_adj -- a 3-D
+ * object on a streamed plan with a detector fan-out: the registration acts on the measured data, so the registered holograms are
+ * the `target` of the launch and the launch's `pred` is all the matrix gradient needs.
+ * ny, nx in [2, 2048] (any value; else ADM_ERR_UNSUPPORTED), 1 <= n_dists <= 64 (else ADM_ERR_INVALID); intensity: raw_data_type,
+ * 0 'magnitude', 1 'intensity'.  The handle owns the buffer of the gradient's partial sums.  Device pointers throughout:
+ * data [n_dists][ny][nx] raw (taken as |data|), affine [n_dists][2][3], target / pred [n_dists][ny][nx].
+ *   adm_register_targets   target = |samp| (magnitude data) or sqrt|samp| (intensity data), samp = the bilinear sample of |data_d|
+ *                          at the point affine_d maps the base coordinate of pixel (y, x) to, clamped to the image.
+ *   adm_register_grad      grad_affine [n_dists][2][3] += dL/daffine of L = mean_{d,y,x} (pred - target)^2 times grad_scale: with
+ *                          c = -(2 / (n_dists ny nx)) grad_scale (pred - target) dtarget/dsamp (0 where that is not finite: an exactly
+ *                          zero sample), torch's grid_sampler backward (zero through coordinates at or beyond a border).
+ * Both are queued on the stream the context is enqueuing on.  Sums in a fixed order, in double, no atomics: two calls give the same
+ * bits. */
+typedef struct adm_register adm_register;
+int adm_register_create(adm_ctx* ctx, int n_dists, int ny, int nx, int intensity, adm_register** out);
+int adm_register_destroy(adm_register* r);
+int adm_register_targets(adm_register* r, const float* data, const float* affine, float* target);
+int adm_register_grad(adm_register* r, const float* data, const float* affine, const float* pred, float grad_scale,
+                      float* grad_affine);
+
 /* y[i] += a * x[i]  (gradient accumulation, adorym/ptychography.py:1063-1066) */
 int adm_axpy(adm_ctx* ctx, float* y, const float* x, float a, size_t n);
 
