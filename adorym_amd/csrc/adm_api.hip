@@ -672,11 +672,11 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
         ADM_HIP(hipMemsetAsync(ws + w.fan_pos, 0, (size_t)batch * fo.n * sizeof(int2), plan->ctx->stream));
         if (plan->fan_dists_dev) {      // the distances live on the device: the table follows them, the gradient can be formed
             if (plan->fan_dists_dirty) {
-                StDistGeom q;
-                q.py = plan->d.probe_y; q.px = plan->d.probe_x; q.n = plan->n_fan; q.sigma = (double)plan->d.sign_convention;
+                StFresnelGeom q;
+                q.py = plan->d.probe_y; q.px = plan->d.probe_x; q.n = plan->n_fan; q.gaps = 0; q.sigma = (double)plan->d.sign_convention;
                 q.lambda_nm = plan->fd_lambda_nm; q.voxel_nm_y = plan->fd_voxel_nm_y; q.voxel_nm_x = plan->fd_voxel_nm_x;
-                ADM_HIP(ms_distgrad_table_launch(q, plan->fan_dists_dev, plan->fan_hs_dev, plan->fan_a_dev, plan->fan_a_dev + q.py,
-                                                 plan->ctx->stream));
+                ADM_HIP(ms_fresnel_table_launch(q, plan->fan_dists_dev, plan->fan_hs_dev, plan->fan_a_dev, plan->fan_a_dev + q.py,
+                                                plan->ctx->stream));
             }
             plan->fan_dists_dirty = false;
             if (grad_dists && p.want_grad) {
@@ -705,10 +705,10 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
     if (sparse) {
         const int Py = plan->d.probe_y, Px = plan->d.probe_x;
         if (plan->zpos_dirty && plan->n_zpos > 1) {
-            StSparseGeom q;
-            q.py = Py; q.px = Px; q.n_slices = plan->n_zpos; q.sigma = (double)plan->d.sign_convention;
+            StFresnelGeom q;
+            q.py = Py; q.px = Px; q.n = plan->n_zpos - 1; q.gaps = 1; q.sigma = (double)plan->d.sign_convention;
             q.lambda_nm = plan->sp_lambda_nm; q.voxel_nm_y = plan->sp_voxel_nm_y; q.voxel_nm_x = plan->sp_voxel_nm_x;
-            ADM_HIP(ms_sparse_table_launch(q, plan->zpos_dev, plan->sp_hs_dev, plan->sp_a_dev, plan->sp_a_dev + Py, plan->ctx->stream));
+            ADM_HIP(ms_fresnel_table_launch(q, plan->zpos_dev, plan->sp_hs_dev, plan->sp_a_dev, plan->sp_a_dev + Py, plan->ctx->stream));
         }
         plan->zpos_dirty = false;
         sp.hs = plan->sp_hs_dev;

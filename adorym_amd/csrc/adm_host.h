@@ -118,8 +118,12 @@ int ms_generic_threads(int py, int px);
 hipError_t ms_generic_launch(const MsParams& p, int batch, hipStream_t st);
 bool ms_streamed_supported(int py, int px);
 int ms_streamed_col_groups(int py, int px);
+// n Fresnel transfer functions of py x px built on the device from float32 lengths (cm) as they sit in a caller's buffer: gaps != 0,
+// table s is the gap between slice positions s and s + 1 of a sparse plan (n + 1 positions); gaps == 0, table d is detector distance d
+// of a fan-out whose distances are refined
+struct StFresnelGeom { int py, px, n, gaps; double sigma, lambda_nm, voxel_nm_y, voxel_nm_x; };
+hipError_t ms_fresnel_table_launch(const StFresnelGeom& q, const float* src_cm, float2* hs, float* ay, float* ax, hipStream_t st);
 // sparse multislice on streamed plans (adm_ms_streamed.hip)
-struct StSparseGeom { int py, px, n_slices; double sigma, lambda_nm, voxel_nm_y, voxel_nm_x; };
 struct StSparse {              // kernel argument of the column launches that serve the slice-position gradient
     float2* keep;              // [B][M][S-1][Py][Px] H_s * spectrum / (Py*Px) of the forward sweep
     double* part;              // [S-1][B*M*column groups] dL/dd partials
@@ -132,7 +136,6 @@ struct StSparseLaunch {
     float2* keep; double* part; const float* ay; const float* ax;
     float* grad_z;             // [S] += dL/dz (cm), or nullptr
 };
-hipError_t ms_sparse_table_launch(const StSparseGeom& q, const float* z, float2* hs, float* ay, float* ax, hipStream_t st);
 hipError_t ms_sparse_anchor_launch(float* z, int n, hipStream_t st);
 int ms_sparse_max_slices();
 // per-angle projection alignment on streamed plans (adm_ms_exitshift.hip): the detector step's column launches with a sub-pixel
@@ -173,12 +176,19 @@ struct StFanout {              // kernel argument
     float2* dfld;              // [B][D][M][Py][Px] detector-plane fields
     int n;                     // D
 };
+struct StDistGrad {            // kernel argument beside StFanout; read by the instantiations with the distance gradient only
+    float2* keep;              // [B][M][Py][Px]
+    double* part;              // [D][B*M*column groups]
+    const float* ay;
+    const float* ax;
+};
 struct StFanoutLaunch {
     int n; const float2* hs;
     float2* fld;               // [B*D][M][Py][Px] detector-plane fields
     float2* det;               // [B*D][M][Py][Px] the detector kernel's parked fields (M > 1), or nullptr
     const int2* pos;           // [B*D] zeros
-    // the distance gradient (adm_ms_distgrad.hip); grad_dists set = requested: the two launchers below hand over to that file
+    // the distance gradient (distances on the device: adm_plan_set_fanout_distances); grad_dists set = requested: the two launchers
+    // below then start the instantiations that keep the spectra and form the partials
     float* grad_dists = nullptr;      // [D] += dL/d distance (per cm), or nullptr
     float2* keep = nullptr;    // [B][M][Py][Px] column-transformed spectra of the exit waves
     double* part = nullptr;    // [D][B*M*column groups] dL/dd partials
@@ -187,18 +197,6 @@ struct StFanoutLaunch {
 };
 hipError_t ms_multidist_fanout_launch(const MsParams& p, int batch, const float2* fld, const StFanoutLaunch& fo, hipStream_t st);
 hipError_t ms_multidist_fanin_launch(const MsParams& p, int batch, float2* fld, const StFanoutLaunch& fo, hipStream_t st);
-// the fan-out with the distances as parameters on the device (adm_plan_set_fanout_distances, adm_ms_distgrad.hip)
-struct StDistGeom { int py, px, n; double sigma, lambda_nm, voxel_nm_y, voxel_nm_x; };
-struct StDistGrad {            // kernel argument, beside StFanout
-    float2* keep;              // [B][M][Py][Px]
-    double* part;              // [D][B*M*column groups]
-    const float* ay;
-    const float* ax;
-};
-hipError_t ms_distgrad_table_launch(const StDistGeom& q, const float* dists_cm, float2* hs, float* ay, float* ax, hipStream_t st);
-hipError_t ms_distgrad_fanout_launch(const MsParams& p, int batch, const float2* fld, const StFanoutLaunch& fo, hipStream_t st);
-hipError_t ms_distgrad_fanin_launch(const MsParams& p, int batch, float2* fld, const StFanoutLaunch& fo, hipStream_t st);
-hipError_t ms_distgrad_sum_launch(const MsParams& p, int batch, const StFanoutLaunch& fo, hipStream_t st);
 // the streamed launch sequence of one minibatch: fld = [B][M][Py][Px] field buffer, part = [B][col groups] loss partials;
 // sp: the tables of a sparse plan, or nullptr; xs: the exit-wave shifts of a plan with adm_plan_set_exit_shift, or nullptr; ps:
 // the probe shifts of a plan with adm_plan_set_probe_shift, or nullptr; fo: the detector fan-out of a plan with

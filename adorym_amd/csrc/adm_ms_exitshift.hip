@@ -19,21 +19,6 @@
 
 namespace adm {
 
-// Phi at spectral element (y, x) for the offset s = (s_y, s_x).  Per-angle alignment exists to recover offsets of tens of pixels:
-// the argument -2 PI (fx s_x + fy s_y) then reaches hundreds of radians (2000 rad at 640 px and an offset beyond the field), where
-// an fp32 argument -- as the reference and shift_phases (adm_multislice.hip) form it -- is 1e-4 rad off and the prediction 2.3e-5
-// from the fp64 model (640 x 12, tests/test_gpu_value_domain.py).  So: ps_phase's scheme (adm_ms_probeshift.hip), the argument in
-// fp64 from the integer frequency index, reduced to one turn, then sin / cos in fp32.
-__device__ __forceinline__ cf es_phase(int y, int py, int x, int px, float2 s) {
-    const double fy = (double)st_freq_index(y, py) / (double)py, fx = (double)st_freq_index(x, px) / (double)px;
-    double arg = -2.0 * 3.14159265359 * (fx * (double)s.y + fy * (double)s.x);
-    const double two_pi = 6.283185307179586476925287;
-    arg -= two_pi * rint(arg / two_pi);
-    float sn, cs;
-    sincos_fast((float)arg, sn, cs);
-    return make_float2(cs, sn);
-}
-
 // field <- column IFFT( Phi_b * H * column FFT(field) ) for one (position, mode, column group); hs = H / (Py*Px), or nullptr:
 // H = 1.  Forward: keeps the multiplied spectrum when q.keep.  Adjoint (CONJ): conj(Phi_b H), and this workgroup's share of
 // dL/ds when q.part.
@@ -41,6 +26,8 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void es_col_conv_ke
                                                                                       const float2* __restrict__ hs, StExitShift q) {
     extern __shared__ cf es_lds[];
     __shared__ double redd[2 * (ST_COL_NT / 64)];
+    // (st_col_begin written out, as in adm_ms_multidist.hip: behind the helper the prologue came out two instructions longer, and the
+    // one-position launch with the shift gradient measured 0.03 - 0.09 % slower twice: profiles/col_refactor/timings.txt)
     const int Py = p.gen_py, Px = p.gen_px, cw = st_cw(Py), ncg = (Px + cw - 1) / cw;
     const int bm = blockIdx.x / ncg, c0 = (blockIdx.x - bm * ncg) * cw;
     const int b = bm / p.n_modes;
@@ -64,7 +51,7 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void es_col_conv_ke
             const int y = i / g.Px, x = c0 + (i - y * g.Px);
             const size_t k = (size_t)y * Px + x;
             const float fy = st_freq(y, Py), fx = st_freq(x, Px);
-            const cf ph = es_phase(y, Py, x, Px, s);
+            const cf ph = st_shift_phase(y, Py, x, Px, s);
             const cf a = g.fld[i];
             if (CONJ) {
                 if (sums) {
@@ -93,22 +80,15 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void es_col_conv_ke
 hipError_t ms_exitshift_col_launch(const MsParams& p, int batch, float2* fld, const float2* hs, bool conj, const StExitShiftLaunch& xs,
                                    hipStream_t st) {
     const StColGeom cg = st_col_geom(p.gen_py, p.gen_px);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = st_col_raise_lds(es_col_conv_kernel<false>);
-        if (e == hipSuccess) e = st_col_raise_lds(es_col_conv_kernel<true>);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    static bool raised = false;
+    hipError_t e = st_col_raise_lds_once(raised, es_col_conv_kernel<false>, es_col_conv_kernel<true>);
+    if (e != hipSuccess) return e;
     const bool sums = p.want_grad && xs.grad_shifts;
     StExitShift q;
     q.shifts = (const float2*)xs.shifts; q.index = xs.index;
     q.keep = sums ? xs.keep : nullptr;
     q.part = sums ? xs.part : nullptr;
-    const dim3 grid((unsigned)(batch * p.n_modes * cg.ncg)), block((unsigned)cg.threads);
-    if (conj) hipLaunchKernelGGL(es_col_conv_kernel<true>, grid, block, cg.lds, st, p, fld, hs, q);
-    else hipLaunchKernelGGL(es_col_conv_kernel<false>, grid, block, cg.lds, st, p, fld, hs, q);
-    return hipGetLastError();
+    return st_col_launch(conj ? es_col_conv_kernel<true> : es_col_conv_kernel<false>, cg, batch * p.n_modes, st, p, fld, hs, q);
 }
 
 }  // namespace adm

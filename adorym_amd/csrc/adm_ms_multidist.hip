@@ -10,16 +10,33 @@
 //   fan-in   md_fanin_kernel: per d, ascending: column FFT of G_d's group (after the row FFT over the detector fields),
 //            acc += conj(H_d / (Py*Px)) * spectrum per element in registers; then one column IFFT, stored into sweep field (b, m):
 //            g_S = sum_d IFFT2( conj(H_d) FFT2(G_d) ).  A fixed order, no atomics.
-// At D = 1 both do exactly st_col_conv_kernel's arithmetic.  (dL/dd_d = -sum_k a_k Im(conj(Ghat_d,k) kept_d,k): the twins of these
-// kernels in adm_ms_distgrad.hip, to which the two launchers hand over when the gradient is requested.)  The helpers: adm_ms_col.h.
+// At D = 1 both do exactly st_col_conv_kernel's arithmetic.
+//
+// Detector distances as parameters (adm_plan_set_fanout_distances, adm_multislice_fwd_adj_fanout_dist): the reference's
+// optimize_free_prop for a 3-D object (adorym/propagate.py:274-277, 556-568: fresnel_propagate_wrapped behind the slice loop,
+// H_d = exp(i a d_d) with a = -sigma PI lambda (u^2 + v^2) per nm and d_d in nm).  The distances then live on the device:
+//   table    st_fresnel_table_kernel (adm_ms_streamed.hip): hs[d][y][x] = exp(i a_yx d_d) / (Py*Px) from the float32 distances
+//            (cm) as they sit in the caller's buffer, and ay[y] + ax[x] = a_yx.
+//   fan-out  md_fanout_kernel<true>: the same arithmetic, and the column-transformed spectrum Psihat of every (position, mode)
+//            field stored once (fan_keep section of the workspace).
+//   fan-in   md_fanin_kernel<true>: the same products, the same ascending-d accumulation -- the object and probe gradients keep
+//            their bits: it is the same loop body -- and per d, with Ghat_d the spectrum of G_d after its column transform,
+//              dL/dd_d = - sum_k a_k Im( conj(Ghat_d,k) * Psihat_k * H_d,k / (Py*Px) )
+//            over the workgroup's elements (products in fp32, sums in fp64): ONE partial per (d, workgroup).
+//   reduce   st_dd_reduce_kernel (adm_ms_streamed.hip): the partials of a distance added in a fixed order,
+//            grad_dists[d] += 1e7 * sum (per cm).  No atomics.
+// The launchers pick the <true> instantiations when, and only when, StFanoutLaunch::grad_dists is set.  The helpers: adm_ms_col.h.
 #include <hip/hip_runtime.h>
 #include "adm_host.h"
 #include "adm_ms_col.h"
 
 namespace adm {
 
-__global__ __launch_bounds__(ST_COL_NT) void md_fanout_kernel(MsParams p, const float2* __restrict__ fld, StFanout q) {
+// GRAD: also keeps the spectrum of its group (r.keep)
+template <bool GRAD> __global__ __launch_bounds__(ST_COL_NT) void md_fanout_kernel(MsParams p, const float2* __restrict__ fld, StFanout q, StDistGrad r) {
     extern __shared__ cf md_lds[];
+    // (st_col_begin written out: behind the helper the scheduler orders the prologue of these two kernels differently, and the
+    // instantiation without the gradient is held to the instruction stream it had before the gradient existed)
     const int Py = p.gen_py, Px = p.gen_px, cw = st_cw(Py), ncg = (Px + cw - 1) / cw;
     const int bm = blockIdx.x / ncg, c0 = (blockIdx.x - bm * ncg) * cw;
     const int b = bm / p.n_modes, m = bm - b * p.n_modes;
@@ -30,10 +47,17 @@ __global__ __launch_bounds__(ST_COL_NT) void md_fanout_kernel(MsParams p, const 
     __syncthreads();
     cf v[GEN_E], sp[GEN_E];
     st_col_fft<false>(g, p, v);
+    float2* keep = GRAD ? r.keep + (size_t)bm * row : nullptr;
 #pragma unroll
     for (int j = 0; j < GEN_E; ++j) {
         const int i = g.tid + j * g.nt;
-        if (j < g.ne && i < g.n) sp[j] = g.fld[i];
+        if (j < g.ne && i < g.n) {
+            sp[j] = g.fld[i];
+            if constexpr (GRAD) {
+                const int y = i / g.Px;
+                keep[(size_t)y * Px + c0 + (i - y * g.Px)] = sp[j];
+            }
+        }
     }
     for (int d = 0; d < q.n; ++d) {
         const float2* hs = q.hs + (size_t)d * row;
@@ -52,7 +76,8 @@ __global__ __launch_bounds__(ST_COL_NT) void md_fanout_kernel(MsParams p, const 
     }
 }
 
-__global__ __launch_bounds__(ST_COL_NT) void md_fanin_kernel(MsParams p, float2* __restrict__ fld, StFanout q) {
+// GRAD: also forms this workgroup's share of dL/dd_d, per d, before the conj(H_d) accumulate
+template <bool GRAD> __global__ __launch_bounds__(ST_COL_NT) void md_fanin_kernel(MsParams p, float2* __restrict__ fld, StFanout q, StDistGrad r) {
     extern __shared__ cf md_lds[];
     const int Py = p.gen_py, Px = p.gen_px, cw = st_cw(Py), ncg = (Px + cw - 1) / cw;
     const int bm = blockIdx.x / ncg, c0 = (blockIdx.x - bm * ncg) * cw;
@@ -60,6 +85,7 @@ __global__ __launch_bounds__(ST_COL_NT) void md_fanin_kernel(MsParams p, float2*
     GenCtx g;
     st_col_ctx(g, md_lds, p, c0, cw);
     const size_t row = (size_t)Py * Px;
+    const float2* keep = GRAD ? r.keep + (size_t)bm * row : nullptr;
     cf v[GEN_E], acc[GEN_E];
 #pragma unroll
     for (int j = 0; j < GEN_E; ++j) acc[j] = make_float2(0.f, 0.f);
@@ -68,6 +94,19 @@ __global__ __launch_bounds__(ST_COL_NT) void md_fanin_kernel(MsParams p, float2*
         st_col_load(g, q.dfld + (((size_t)b * q.n + d) * p.n_modes + m) * row, Px, c0);
         __syncthreads();
         st_col_fft<false>(g, p, v);
+        double dsum[1] = {0.0};
+        if constexpr (GRAD) {
+            // the gradient's pass over this thread's elements first, a loop of its own (rolled: beside the 16 accumulators of the
+            // unrolled pass below its operands no longer fit the registers), then the accumulate as it stands without the gradient
+#pragma unroll 1
+            for (int i = g.tid; i < g.n; i += g.nt) {
+                const int y = i / g.Px, x = c0 + (i - y * g.Px);
+                const size_t k = (size_t)y * Px + x;
+                const cf a = g.fld[i];
+                const cf w = cmul(keep[k], hs[k]);
+                dsum[0] += (double)((r.ay[y] + r.ax[x]) * (a.x * w.y - a.y * w.x));
+            }
+        }
 #pragma unroll
         for (int j = 0; j < GEN_E; ++j) {
             const int i = g.tid + j * g.nt;
@@ -75,6 +114,13 @@ __global__ __launch_bounds__(ST_COL_NT) void md_fanin_kernel(MsParams p, float2*
                 const int y = i / g.Px;
                 acc[j] = cadd(acc[j], cmulc(g.fld[i], hs[(size_t)y * Px + c0 + (i - y * g.Px)]));
             }
+        }
+        if constexpr (GRAD) {
+            __shared__ double redd[ST_COL_NT / 64];      // (inside the discarded branch: no LDS without the gradient)
+            // (the barrier inside also stands between this distance's reads of redd on thread 0 and the next distance's writes: those
+            // come behind the barrier that follows the next load)
+            st_block_sum_f64(dsum, redd, g.tid, g.nt, true);
+            if (g.tid == 0) r.part[(size_t)d * gridDim.x + blockIdx.x] = -dsum[0];
         }
     }
 #pragma unroll
@@ -87,35 +133,31 @@ __global__ __launch_bounds__(ST_COL_NT) void md_fanin_kernel(MsParams p, float2*
     st_col_store(g, fld + (size_t)bm * row, Px, c0);
 }
 
-static hipError_t md_raise_lds() {
-    static bool attr_set = false;
-    if (attr_set) return hipSuccess;
-    hipError_t e = st_col_raise_lds(md_fanout_kernel);
-    if (e == hipSuccess) e = st_col_raise_lds(md_fanin_kernel);
-    attr_set = e == hipSuccess;
-    return e;
+static void md_args(const StFanoutLaunch& fo, StFanout& q, StDistGrad& r) {
+    q.hs = fo.hs; q.dfld = fo.fld; q.n = fo.n;
+    r.keep = fo.keep; r.part = fo.part; r.ay = fo.ay; r.ax = fo.ax;
 }
 
 hipError_t ms_multidist_fanout_launch(const MsParams& p, int batch, const float2* fld, const StFanoutLaunch& fo, hipStream_t st) {
-    if (fo.grad_dists) return ms_distgrad_fanout_launch(p, batch, fld, fo, st);
     const StColGeom cg = st_col_geom(p.gen_py, p.gen_px);
-    hipError_t e = md_raise_lds();
+    static bool raised = false;
+    hipError_t e = st_col_raise_lds_once(raised, md_fanout_kernel<false>, md_fanout_kernel<true>);
     if (e != hipSuccess) return e;
     StFanout q;
-    q.hs = fo.hs; q.dfld = fo.fld; q.n = fo.n;
-    hipLaunchKernelGGL(md_fanout_kernel, dim3((unsigned)(batch * p.n_modes * cg.ncg)), dim3((unsigned)cg.threads), cg.lds, st, p, fld, q);
-    return hipGetLastError();
+    StDistGrad r;
+    md_args(fo, q, r);
+    return st_col_launch(fo.grad_dists ? md_fanout_kernel<true> : md_fanout_kernel<false>, cg, batch * p.n_modes, st, p, fld, q, r);
 }
 
 hipError_t ms_multidist_fanin_launch(const MsParams& p, int batch, float2* fld, const StFanoutLaunch& fo, hipStream_t st) {
-    if (fo.grad_dists) return ms_distgrad_fanin_launch(p, batch, fld, fo, st);
     const StColGeom cg = st_col_geom(p.gen_py, p.gen_px);
-    hipError_t e = md_raise_lds();
+    static bool raised = false;
+    hipError_t e = st_col_raise_lds_once(raised, md_fanin_kernel<false>, md_fanin_kernel<true>);
     if (e != hipSuccess) return e;
     StFanout q;
-    q.hs = fo.hs; q.dfld = fo.fld; q.n = fo.n;
-    hipLaunchKernelGGL(md_fanin_kernel, dim3((unsigned)(batch * p.n_modes * cg.ncg)), dim3((unsigned)cg.threads), cg.lds, st, p, fld, q);
-    return hipGetLastError();
+    StDistGrad r;
+    md_args(fo, q, r);
+    return st_col_launch(fo.grad_dists ? md_fanin_kernel<true> : md_fanin_kernel<false>, cg, batch * p.n_modes, st, p, fld, q, r);
 }
 
 }  // namespace adm

@@ -1,7 +1,7 @@
 // Sub-pixel probe positions on streamed plans (adm_plan_set_probe_shift): position b illuminates with the probe modes
 // Fourier-shifted by an offset s = (s_y, s_x) of its own (adorym/util.py:380-397: realign_image_fourier),
 //   probe_b,m = IFFT2( Phi_b * FFT2(probe_m) ),   Phi_b[ky,kx] = exp(-2 PI i (fx s_x + fy s_y)),   f = fftfreq(n, 1),
-// the model of adm_probe_shift (adm_multislice.hip); the phase argument is formed in fp64 here (ps_phase).  The LDS kernels
+// the model of adm_probe_shift (adm_multislice.hip); the phase argument is formed in fp64 here (st_shift_phase, adm_ms_col.h).  The LDS kernels
 // materialise one probe set per position; here the fields live in global memory, so the shift is part of the sweep of ms_streamed_launch
 // (adm_ms_streamed.hip), which calls the launchers at the end of this file.  Launches of one minibatch, beside the sweep's own:
 //   in front   st_row_kernel (batch = 1, from the probe, row FFT) -> phat;  ps_colfft_kernel: column FFT of phat
@@ -25,28 +25,12 @@
 
 namespace adm {
 
-// Phi at spectral element (y, x) for the offset s = (s_y, s_x).  The argument -2 PI (fx s_x + fy s_y) reaches 16 rad at shifts of
-// 2.5 px, where fp32 resolves 1e-6: formed in fp32 (as shift_phases of adm_multislice.hip forms it) that rounding alone puts
-// dL/ds of an exit-wave detector 3.4e-4 from the fp64 model, because the terms of that sum cancel to a thousandth of their size.
-// So: the argument in fp64, reduced to one turn, then sin / cos in fp32 (the scheme of st_sparse_table_kernel); what is left,
-// 8e-5 in that case, is the fp32 rounding of the shifts themselves.
-__device__ __forceinline__ cf ps_phase(int y, int py, int x, int px, float2 s) {
-    const double fy = (double)st_freq_index(y, py) / (double)py, fx = (double)st_freq_index(x, px) / (double)px;
-    double arg = -2.0 * 3.14159265359 * (fx * (double)s.y + fy * (double)s.x);
-    const double two_pi = 6.283185307179586476925287;
-    arg -= two_pi * rint(arg / two_pi);
-    float sn, cs;
-    sincos_fast((float)arg, sn, cs);
-    return make_float2(cs, sn);
-}
-
 // phat <- column FFT(phat) for one (mode, column group): the second half of Phat_m = FFT2(probe_m)
 __global__ __launch_bounds__(ST_COL_NT) void ps_colfft_kernel(MsParams p, float2* __restrict__ phat) {
     extern __shared__ cf ps_lds[];
-    const int Px = p.gen_px, cw = st_cw(p.gen_py), ncg = (Px + cw - 1) / cw;
-    const int m = blockIdx.x / ncg, c0 = (blockIdx.x - m * ncg) * cw;
+    const int Px = p.gen_px;
     GenCtx g;
-    st_col_ctx(g, ps_lds, p, c0, cw);
+    const auto [m, c0] = st_col_begin(g, ps_lds, p);      // (the launch counts modes)
     float2* f = phat + (size_t)m * p.gen_py * Px;
     st_col_load(g, f, Px, c0);
     __syncthreads();
@@ -61,11 +45,10 @@ __global__ __launch_bounds__(ST_COL_NT) void ps_colfft_kernel(MsParams p, float2
 template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT, 4) void ps_col_kernel(MsParams p, float2* __restrict__ fld, StProbeShift q) {
     extern __shared__ cf ps_lds[];
     __shared__ double redd[2 * (ST_COL_NT / 64)];
-    const int Py = p.gen_py, Px = p.gen_px, cw = st_cw(Py), ncg = (Px + cw - 1) / cw;
-    const int bm = blockIdx.x / ncg, c0 = (blockIdx.x - bm * ncg) * cw;
-    const int b = bm / p.n_modes, m = bm - b * p.n_modes;
+    const int Py = p.gen_py, Px = p.gen_px;
     GenCtx g;
-    st_col_ctx(g, ps_lds, p, c0, cw);
+    const auto [bm, c0] = st_col_begin(g, ps_lds, p);
+    const int b = bm / p.n_modes, m = bm - b * p.n_modes;
     const size_t row = (size_t)Py * Px;
     float2* f = fld + (size_t)bm * row;
     const float2* ph_m = q.phat + (size_t)m * row;
@@ -83,7 +66,7 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT, 4) void ps_col_kern
         if (j < g.ne && i < g.n) {
             const int y = i / g.Px, x = c0 + (i - y * g.Px);
             const float fy = st_freq(y, Py), fx = st_freq(x, Px);
-            const cf ph = ps_phase(y, Py, x, Px, s);
+            const cf ph = st_shift_phase(y, Py, x, Px, s);
             const cf a = g.fld[i];
             if (CONJ) {
                 if (sums) {
@@ -107,33 +90,21 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT, 4) void ps_col_kern
     st_col_store(g, f, Px, c0);
 }
 
-static hipError_t ms_probeshift_attr() {
-    static bool attr_set = false;
-    if (attr_set) return hipSuccess;
-    hipError_t e = st_col_raise_lds(ps_colfft_kernel);
-    if (e == hipSuccess) e = st_col_raise_lds(ps_col_kernel<false>);
-    if (e == hipSuccess) e = st_col_raise_lds(ps_col_kernel<true>);
-    if (e == hipSuccess) attr_set = true;
-    return e;
-}
-
 // phat <- column FFT(phat): [M][Py][Px], the row FFT of the probe modes already in it
 hipError_t ms_probeshift_spectrum_launch(const MsParams& p, float2* phat, hipStream_t st) {
     const StColGeom cg = st_col_geom(p.gen_py, p.gen_px);
-    hipError_t e = ms_probeshift_attr();
+    static bool raised = false;
+    hipError_t e = st_col_raise_lds_once(raised, ps_colfft_kernel);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ps_colfft_kernel, dim3((unsigned)(p.n_modes * cg.ncg)), dim3((unsigned)cg.threads), cg.lds, st, p, phat);
-    return hipGetLastError();
+    return st_col_launch(ps_colfft_kernel, cg, p.n_modes, st, p, phat);
 }
 
 hipError_t ms_probeshift_col_launch(const MsParams& p, int batch, float2* fld, bool conj, const StProbeShift& q, hipStream_t st) {
     const StColGeom cg = st_col_geom(p.gen_py, p.gen_px);
-    hipError_t e = ms_probeshift_attr();
+    static bool raised = false;
+    hipError_t e = st_col_raise_lds_once(raised, ps_col_kernel<false>, ps_col_kernel<true>);
     if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)(batch * p.n_modes * cg.ncg)), block((unsigned)cg.threads);
-    if (conj) hipLaunchKernelGGL(ps_col_kernel<true>, grid, block, cg.lds, st, p, fld, q);
-    else hipLaunchKernelGGL(ps_col_kernel<false>, grid, block, cg.lds, st, p, fld, q);
-    return hipGetLastError();
+    return st_col_launch(conj ? ps_col_kernel<true> : ps_col_kernel<false>, cg, batch * p.n_modes, st, p, fld, q);
 }
 
 }  // namespace adm

@@ -26,7 +26,7 @@
 // A plan with probe shifts (adm_plan_set_probe_shift) puts three launches in front of the sweep and up to three behind it
 // (adm_ms_probeshift.hip lists them).  A plan with a detector fan-out (adm_plan_set_detector_fanout) replaces the Fresnel detector's
 // two column launches and runs the detector step over D entries per position (adm_ms_multidist.hip; with the gradient w.r.t. the
-// distances requested: adm_ms_distgrad.hip, and one reduce launch at the end).
+// distances requested: one reduce launch at the end).
 //
 // Row launches: one workgroup per (position, group of whole rows), all modes in turn (the slice factors are loaded once and the
 // tile gradient of the modes is summed in registers).  Column launches: one workgroup per (position, mode, 8 adjacent columns;
@@ -43,7 +43,7 @@ constexpr int ST_ROW_NT = 256;                 // threads of a row workgroup
 constexpr int ST_ROW_E = 8;                    // elements per thread in a row workgroup
 constexpr int ST_ROW_ELEMS = ST_ROW_NT * ST_ROW_E;   // whole rows, at most this many elements (one row of 2048 at the largest)
 constexpr int ST_MAX_SIDE = 2048;
-constexpr int ST_MAX_SLICES = 1024;         // most slices of a sparse plan (st_sparse_reduce_kernel keeps one sum per gap in LDS)
+constexpr int ST_MAX_SLICES = 1024;         // most slices of a sparse plan (st_dd_reduce_kernel keeps one sum per gap in LDS)
 
 // row transform passes of the line group in LDS (INV: conjugate twiddles)
 template <bool INV, int E> __device__ __forceinline__ void st_row_fft(const GenCtx& g, const MsParams& p, cf (&v)[E]) {
@@ -150,10 +150,9 @@ __global__ __launch_bounds__(ST_ROW_NT) void st_row_kernel(MsParams p, StRow r, 
 // field <- column IFFT( H * column FFT(field) ) for one (position, mode, column group); hs = H / (Py*Px) (CONJ: conj)
 template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_kernel(MsParams p, float2* __restrict__ fld, const float2* __restrict__ hs) {
     extern __shared__ cf st_lds[];
-    const int Px = p.gen_px, cw = st_cw(p.gen_py), ncg = (Px + cw - 1) / cw;
-    const int bm = blockIdx.x / ncg, c0 = (blockIdx.x - bm * ncg) * cw;
+    const int Px = p.gen_px;
     GenCtx g;
-    st_col_ctx(g, st_lds, p, c0, cw);
+    const auto [bm, c0] = st_col_begin(g, st_lds, p);
     float2* f = fld + (size_t)bm * p.gen_py * Px;
     st_col_load(g, f, Px, c0);
     __syncthreads();
@@ -176,10 +175,10 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_ke
 __global__ __launch_bounds__(ST_COL_NT) void st_det_kernel(MsParams p, float2* __restrict__ fld, float* __restrict__ part) {
     extern __shared__ cf st_lds[];
     __shared__ float red[ST_COL_NT / 64];
-    const int Py = p.gen_py, Px = p.gen_px, cw = st_cw(Py), ncg = (Px + cw - 1) / cw;
-    const int b = blockIdx.x / ncg, cg = blockIdx.x - b * ncg, c0 = cg * cw;
+    const int Py = p.gen_py, Px = p.gen_px, cw = st_cw(Py);
     GenCtx g;
-    st_col_ctx(g, st_lds, p, c0, cw);
+    const StColWg wg = st_col_begin(g, st_lds, p);      // (one workgroup per position and column group: all modes)
+    const int b = wg.bm, c0 = wg.c0;
     const int M = p.n_modes;
     const bool far = p.det_mode == ADM_DET_FARFIELD_;
     const int fwd_dir = far ? (p.det_inverse ? 2 : 1) : 0, adj_dir = far ? (p.det_inverse ? 1 : 2) : 0;
@@ -260,14 +259,15 @@ __global__ __launch_bounds__(ST_COL_NT) void st_det_kernel(MsParams p, float2* _
 // launches above with hs + s*Py*Px.  When dL/dz is wanted, the column launches are the two kernels below instead: the forward
 // one keeps H_s Psihat'_s / (Py*Px) (in LDS after the multiply), the adjoint one holds Ghat after its column transform and sums
 //   dL/dd_s = - sum_k a_k Im( conj(Ghat_k) * kept_k )
-// over its elements (products in fp32, sums in fp64), ONE partial per workgroup; st_sparse_reduce_kernel adds the partials of a
+// over its elements (products in fp32, sums in fp64), ONE partial per workgroup; st_dd_reduce_kernel adds the partials of a
 // step in a fixed order and accumulates dL/dz_j = 1e7 (dL/dd_{j-1} - dL/dd_j) into the caller's buffer.  No atomics.
 
 // hs[s][y][x] = exp(i a_yx d_s) / (Py*Px): the phase (hundreds of radians at 10 um gaps) in fp64, reduced to one turn, then
-// sin / cos in fp32 and one rounding for the division.  ay[y] + ax[x] = a_yx for the gradient kernel (fp32).
-__global__ __launch_bounds__(256) void st_sparse_table_kernel(StSparseGeom q, const float* __restrict__ z, float2* __restrict__ hs,
-                                                               float* __restrict__ ay, float* __restrict__ ax) {
-    const size_t row = (size_t)q.py * q.px, n = (size_t)(q.n_slices - 1) * row;
+// sin / cos in fp32 and one rounding for the division.  ay[y] + ax[x] = a_yx for the gradient kernels (fp32).  d_s: the gap between
+// slice positions s and s + 1 (q.gaps), or detector distance s of a fan-out whose distances are refined (adm_ms_multidist.hip).
+__global__ __launch_bounds__(256) void st_fresnel_table_kernel(StFresnelGeom q, const float* __restrict__ src, float2* __restrict__ hs,
+                                                                float* __restrict__ ay, float* __restrict__ ax) {
+    const size_t row = (size_t)q.py * q.px, n = (size_t)q.n * row;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const double c = -q.sigma * 3.14159265359 * q.lambda_nm;
     if (i < (size_t)q.py) { const double u = (double)st_freq_index((int)i, q.py) / q.py / q.voxel_nm_y; ay[i] = (float)(c * u * u); }
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256) void st_sparse_table_kernel(StSparseGeom q, co
     const int s = (int)(i / row);
     const int y = (int)((i - (size_t)s * row) / q.px), x = (int)(i - (size_t)s * row - (size_t)y * q.px);
     const double u = (double)st_freq_index(y, q.py) / q.py / q.voxel_nm_y, v = (double)st_freq_index(x, q.px) / q.px / q.voxel_nm_x;
-    const double d = ((double)z[s + 1] - (double)z[s]) * 1e7;
+    const double d = q.gaps ? ((double)src[s + 1] - (double)src[s]) * 1e7 : (double)src[s] * 1e7;
     double ph = c * (u * u + v * v) * d;
     const double two_pi = 6.283185307179586476925287;
     ph -= two_pi * rint(ph / two_pi);
@@ -298,10 +298,9 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_sp
                                                                                              const float2* __restrict__ hs, StSparse q) {
     extern __shared__ cf st_lds[];
     __shared__ double redd[ST_COL_NT / 64];
-    const int Px = p.gen_px, cw = st_cw(p.gen_py), ncg = (Px + cw - 1) / cw;
-    const int bm = blockIdx.x / ncg, c0 = (blockIdx.x - bm * ncg) * cw;
+    const int Px = p.gen_px;
     GenCtx g;
-    st_col_ctx(g, st_lds, p, c0, cw);
+    const auto [bm, c0] = st_col_begin(g, st_lds, p);
     const size_t row = (size_t)p.gen_py * Px;
     float2* f = fld + (size_t)bm * row;
     float2* keep = q.keep + ((size_t)bm * q.n_conv + q.step) * row;
@@ -334,12 +333,14 @@ template <bool CONJ> __global__ __launch_bounds__(ST_COL_NT) void st_col_conv_sp
     st_col_store(g, f, Px, c0);
 }
 
-// gz[j] += 1e7 * (dL/dd_{j-1} - dL/dd_j), dL/dd_s = the npart partials of step s added in a fixed order (one workgroup)
-__global__ __launch_bounds__(256) void st_sparse_reduce_kernel(const double* __restrict__ part, int npart, int n_conv, float* gz) {
+// dL/dd_s = the npart partials of step s added in a fixed order (one workgroup), s < n; then, per cm,
+//   gaps != 0 (sparse plans, d_s the gap behind slice s):        out[j] += 1e7 * (dL/dd_{j-1} - dL/dd_j),  j <= n   (dL/dz)
+//   gaps == 0 (fan-out, d_s detector distance s; n <= 64):       out[s] += 1e7 * dL/dd_s
+__global__ __launch_bounds__(256) void st_dd_reduce_kernel(const double* __restrict__ part, int npart, int n, int gaps, float* out) {
     __shared__ double red[256];
     __shared__ double gd[ST_MAX_SLICES];
     const int t = threadIdx.x;
-    for (int s = 0; s < n_conv; ++s) {
+    for (int s = 0; s < n; ++s) {
         double a = 0.0;
         for (int i = t; i < npart; i += 256) a += part[(size_t)s * npart + i];
         red[t] = a;
@@ -351,9 +352,13 @@ __global__ __launch_bounds__(256) void st_sparse_reduce_kernel(const double* __r
         if (t == 0) gd[s] = red[0];
         __syncthreads();
     }
-    for (int j = t; j <= n_conv; j += 256) {
-        const double d = (j > 0 ? gd[j - 1] : 0.0) - (j < n_conv ? gd[j] : 0.0);
-        gz[j] += (float)(1e7 * d);
+    if (gaps) {
+        for (int j = t; j <= n; j += 256) {
+            const double d = (j > 0 ? gd[j - 1] : 0.0) - (j < n ? gd[j] : 0.0);
+            out[j] += (float)(1e7 * d);
+        }
+    } else {
+        for (int d = t; d < n; d += 256) out[d] += (float)(1e7 * gd[d]);
     }
 }
 
@@ -406,10 +411,10 @@ __global__ __launch_bounds__(256) void st_loss_reduce_kernel(const float* __rest
 bool ms_streamed_supported(int py, int px) { return py >= 1 && px >= 1 && py <= ST_MAX_SIDE && px <= ST_MAX_SIDE; }
 int ms_streamed_col_groups(int py, int px) { return st_col_geom(py, px).ncg; }
 
-hipError_t ms_sparse_table_launch(const StSparseGeom& q, const float* z, float2* hs, float* ay, float* ax, hipStream_t st) {
-    size_t n = (size_t)(q.n_slices - 1) * q.py * q.px;
-    if (n < (size_t)(q.py > q.px ? q.py : q.px)) n = q.py > q.px ? q.py : q.px;
-    hipLaunchKernelGGL(st_sparse_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, z, hs, ay, ax);
+hipError_t ms_fresnel_table_launch(const StFresnelGeom& q, const float* src_cm, float2* hs, float* ay, float* ax, hipStream_t st) {
+    size_t n = (size_t)q.n * q.py * q.px;
+    if (n < (size_t)(q.py > q.px ? q.py : q.px)) n = q.py > q.px ? q.py : q.px;      // (ay and ax are filled whatever n is)
+    hipLaunchKernelGGL(st_fresnel_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, src_cm, hs, ay, ax);
     return hipGetLastError();
 }
 hipError_t ms_sparse_anchor_launch(float* z, int n, hipStream_t st) {
@@ -432,18 +437,11 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
     if (rows < 1) rows = 1;
     if (rows > Py) rows = Py;
     const StColGeom cg = st_col_geom(Py, Px);
-    const int ngr = (Py + rows - 1) / rows, ncg = cg.ncg, cnt = cg.threads;
-    const size_t clds = cg.lds;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = st_col_raise_lds(st_col_conv_kernel<false>);
-        if (e == hipSuccess) e = st_col_raise_lds(st_col_conv_kernel<true>);
-        if (e == hipSuccess) e = st_col_raise_lds(st_det_kernel);
-        if (e == hipSuccess) e = st_col_raise_lds(st_col_conv_sparse_kernel<false>);
-        if (e == hipSuccess) e = st_col_raise_lds(st_col_conv_sparse_kernel<true>);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    const int ngr = (Py + rows - 1) / rows, ncg = cg.ncg;
+    static bool raised = false;
+    hipError_t e = st_col_raise_lds_once(raised, st_col_conv_kernel<false>, st_col_conv_kernel<true>, st_det_kernel,
+                                         st_col_conv_sparse_kernel<false>, st_col_conv_sparse_kernel<true>);
+    if (e != hipSuccess) return e;
     auto row = [&](int step, int mode, int pre, int post, int from_probe, int to_gprobe) {
         StRow r;
         r.rows = rows; r.step = step; r.mode = mode; r.pre = pre; r.post = post; r.from_probe = from_probe; r.to_gprobe = to_gprobe;
@@ -451,9 +449,7 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         return hipGetLastError();
     };
     auto col = [&](const float2* h, bool conj) {
-        if (conj) hipLaunchKernelGGL(st_col_conv_kernel<true>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h);
-        else hipLaunchKernelGGL(st_col_conv_kernel<false>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h);
-        return hipGetLastError();
+        return st_col_launch(conj ? st_col_conv_kernel<true> : st_col_conv_kernel<false>, cg, batch * M, st, p, fld, h);
     };
     // convolution `step` of the slice loop: the plan's one H, or a sparse plan's H_step -- through the kernels that also keep the
     // spectrum / form the dL/dd partials when the slice-position gradient is wanted
@@ -465,9 +461,7 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         if (!zgrad) return col(h, conj);
         StSparse q;
         q.keep = sp->keep; q.part = sp->part; q.ay = sp->ay; q.ax = sp->ax; q.step = step; q.n_conv = S - 1;
-        if (conj) hipLaunchKernelGGL(st_col_conv_sparse_kernel<true>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h, q);
-        else hipLaunchKernelGGL(st_col_conv_sparse_kernel<false>, dim3(batch * M * ncg), dim3(cnt), clds, st, p, fld, h, q);
-        return hipGetLastError();
+        return st_col_launch(conj ? st_col_conv_sparse_kernel<true> : st_col_conv_sparse_kernel<false>, cg, batch * M, st, p, fld, h, q);
     };
     // detector fan-out (adm_ms_multidist.hip): the detector step sends every sweep field to fo->n planes; the row launches around
     // the detector kernel, that kernel and the loss reduction then run over the batch * fo->n detector entries
@@ -480,15 +474,15 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         return hipGetLastError();
     };
     // (p, batch, fld: the sweep's own, or -- with a fan-out -- the detector entries'; the names of the outer ones on purpose)
+    StColGeom dg = cg;
+    dg.lds += (size_t)Py * cg.cw * sizeof(float);      // (the detector kernel's per-element factor behind the twiddles)
     auto detect = [&](const MsParams& p, int batch, float2* fld) {
-        hipLaunchKernelGGL(st_det_kernel, dim3(batch * ncg), dim3(cnt), clds + (size_t)Py * cg.cw * sizeof(float), st, p, fld, part);
-        hipError_t e = hipGetLastError();
+        hipError_t e = st_col_launch(st_det_kernel, dg, batch, st, p, fld, part);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(st_loss_reduce_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, part, ncg, batch, p.loss_sum);
         return hipGetLastError();
     };
     auto det_col = [&](bool conj) { return xs ? ms_exitshift_col_launch(p, batch, fld, hfree_s, conj, *xs, st) : col(hfree_s, conj); };
-    hipError_t e = hipSuccess;
     // sub-pixel probe positions: Phat = FFT2(probe) once, then the fields of every (position, mode) up to their row IFFT, which
     // the first row launch of the sweep does in front of its modulation
     StProbeShift pq;
@@ -537,10 +531,13 @@ hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* 
         }
     }
     if (e == hipSuccess && zgrad) {
-        hipLaunchKernelGGL(st_sparse_reduce_kernel, dim3(1), dim3(256), 0, st, sp->part, batch * M * ncg, S - 1, sp->grad_z);
+        hipLaunchKernelGGL(st_dd_reduce_kernel, dim3(1), dim3(256), 0, st, sp->part, batch * M * ncg, S - 1, 1, sp->grad_z);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && fo && fo->grad_dists) e = ms_distgrad_sum_launch(p, batch, *fo, st);
+    if (e == hipSuccess && fo && fo->grad_dists) {
+        hipLaunchKernelGGL(st_dd_reduce_kernel, dim3(1), dim3(256), 0, st, fo->part, batch * M * ncg, fo->n, 0, fo->grad_dists);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess && xs && xs->grad_shifts) {
         hipLaunchKernelGGL(st_shift_reduce_kernel, dim3(batch), dim3(256), 0, st, xs->part, batch, M * ncg, xs->index, xs->grad_shifts);
         e = hipGetLastError();

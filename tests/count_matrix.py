@@ -337,14 +337,14 @@ KERNEL_ROWS = {
     'st_loss_reduce_kernel': ('adm_ms_streamed.hip', 'test_streamed', ['streamed_B256', 'streamed_B257']),
     'st_shift_reduce_kernel': ('adm_ms_streamed.hip', 'test_streamed', ['streamed_shift_4x1032_M2', 'streamed_shift_B300_mixed']),
     'st_col_conv_sparse_kernel': ('adm_ms_streamed.hip', 'test_sparse', ['sparse_B257', 'sparse_B3_M5']),
-    'st_sparse_reduce_kernel': ('adm_ms_streamed.hip', 'test_sparse', ['sparse_B257', 'sparse_B3_M5']),
+    'st_dd_reduce_kernel': ('adm_ms_streamed.hip', 'test_sparse', ['sparse_B257', 'sparse_B3_M5']),
     'es_col_conv_kernel': ('adm_ms_exitshift.hip', 'test_exit_shift', ['exit_shift_B257']),
     'ps_col_kernel': ('adm_ms_probeshift.hip', 'test_streamed', ['streamed_shift_B257', 'streamed_shift_4x1032_M2']),
 }
 # kernels of those files that take no count: one workgroup per row group of ONE probe set, a table per slice, one anchor
 NO_COUNT = {'ps_colfft_kernel': 'the spectrum of the M shared probe modes: its grid is M * column groups, run with M = 2 by '
                                 'streamed_shift_4x1032_M2 but never beyond the modes the shape matrix runs',
-            'st_sparse_table_kernel': 'one thread per element of the S - 1 transfer functions', 'st_sparse_anchor_kernel': 'one workgroup'}
+            'st_fresnel_table_kernel': 'one thread per element of the S - 1 (a fan-out: D) transfer functions', 'st_sparse_anchor_kernel': 'one workgroup'}
 
 
 # ---------------------------------------------------------------------------------------------------------------- the engine

@@ -231,7 +231,7 @@ SPARSE_CASES = {
     'P135x201_S3_real_imag': dict(P=(135, 201), S=3, unknown_type='real_imag'),
     'P2048x5_S3_exit_wave': dict(P=(2048, 5), S=3, free_prop=0, B=5),
     'P1536x1280_S3_B4': dict(P=(1536, 1280), S=3, B=4),
-    'P24_S40': dict(P=24, S=40, B=5),            # 39 gaps in st_sparse_reduce_kernel
+    'P24_S40': dict(P=24, S=40, B=5),            # 39 gaps in st_dd_reduce_kernel
 }
 # the restatement's own fp32 dL/dz error on these cases (CPU; the sweep asserts >= 1e-6): 2.6e-5, 2.0e-5, 6.5e-5, 7.3e-5, 2.7e-6,
 # 7.9e-5, 2.5e-5.  An exit-wave detector averages the rounding errors out: (2048, 5) with B = 11 has 8e-8 and would measure the
@@ -245,10 +245,10 @@ KERNELS = {
     'st_col_conv_kernel<true>': (_M, ('test_shapes_vs_oracle', 'test_sequences_vs_oracle')),
     'st_det_kernel': (_M, ('test_shapes_vs_oracle', 'test_sequences_vs_oracle')),
     'st_loss_reduce_kernel': (_M, ('test_shapes_vs_oracle', 'test_sequences_vs_oracle')),
-    'st_sparse_table_kernel': (_M, ('test_sparse_vs_restatement',)),
+    'st_fresnel_table_kernel': (_M, ('test_sparse_vs_restatement',)),
     'st_col_conv_sparse_kernel<false>': (_M, ('test_sparse_vs_restatement',)),
     'st_col_conv_sparse_kernel<true>': (_M, ('test_sparse_vs_restatement',)),
-    'st_sparse_reduce_kernel': (_M, ('test_sparse_vs_restatement',)),
+    'st_dd_reduce_kernel': (_M, ('test_sparse_vs_restatement',)),
     'st_sparse_anchor_kernel': (_M, ('test_most_slice_positions',)),
     'st_shift_reduce_kernel': ('test_gpu_prj_offset', ('test_kernels_vs_reference', 'test_geometries_vs_restatement')),
 }

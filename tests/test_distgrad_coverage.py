@@ -1,7 +1,9 @@
-"""CPU-only bookkeeping of adm_ms_distgrad.hip (the distances of the detector fan-out as parameters on the device): the two entry
-points are declared, exported and bound; every __global__ kernel in the file is named by a GPU test; the file is built and
-documented; its recorded resource usage shows no scratch; and with no gradient requested ms_streamed_launch does not reach the
-file -- read from the sources, as tests/test_multidist3d_coverage.py does."""
+"""CPU-only bookkeeping of the distance gradient of the detector fan-out (the distances as parameters on the device): the
+instantiations md_fanout_kernel<true> / md_fanin_kernel<true> of adm_ms_multidist.hip and the table and reduce kernels they share
+with sparse multislice (st_fresnel_table_kernel, st_dd_reduce_kernel of adm_ms_streamed.hip).  The two entry points are declared,
+exported and bound; every kernel is named by a GPU test; the code is built and documented; its recorded resource usage shows no
+scratch; and with no gradient requested ms_streamed_launch does not reach the gradient code -- read from the sources, as
+tests/test_multidist3d_coverage.py does."""
 import ctypes
 import os
 import re
@@ -11,12 +13,12 @@ from tests.test_kernel_matrix_coverage import _function_body
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'adorym_amd', 'csrc')
 
-# kernel: (test module, tests whose docstrings name it)
+# kernel (templates: the instantiation): (source file, test module, tests whose docstrings name it)
 KERNELS = {
-    'dg_table_kernel': ('test_gpu_multidist3d_dist', ['test_kernels_vs_reference', 'test_changed_distances_rebuild_the_table']),
-    'dg_fanout_kernel': ('test_gpu_multidist3d_dist', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
-    'dg_fanin_kernel': ('test_gpu_multidist3d_dist', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
-    'dg_reduce_kernel': ('test_gpu_multidist3d_dist', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
+    'st_fresnel_table_kernel': ('adm_ms_streamed.hip', 'test_gpu_multidist3d_dist', ['test_kernels_vs_reference', 'test_changed_distances_rebuild_the_table']),
+    'md_fanout_kernel<true>': ('adm_ms_multidist.hip', 'test_gpu_multidist3d_dist', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
+    'md_fanin_kernel<true>': ('adm_ms_multidist.hip', 'test_gpu_multidist3d_dist', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
+    'st_dd_reduce_kernel': ('adm_ms_streamed.hip', 'test_gpu_multidist3d_dist', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
 }
 
 
@@ -49,43 +51,57 @@ def test_the_entry_points_are_declared_exported_and_bound():
 
 
 def test_every_kernel_is_named_by_a_gpu_test():
-    dg = _read('adm_ms_distgrad.hip')
-    found = set()
-    for m in re.finditer(r'(template\s*<[^>]*>\s*)?__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(\w+)\s*\(', dg):
-        assert not m.group(1), 'a template: list its instantiations in KERNELS and check that each is launched'
-        found.add(m.group(2))
-    assert len(re.findall(r'__global__', dg)) == len(KERNELS) and found == set(KERNELS), found ^ set(KERNELS)
-    for k, (module, tests) in KERNELS.items():
+    md, st = _read('adm_ms_multidist.hip'), _read('adm_ms_streamed.hip')
+    assert not os.path.exists(os.path.join(CSRC, 'adm_ms_distgrad.hip'))
+    # templates are listed by instantiation (tests/test_multidist3d_coverage.py holds the file to exactly these two templates)
+    for k, (src, module, tests) in KERNELS.items():
+        name, inst = re.match(r'(\w+)(<true>)?$', k).groups()
+        head = re.search(r'(template\s*<[^>]*>\s*)?__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+%s\s*\(' % name, _read(src))
+        assert head and bool(head.group(1)) == bool(inst), k
         text = open(os.path.join(ROOT, 'tests', module + '.py')).read()
         for t in tests:
             m = re.search(r'^def %s\(.*?\n    """(.*?)"""' % t, text, re.M | re.S)
             assert m and k in m.group(1), (k, t)
-        assert len(re.findall(r'hipLaunchKernelGGL\(%s\b' % k, dg)) == 1, k
-    code = re.sub(r'//.*', '', dg)
-    assert not re.search(r'\batomic\w*\s*\(', code)              # fixed orders of all sums
-    assert '#include "adm_ms_col.h"' in dg and 'st_col_geom(' in dg and 'st_col_raise_lds(' in dg and 'st_block_sum_f64(' in dg
-    for k in ('dg_fanout_kernel', 'dg_fanin_kernel'):
-        assert re.search(r'__launch_bounds__\(ST_COL_NT\)\s+void\s+%s\b' % k, dg), k
+    # each is launched exactly once for the distances: the instantiations by the launch line that picks them, the table by its
+    # launcher, the reduce kernel by the one launch with gaps = 0
+    for k in ('md_fanout_kernel', 'md_fanin_kernel'):
+        assert len(re.findall(r'st_col_launch\(fo\.grad_dists \? %s<true> : %s<false>,' % (k, k), md)) == 1, k
+        assert re.search(r'__launch_bounds__\(ST_COL_NT\)\s+void\s+%s\b' % k, md), k
+    assert len(re.findall(r'hipLaunchKernelGGL\(st_fresnel_table_kernel\b', st)) == 1
+    assert len(re.findall(r'hipLaunchKernelGGL\(st_dd_reduce_kernel, [^;]*, 0, fo->grad_dists\);', st)) == 1
+    assert len(re.findall(r'hipLaunchKernelGGL\(st_dd_reduce_kernel\b', st)) == 2          # (the other: the gaps of a sparse plan)
+    # fixed orders of all sums: no atomics in the fan-out's file nor in the two shared kernels
+    assert not re.search(r'\batomic\w*\s*\(', re.sub(r'//.*', '', md))
+    for k in ('st_fresnel_table_kernel', 'st_dd_reduce_kernel'):
+        assert not re.search(r'\batomic\w*\s*\(', re.sub(r'//.*', '', _function_body(st, r'void\s+%s\s*\(' % k))), k
+    assert '#include "adm_ms_col.h"' in md and 'st_col_geom(' in md and 'st_col_raise_lds_once(' in md and 'st_block_sum_f64(' in md
 
 
-def test_without_a_request_the_streamed_launch_does_not_reach_the_file():
-    """The only ways into adm_ms_distgrad.hip from a launch: the first line of the two fan-out launchers and the sum launch at the
-    end of ms_streamed_launch, each behind StFanoutLaunch::grad_dists; and that pointer is set in one place, behind the caller's
-    buffer and want_grad."""
+def test_without_a_request_the_streamed_launch_does_not_reach_the_gradient_code():
+    """The only ways into the gradient code from a launch: the <true> instantiations in the launch line of the two fan-out launchers
+    and the gaps = 0 reduce launch at the end of ms_streamed_launch, each behind StFanoutLaunch::grad_dists; and that pointer is set
+    in one place, behind the caller's buffer and want_grad."""
     md, st, api = _read('adm_ms_multidist.hip'), _read('adm_ms_streamed.hip'), _read('adm_api.hip')
-    calls = re.findall(r'^.*\bms_distgrad_\w+\(.*$', md + st, re.M)
-    assert len(calls) == 3, calls
-    assert sum('if (fo.grad_dists) return ms_distgrad_fanout_launch(p, batch, fld, fo, st);' in c for c in calls) == 1
-    assert sum('if (fo.grad_dists) return ms_distgrad_fanin_launch(p, batch, fld, fo, st);' in c for c in calls) == 1
-    assert sum('if (e == hipSuccess && fo && fo->grad_dists) e = ms_distgrad_sum_launch(p, batch, *fo, st);' in c for c in calls) == 1
+    # <true> is named where the LDS limit is raised and behind `fo.grad_dists ?`, nowhere else in the code
+    code = re.sub(r'//.*', '', md)
+    for k in ('md_fanout_kernel', 'md_fanin_kernel'):
+        uses = [m.start() for m in re.finditer(r'%s<true>' % k, code)]
+        assert len(uses) == 2, (k, uses)
+        assert code[:uses[0]].rstrip().endswith('st_col_raise_lds_once(raised, %s<false>,' % k)
+        assert code[:uses[1]].endswith('st_col_launch(fo.grad_dists ? ')
+    body = _function_body(st, r'hipError_t\s+ms_streamed_launch\s*\(')
+    assert re.search(r'if \(e == hipSuccess && fo && fo->grad_dists\) \{\s*hipLaunchKernelGGL\(st_dd_reduce_kernel, dim3\(1\), dim3\(256\), 0, st, '
+                     r'fo->part, batch \* M \* ncg, fo->n, 0, fo->grad_dists\);', body)
+    assert len(re.findall(r'\bgrad_dists\b', re.sub(r'//.*', '', md + st))) == 4          # (two launch lines, the condition, the argument)
+    assert 'ms_distgrad_' not in md + st + api + _read('adm_host.h')
     assert 'float* grad_dists = nullptr;' in _read('adm_host.h')
     sets = re.findall(r'^.*\bgrad_dists\s*=[^=].*$', api, re.M)
     assert len(sets) == 1 and 'fo.grad_dists = grad_dists;' in sets[0], sets
     body = _function_body(api, r'static int streamed_launch\s*\(')
     assert re.search(r'if \(grad_dists && p\.want_grad\) \{\s*fo\.grad_dists = grad_dists;', body)
-    # the table is rebuilt only behind the dirty flag
-    assert re.search(r'if \(plan->fan_dists_dirty\) \{[^}]*ms_distgrad_table_launch\(', body, re.S)
-    assert len(re.findall(r'ms_distgrad_table_launch\(', api)) == 1
+    # the table is rebuilt only behind the dirty flag, by the launcher it shares with the sparse plan's gaps
+    assert re.search(r'if \(plan->fan_dists_dirty\) \{[^}]*q\.gaps = 0;[^}]*ms_fresnel_table_launch\(q, plan->fan_dists_dev,', body, re.S)
+    assert len(re.findall(r'ms_fresnel_table_launch\(q, plan->fan_dists_dev', api)) == 1 and len(re.findall(r'ms_fresnel_table_launch\(', api)) == 2
 
 
 def test_the_workspace_sections_exist_only_on_a_refining_plan():
@@ -99,17 +115,18 @@ def test_the_workspace_sections_exist_only_on_a_refining_plan():
 
 def test_the_file_is_built_and_documented():
     build = _read('build.py')
-    assert "'adm_ms_distgrad.hip'" in re.search(r'^SRCS = \[.*\]$', build, re.M).group(0)
+    srcs = re.search(r'^SRCS = \[.*\]$', build, re.M).group(0)
+    assert "'adm_ms_multidist.hip'" in srcs and "'adm_ms_streamed.hip'" in srcs and 'distgrad' not in srcs
     for doc in ('README.md', 'DESIGN.md'):
         text = open(os.path.join(ROOT, doc)).read()
-        assert 'adm_ms_distgrad.hip' in text and 'fanout_free_prop' in text, doc
+        assert 'md_fanin_kernel<true>' in text and 'st_dd_reduce_kernel' in text and 'fanout_free_prop' in text, doc
     assert os.path.exists(os.path.join(ROOT, 'tools', 'bench_multidist3d_dist.py'))
 
 
 def test_resource_usage_is_recorded_without_scratch():
     text = open(os.path.join(ROOT, 'profiles', 'distgrad', 'resource_usage.txt')).read()
     names = re.findall(r'Function Name: (\S+)', text)
-    for k in KERNELS:
+    for k in ('st_fresnel_table_kernel', 'md_fanout_kernelILb1E', 'md_fanin_kernelILb1E', 'st_dd_reduce_kernel'):      # (<true> as the compiler names it)
         assert any(k in n for n in names), k
     scratch = re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', text)
     assert len(scratch) == len(names) == len(KERNELS) and set(scratch) == {'0'}

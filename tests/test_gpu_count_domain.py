@@ -120,7 +120,7 @@ def test_exit_shift(A, ctx):
 
 @pytest.mark.parametrize('name', family_rows('sparse'))
 def test_sparse(A, ctx, name):
-    """st_col_conv_sparse_kernel and st_sparse_reduce_kernel (its npart = B * M * column groups partials) at B = 257 and M = 5."""
+    """st_col_conv_sparse_kernel and st_dd_reduce_kernel (its npart = B * M * column groups partials) at B = 257 and M = 5."""
     case = CM.build(name)
     r64, e32 = SP.yardstick(case)
     res = SP.run_sparse(A, ctx, case, keep_engine=True)

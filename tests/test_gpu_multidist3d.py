@@ -126,7 +126,7 @@ def fixture_case(F, name):
 
 @pytest.mark.parametrize('name', FIXTURE_CASES)
 def test_kernels_vs_reference(A, ctx, F, name):
-    """md_fanout_kernel, md_fanin_kernel: prediction, loss, object gradient and probe gradients against the reference's fp64 run, the
+    """md_fanout_kernel<false>, md_fanin_kernel<false>: prediction, loss, object gradient and probe gradients against the reference's fp64 run, the
     reference's own fp32 run as the yardstick of the 3x rule (field 12 x 20, S = 5, D = 3; one and two modes, both sign
     conventions, magnitude and intensity data)."""
     case = fixture_case(F, name)
@@ -231,7 +231,7 @@ def run_one_distance_fanout(A, ctx, case):
 
 @pytest.mark.parametrize('shape,D', GEOMETRY_CASES, ids=lambda v: '%dx%d' % v if isinstance(v, tuple) else 'D%d' % v)
 def test_geometries_vs_restatement(A, ctx, shape, D):
-    """md_fanout_kernel, md_fanin_kernel at every column-launch geometry (tall, narrow fields: the full LDS layout at small cost);
+    """md_fanout_kernel<false>, md_fanin_kernel<false> at every column-launch geometry (tall, narrow fields: the full LDS layout at small cost);
     S = 2, B = 3 positions over the object's edges, D = 2 at every field and D = 1, D = 4 at one each."""
     case = make_case(shape, D=D, **GEOMETRIES[shape])
     r64, r32 = yardstick((shape, D), case)

@@ -1,4 +1,4 @@
-"""The distances of the detector fan-out as parameters on the GPU (pytest -m gpu): adm_ms_distgrad.hip through the engine
+"""The distances of the detector fan-out as parameters on the GPU (pytest -m gpu): the gradient instantiations of adm_ms_multidist.hip through the engine
 (MultisliceEngine(detector_fanout=True, refine_distances=True), multislice(grad_dists=...)) and the C ABI
 (adm_plan_set_fanout_distances, adm_multislice_fwd_adj_fanout_dist) as the engine calls it.
 
@@ -98,7 +98,7 @@ def fixture_case(F, name):
 
 @pytest.mark.parametrize('name', MD.FIXTURE_CASES)
 def test_kernels_vs_reference(A, ctx, F, name):
-    """dg_table_kernel, dg_fanout_kernel, dg_fanin_kernel, dg_reduce_kernel: prediction, loss, object gradient, probe gradient and
+    """st_fresnel_table_kernel, md_fanout_kernel<true>, md_fanin_kernel<true>, st_dd_reduce_kernel: prediction, loss, object gradient, probe gradient and
     dL/d free_prop_cm against the reference's fp64 run with optimize_free_prop (field 12 x 20, S = 5, D = 3, the model's distances
     off the data's by 10 %, -8 %, 5 %; one and two modes, both sign conventions, magnitude and intensity data)."""
     case = fixture_case(F, name)
@@ -129,7 +129,7 @@ GEOMETRIES = {
     '1025x12_cw4': dict(P=FM.TALL, B=2, D=3, M=1),                            # column width 4, the 1024 / 1025 boundary
     'M2': dict(B=3, D=2, M=2),
     'M4_D3': dict(B=3, D=3, M=4),
-    'B85_255_partials': dict(B=85, D=2, M=1),                                 # B * M * ncg = 255: below dg_reduce_kernel's stride
+    'B85_255_partials': dict(B=85, D=2, M=1),                                 # B * M * ncg = 255: below st_dd_reduce_kernel's stride
     'B86_258_partials': dict(B=86, D=2, M=1),                                 # ... and 258: above it
     'sigma_m1': dict(B=3, D=3, M=2, sign_convention=-1),
     'repeated': dict(B=3, D=3, M=2, dists=FM.DISTANCE_SETS['repeated']),
@@ -168,7 +168,7 @@ def test_the_geometries_sit_on_both_sides_of_the_reduce_stride():
 
 @pytest.mark.parametrize('name', list(GEOMETRIES))
 def test_geometries_vs_restatement(A, ctx, name):
-    """dg_fanout_kernel, dg_fanin_kernel, dg_reduce_kernel over the column geometries (clipped last group, cw = 4 at 1025 rows), the
+    """md_fanout_kernel<true>, md_fanin_kernel<true>, st_dd_reduce_kernel over the column geometries (clipped last group, cw = 4 at 1025 rows), the
     fan-out limit D = 64, one to four modes, both sides of the reduce kernel's stride of 256 partials, sigma = -1, a repeated
     distance and an aliased set: dL/dd against the fp64 restatement, and prediction, loss, object and probe gradients as the
     fan-out tests judge them."""
@@ -244,7 +244,7 @@ def test_device_table_agrees_with_host_table(A, ctx):
 
 
 def test_changed_distances_rebuild_the_table(A, ctx):
-    """dg_table_kernel: after dists.set(new) + dists_changed() the predictions are those of a fresh engine built at ``new``, bit
+    """st_fresnel_table_kernel: after dists.set(new) + dists_changed() the predictions are those of a fresh engine built at ``new``, bit
     for bit; the distances the engine was built with are gone."""
     case = built('M2', **GEOMETRIES['M2'])[0]
     new = round32([1.3 * d for d in case['dists']])

@@ -256,7 +256,7 @@ def test_sides_at_the_edge(A, ctx):
 
 def test_most_slice_positions(A, ctx):
     """A sparse plan of ST_MAX_SLICES + 1 slice positions is refused with a message; one of exactly ST_MAX_SLICES is accepted
-    and runs at an 8 x 8 field (1023 gaps in st_sparse_reduce_kernel's LDS) against the restatement, whose two runs take a few
+    and runs at an 8 x 8 field (1023 gaps in st_dd_reduce_kernel's LDS) against the restatement, whose two runs take a few
     seconds; st_sparse_anchor_kernel moves all 1024 positions."""
     n = SM.ST_MAX_SLICES
     pos = np.array([(0, 0), (3, 5)])

@@ -168,7 +168,7 @@ def test_features_vs_oracle(A, ctx, name):
     """Detector, loss, unknown-type and binning variants of the sweep behind shifted probes, at 40 x 52.
 
     near_field: with an exit-wave detector and this weak object the terms of dL/ds cancel to 2e-4 ... 4e-4 against 0.05 ... 0.2
-    in the far field, so the case is the one that sees the rounding of the phase argument (ps_phase forms it in fp64)."""
+    in the far field, so the case is the one that sees the rounding of the phase argument (st_shift_phase forms it in fp64)."""
     kw = dict(S=2, B=6, pp='shifts')
     kw.update(FEATURE_CASES[name])
     report_and_check(run_ps(A, ctx, case_of((40, 52), **kw)), name)

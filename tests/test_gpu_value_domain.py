@@ -151,7 +151,7 @@ def test_large_shifts_tuned(A, ctx, P, M, cache):
 
 @pytest.mark.parametrize('P', VM.STREAMED_FIELDS, ids=_id)
 def test_large_shifts_streamed_probe_shift(A, ctx, P):
-    """ps_phase of adm_ms_probeshift.hip at the same shifts, by test_gpu_streamed_probe_shift's checks."""
+    """st_shift_phase (adm_ms_col.h) in adm_ms_probeshift.hip at the same shifts, by test_gpu_streamed_probe_shift's checks."""
     from tests import test_gpu_streamed_probe_shift as PS
     res = PS.run_ps(A, ctx, shift_case(P, S=2, B=6), canaries=True)
     PS.report_and_check(res, 'streamed shifts %s' % (P,))
@@ -160,7 +160,7 @@ def test_large_shifts_streamed_probe_shift(A, ctx, P):
 @pytest.mark.parametrize('free_prop', ['fresnel', 0], ids=['fresnel', 'exit_wave'])
 @pytest.mark.parametrize('P', [(24, 20), (640, 12)], ids=_id)
 def test_large_shifts_exit_wave(A, ctx, P, free_prop):
-    """es_phase of adm_ms_exitshift.hip at the same shifts: check_3x / gs_bar of test_gpu_prj_offset with prj_offset_ref, which
+    """st_shift_phase (adm_ms_col.h) in adm_ms_exitshift.hip at the same shifts: check_3x / gs_bar of test_gpu_prj_offset with prj_offset_ref, which
     forms its fp32 argument in fp32 as the reference does, as the yardstick."""
     from tests import test_gpu_prj_offset as PO
     fp = PO.FREE_PROP_CM if free_prop == 'fresnel' else 0

@@ -11,11 +11,13 @@ from tests.test_kernel_matrix_coverage import _function_body
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'adorym_amd', 'csrc')
 
-# kernel: (test module, tests whose docstrings name it)
+# kernel instantiation: (test module, tests whose docstrings name it); the instantiations with the distance gradient are listed, and
+# held to their tests, by tests/test_distgrad_coverage.py
 KERNELS = {
-    'md_fanout_kernel': ('test_gpu_multidist3d', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
-    'md_fanin_kernel': ('test_gpu_multidist3d', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
+    'md_fanout_kernel<false>': ('test_gpu_multidist3d', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
+    'md_fanin_kernel<false>': ('test_gpu_multidist3d', ['test_kernels_vs_reference', 'test_geometries_vs_restatement']),
 }
+WITH_GRADIENT = {'md_fanout_kernel<true>', 'md_fanin_kernel<true>'}
 
 
 def _read(name):
@@ -39,23 +41,29 @@ def test_the_entry_point_is_declared_exported_and_bound():
 
 
 def test_every_kernel_is_named_by_a_gpu_test():
+    from tests.test_distgrad_coverage import KERNELS as DIST
     md = _read('adm_ms_multidist.hip')
     found = set()
-    for m in re.finditer(r'(template\s*<[^>]*>\s*)?__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(\w+)\s*\(', md):
-        assert not m.group(1), 'a template: list its instantiations in KERNELS and check that each is launched'
-        found.add(m.group(2))
-    assert len(re.findall(r'__global__', md)) == 2 and found == set(KERNELS), found ^ set(KERNELS)
+    for m in re.finditer(r'(template\s*<([^>]*)>\s*)?__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(\w+)\s*\(', md):
+        assert m.group(1) and m.group(2).strip() == 'bool GRAD', 'both kernels are templates on the distance gradient'
+        found |= {m.group(3) + '<false>', m.group(3) + '<true>'}
+    assert len(re.findall(r'__global__', md)) == 2 and found == set(KERNELS) | WITH_GRADIENT, found ^ set(KERNELS)
+    assert WITH_GRADIENT <= set(DIST)
     for k, (module, tests) in KERNELS.items():
         text = open(os.path.join(ROOT, 'tests', module + '.py')).read()
         for t in tests:
             m = re.search(r'^def %s\(.*?\n    """(.*?)"""' % t, text, re.M | re.S)
             assert m and k in m.group(1), (k, t)
-        # every kernel (the file has no template: one instantiation each) is launched, once
-        assert len(re.findall(r'hipLaunchKernelGGL\(%s\b' % k, md)) == 1, k
+    # every instantiation is launched, once: one launch line per template, which picks by the request
+    for k in ('md_fanout_kernel', 'md_fanin_kernel'):
+        line = 'st_col_launch(fo.grad_dists ? %s<true> : %s<false>, cg, batch * p.n_modes, st, p, fld, q, r);' % (k, k)
+        assert md.count(line) == 1 and len(re.findall(r'st_col_launch\(', md)) == 2, k
+        assert re.search(r'__launch_bounds__\(ST_COL_NT\)\s+void\s+%s\b' % k, md), k
+    assert 'hipLaunchKernelGGL' not in md
     code = re.sub(r'//.*', '', md)
-    assert not re.search(r'\batomic\w*\s*\(', code)              # a fixed order of the sum over the distances
+    assert not re.search(r'\batomic\w*\s*\(', code)              # a fixed order of the sum over the distances and of the partials
     assert 'reduce_kernel' not in code
-    assert '#include "adm_ms_col.h"' in md and 'st_col_geom(' in md and 'st_col_raise_lds(' in md
+    assert '#include "adm_ms_col.h"' in md and 'st_col_geom(' in md and 'st_col_raise_lds_once(' in md and 'st_block_sum_f64(' in md
 
 
 def test_the_streamed_launch_reaches_the_file_only_with_its_pointer():
@@ -88,7 +96,7 @@ def test_the_file_is_built_and_documented():
 def test_resource_usage_is_recorded_without_scratch():
     text = open(os.path.join(ROOT, 'profiles', 'multidist3d', 'resource_usage.txt')).read()
     names = re.findall(r'Function Name: (\S+)', text)
-    for k in KERNELS:
+    for k in ('md_fanout_kernelILb0E', 'md_fanin_kernelILb0E'):          # (the <false> instantiations as the compiler names them)
         assert any(k in n for n in names), k
     scratch = re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', text)
     assert len(scratch) == len(names) == 2 and set(scratch) == {'0'}

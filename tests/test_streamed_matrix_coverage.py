@@ -98,9 +98,13 @@ def test_the_mirror_follows_the_row_groups_of_the_launch():
     assert re.search(r'int rows = ST_ROW_ELEMS / Px;\s*if \(rows < 1\) rows = 1;\s*if \(rows > Py\) rows = Py;', body)
     # the column launches: the one geometry function of adm_ms_col.h; the detector kernel's float plane on top of its LDS bytes
     assert 'const StColGeom cg = st_col_geom(Py, Px);' in body
-    assert 'const int ngr = (Py + rows - 1) / rows, ncg = cg.ncg, cnt = cg.threads;' in body and 'const size_t clds = cg.lds;' in body
+    assert 'const int ngr = (Py + rows - 1) / rows, ncg = cg.ncg;' in body
     assert 'int ms_streamed_col_groups(int py, int px) { return st_col_geom(py, px).ncg; }' in st
-    assert 'dim3(batch * ncg), dim3(cnt), clds + (size_t)Py * cg.cw * sizeof(float), st, p, fld, part);' in body
+    assert re.search(r'StColGeom dg = cg;\s*dg\.lds \+= \(size_t\)Py \* cg\.cw \* sizeof\(float\);', body)
+    assert 'st_col_launch(st_det_kernel, dg, batch, st, p, fld, part);' in body
+    # ... and the one launch line: groups * cg.ncg workgroups of cg.threads threads with cg.lds bytes
+    launch = _function_body(_read('adm_ms_col.h'), r'inline\s+hipError_t\s+st_col_launch\s*\(')
+    assert 'hipLaunchKernelGGL(kernel, dim3((unsigned)(groups * cg.ncg)), dim3((unsigned)cg.threads), cg.lds, st, args...);' in launch
     geom = _function_body(_read('adm_ms_col.h'), r'inline\s+StColGeom\s+st_col_geom\s*\(\s*int\s+Py\s*,\s*int\s+Px\s*\)')
     for line in ('const int cw = st_cw(Py);', 'c.cw = cw; c.ncg = (Px + cw - 1) / cw; c.threads = st_col_threads(Py);',
                  'c.lds = ((size_t)Py * cw + Py) * sizeof(float2);'):
@@ -178,16 +182,18 @@ def test_the_matrix_names_exactly_the_kernels_of_the_source():
             assert re.search(r'^def %s\(' % t, text, re.M), (k, module, t)
     # every instantiation of the templates is launched
     for name in ('st_col_conv_kernel', 'st_col_conv_sparse_kernel'):
-        assert {v for v in re.findall(r'hipLaunchKernelGGL\(%s<(\w+)>' % name, st)} == {'true', 'false'}, name
+        assert re.findall(r'st_col_launch\(conj \? %s<(\w+)> : %s<(\w+)>,' % (name, name), st) == [('true', 'false')], name
 
 
 def test_the_column_helpers_are_defined_once():
     """What the translation units of the path share is defined exactly once under adorym_amd/csrc, in adm_ms_col.h, and no copy
     under the prefix of a translation unit exists."""
     names = ('st_cw', 'st_col_threads', 'st_col_fft', 'st_col_ctx', 'st_col_load', 'st_col_store', 'st_freq_index', 'st_freq',
-             'st_col_geom', 'st_col_raise_lds', 'st_block_sum_f64')
+             'st_col_geom', 'st_col_raise_lds', 'st_block_sum_f64', 'st_col_begin', 'st_shift_phase', 'st_col_raise_lds_once',
+             'st_col_launch')
     srcs = {f: _read(f) for f in sorted(os.listdir(CSRC)) if f.endswith(('.hip', '.h'))}
-    path = ('adm_ms_col.h', 'adm_ms_streamed.hip', 'adm_ms_exitshift.hip', 'adm_ms_probeshift.hip')
+    path = ('adm_ms_col.h', 'adm_ms_streamed.hip', 'adm_ms_exitshift.hip', 'adm_ms_probeshift.hip', 'adm_ms_multidist.hip')
+    assert not any(re.search(r'\b(es|ps)_phase\b|\battr_set\b', srcs[f]) for f in path)      # (the copies that were)
     # a definition: the name, its parameter list, its body (a call is followed by ';', an operator or ')')
     definition = r'\b%s\s*\([^;{}()]*(?:\([^;{}()]*\)[^;{}()]*)*\)\s*\{'
     where = lambda text, files: [f for f in files for _ in re.finditer(text, srcs[f])]

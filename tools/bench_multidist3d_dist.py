@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """
-The cost of refining the distances of the detector fan-out (adm_plan_set_fanout_distances, adm_ms_distgrad.hip).  Not the headline
+The cost of refining the distances of the detector fan-out (adm_plan_set_fanout_distances; md_fanout_kernel<true> / md_fanin_kernel<true>
+of adm_ms_multidist.hip, st_fresnel_table_kernel and st_dd_reduce_kernel of adm_ms_streamed.hip).  Not the headline
 metric (bench.py is); prints one JSON object.
 
     python tools/bench_multidist3d_dist.py [--reps 15] [--inner 10]          # on a GPU box
