@@ -95,6 +95,11 @@ FIELDS = (
     (256, 16, 64),                        # the most distances: C4 in 8 rounds, 65 sums over 2 C5 blocks
 )
 VARIANT_FIELD = (128, 256, 4)
+# the value axis of ctf_sincos (sincos_fast, as holo_h): the rungs of tests/holo_value_matrix.py, whose top rung (PHASE_MAX) is the largest
+# of its ladder at which the float32 restatement keeps within a third of every bar -- here too (at 1e4 rad it does not: pred 2.1e-6,
+# grad 1.3e-4).  At the table's own distances xi reaches 103 rad.
+PHASE_FIELD = (32, 16, 2)
+PHASE_RUNGS = (100., 1000., 3000.)
 
 
 _GRAD = ('test_fields_gradient_launch', 'test_variants', 'test_clip')
@@ -164,14 +169,22 @@ def dists_for(nd):
     return 40. + 50. * np.arange(nd) / max(nd - 1, 1)                  # cm; (40, 65, 90) at nd = 3
 
 
-def inputs(ny, nx, nd, raw='intensity', clip=False, seed=None):
+def max_xi(ny, nx, dists):
+    """The largest argument ctf_sincos sees: PI lambda d_nm (u^2 + v^2) at Nyquist of both axes and the largest distance."""
+    return float(R.PI * (1240. / ENERGY_EV) * np.max(dists) * 1e7 * R.uv2((ny, nx), PSIZE_CM).max())
+
+
+def inputs(ny, nx, nd, raw='intensity', clip=False, seed=None, phase=None):
     """Host inputs of one case: obj [ny, nx, 2] float32 (beta non-zero: the model must ignore it), data [nd, ny, nx] float32 -- the
     fp64 model of a second object at lg_kappa = 1.5 -- dists [nd] float64, lg_kappa float32.  ``clip``: a tone of a quarter of the
     sampling frequency along both axes, un-windowed (one bin of the spectrum: A_d scales it by osc_d), strong enough to take a
-    quarter of the pixels of at least one distance below zero."""
+    quarter of the pixels of at least one distance below zero.  ``phase``: the distances scaled so that the largest argument of
+    ctf_sincos (``max_xi``) is so many radians."""
     s = 2600 + 31 * ny + 7 * nx + nd if seed is None else seed
     r = cases.rng(s)
     dists = dists_for(nd)
+    if phase is not None:
+        dists = dists * (phase / max_xi(ny, nx, dists))
     delta = delta_map(ny, nx, s)
     truth = delta_map(ny, nx, s + 50, scale=1.2)
     if clip:

@@ -111,6 +111,15 @@ def test_conditions_of_every_gpu_case(shape):
     print(CM.conditions(CM.case(*shape[:3], **kw)))
 
 
+@pytest.mark.parametrize('phase', CM.PHASE_RUNGS, ids=lambda v: '%g_rad' % v)
+def test_conditions_of_the_large_phase_cases(phase):
+    """The same conditions with the distances scaled until xi reaches the rung (MIN_I included: the object needs no less contrast)."""
+    c = CM.case(*CM.PHASE_FIELD, phase=phase)
+    assert abs(CM.max_xi(c['ny'], c['nx'], c['dists']) / phase - 1) < 1e-9 and CM.max_xi(16, 16, CM.dists_for(3)) < 104
+    assert CM.PHASE_FIELD in CM.FIELDS and CM.PHASE_RUNGS[0] <= 100 and CM.PHASE_RUNGS[-1] >= 3000
+    print(CM.conditions(c))
+
+
 def test_conditions_of_the_clipped_case():
     c = CM.case(*CM.VARIANT_FIELD, clip=True)
     print(CM.conditions(c))

@@ -251,6 +251,20 @@ def test_engine_matches_the_abi(ctx, A):
     same_bits(gk.get(), base['g_kappa'], 'engine grad_lg_kappa')
 
 
+# ------------------------------------------------------------------------------------------------------------ large arguments
+@pytest.mark.parametrize('phase', CM.PHASE_RUNGS, ids=lambda v: '%g_rad' % v)
+def test_large_phase(ctx, phase):
+    """ctf_sincos goes through sincos_fast, as the Fresnel factor of adm_holo.hip does: the distances of 32 x 16 x 2 scaled so that
+    xi reaches 100, 1000 and 3000 rad (the rungs of tests/holo_value_matrix.py; the table's own distances reach 103 rad), judged
+    by this module's rules whole and by bands."""
+    c = CM.case(*CM.PHASE_FIELD, phase=phase)
+    what = '%s at %g rad' % (ident(CM.PHASE_FIELD), phase)
+    res = launch(ctx, c)
+    check_whole(res, c, what)
+    check_bands(res, c, what)
+    assert not CM.bits(res['g_obj'][..., 1]).any()
+
+
 # ------------------------------------------------------------------------------------------------------------ the clip
 def test_clip(ctx):
     """A quarter of the pixels of at least one distance have I_d <= -0.05 (none lies between -0.05 and 0.05): the prediction is

@@ -337,11 +337,14 @@ def test_fused_adam_equals_the_separate_update_bitwise(ctx, shape, unknown_type,
 
 # ------------------------------------------------------------------------------------------------------------ shift stage
 def shift_stage(ctx, shape):
-    nd = HM.FIELDS[shape]
-    c = HM.case(*shape, nd, shifts=True)
+    shift_stage_of(ctx, HM.case(*shape, HM.FIELDS[shape], shifts=True), ident(shape) + ' shifts')
+
+
+def shift_stage_of(ctx, c, what):
+    """The shift stage of the case ``c`` (tests/test_gpu_holo_value_domain.py judges its cases with it too); returns the launch."""
+    nd = c['nd']
     o, s = c['o64'], c['o32']
     g = HM.geometry(c['ny'], c['nx'], nd)
-    what = ident(shape) + ' shifts'
     eng = engine(ctx, c)
     spec = eng.data_spectrum(ctx.array(c['data']))
     # D^ [d][kx][ky] against FFT2(|data|): itself a spectrum, so the blocks of SLF<N, 0> are judged directly
@@ -369,6 +372,7 @@ def shift_stage(ctx, shape):
     fwd = launch(ctx, c, eng=eng, shifted=True, spectrum=spec, want_grad=False, seed='sentinel', want=('probe', 'shifts'), want_pred=False)
     assert abs(fwd['loss'] / o['loss'] - 1) < BARS['loss']
     untouched(fwd, ('g_obj', 'g_probe', 'g_shifts'), what)
+    return res
 
 
 @pytest.mark.parametrize('shape', [f for f in HM.SHIFT_FIELDS if f not in HM.NEW_KERNELS], ids=ident)
