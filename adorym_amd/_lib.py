@@ -132,6 +132,8 @@ SIGNATURES = {
     'adm_rotation_csr_build': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
     'adm_project_z': (_I, [_VP, _VP, _I, _I, _VP]),
     'adm_project_z_adj': (_I, [_VP, _VP, _I, _I, _VP]),
+    'adm_rotate_project_fwd': (_I, [_VP, _VP, _VP, _VP, _I, _I]),
+    'adm_rotate_project_adj': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I]),
     'adm_multislice_fwd_adj': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _SZ]),
     'adm_plan_set_transmission_cache': (_I, [_VP, _I]),
     'adm_transmission_refresh': (_I, [_VP, _VP, _I, _I]),

@@ -3,6 +3,7 @@
 #include <hip/hip_fp16.h>
 #include "adm_host.h"
 #include "adm_ms_math.h"
+#include "adm_rot_bilin.h"
 
 namespace adm {
 // --------------------------------------------------------------------------------------------
@@ -13,46 +14,6 @@ namespace adm {
 // thread.  A 16x16 (x', z') patch per block keeps the source footprint compact for any angle;
 // writes are 128-B row segments of the slice-major [Z][Yp][Xp][2] layout.
 // --------------------------------------------------------------------------------------------
-struct RotGeom {
-    int Y, X, Z, Yp, Xp, pad_y0, pad_x0;
-};
-
-struct Bilin {
-    int i00, i01, i10, i11;   // float2 offsets inside one y plane of obj ([X][Z])
-    float w00, w01, w10, w11;
-};
-
-__device__ __forceinline__ Bilin make_bilin(const uint16_t* coords, int xr, int zr, int X, int Z) {
-#pragma clang fp contract(off)      // torch / NumPy evaluate this pipeline without fused multiply-adds: match them bit for bit
-    Bilin b;
-    if (coords == nullptr) {
-        b.i00 = b.i01 = b.i10 = b.i11 = xr * Z + zr;
-        b.w00 = 1.f; b.w01 = b.w10 = b.w11 = 0.f;
-        return b;
-    }
-    const __half* ch = reinterpret_cast<const __half*>(coords) + 2 * ((size_t)xr * Z + zr);
-    const double x_old = (double)__half2float(ch[0]);
-    const double z_old = (double)__half2float(ch[1]);
-    // wrappers.py:1137: grid = -1 + 2*grid/arr_shape + 1/arr_shape on the flipped (z, x) pair, arr_shape = (X, Z)
-    const float gz = (float)(-1.0 + 2.0 * z_old / (double)X + 1.0 / (double)X);
-    const float gx = (float)(-1.0 + 2.0 * x_old / (double)Z + 1.0 / (double)Z);
-    float iz = ((gz + 1.f) * (float)Z - 1.f) / 2.f;
-    float ix = ((gx + 1.f) * (float)X - 1.f) / 2.f;
-    iz = fminf((float)(Z - 1), fmaxf(iz, 0.f));
-    ix = fminf((float)(X - 1), fmaxf(ix, 0.f));
-    const float fz = floorf(iz), fx = floorf(ix);
-    const float tz = iz - fz, tx = ix - fx;
-    const int z0 = (int)fz, x0 = (int)fx;
-    const bool vz = (z0 + 1 <= Z - 1), vx = (x0 + 1 <= X - 1);
-    const int z1 = vz ? z0 + 1 : z0, x1 = vx ? x0 + 1 : x0;
-    b.i00 = x0 * Z + z0; b.i01 = x0 * Z + z1; b.i10 = x1 * Z + z0; b.i11 = x1 * Z + z1;
-    b.w00 = (1.f - tx) * (1.f - tz);
-    b.w01 = vz ? (1.f - tx) * tz : 0.f;
-    b.w10 = vx ? tx * (1.f - tz) : 0.f;
-    b.w11 = (vx && vz) ? tx * tz : 0.f;
-    return b;
-}
-
 // trans != nullptr: the slice transmission of every gathered voxel is stored beside it (same layout), so that the
 // multislice kernel multiplies with a loaded number instead of evaluating exp / sincos per covering position and sweep.
 __global__ __launch_bounds__(256) void rotate_fwd_kernel(const float2* __restrict__ obj, const uint16_t* __restrict__ coords,

@@ -721,7 +721,10 @@ class MultiDistModel(PtychographyModel):
     ``common_vars_dict['forward_algorithm'] == 'ctf'`` (:1011-1014, modulate_and_get_ctf): the contrast-transfer-function model of
     a weak, homogeneous object, I_d = 1 + Re IFFT2(2 (sin xi_d + cos xi_d / kappa) FFT2(delta)) with kappa = 10^ctf_lg_kappa[0].
     ``common_vars_dict['ctf_engine']`` is an adorym_amd.CTFEngine; gradients w.r.t. obj (beta's is exactly zero) and ctf_lg_kappa
-    come from adm_ctf_fwd_adj.  Neither the probe nor beta enters the model; one undivided field of view only.
+    come from adm_ctf_fwd_adj.  Neither the probe nor beta enters the model; one undivided field of view only.  A 3-D object under
+    this model (``two_d_mode=False``: :905-914 rotates it, propagate.py:467-476 sums it along the beam) is served when, and only
+    when, ``common_vars_dict['ctf_projector']`` is an adorym_amd.RotatedProjector: the angle's projection (adm_rotate_project_fwd) is
+    the engine's one slice and its gradient is back-projected into grad_obj (adm_rotate_project_adj); no rotated-frame buffer.
 
     A 3-D object (``two_d_mode=False``: holotomography, :905-914, 971-1019), one undivided field of view without a safe zone,
     ``forward_algorithm='fresnel'``: ``common_vars_dict['engine']`` is a MultisliceEngine built with ``detector_fanout=True`` for
@@ -749,6 +752,11 @@ class MultiDistModel(PtychographyModel):
         self.holo = None if (self.is_ctf or not common_vars_dict) else common_vars_dict['holo_engine']
         if self.is_ctf and self.ctf is None:
             raise ValueError("MultiDistModel with forward_algorithm='ctf' needs common_vars_dict['ctf_engine'] (an adorym_amd.CTFEngine)")
+        # ... of a 3-D object when the caller brought the projector that rotates and sums it (what the caller brought decides)
+        self.ctf_projector = common_vars_dict.get('ctf_projector') if self.is_ctf else None
+        self.ctf_3d = self.ctf_projector is not None
+        if self.ctf_3d and self.engine is None:
+            self.engine = self.ctf_projector          # (its plan carries the object geometry for the regulariser kernels)
         self._data_key = None
         self._data_dev = None
         self._small = {}
@@ -858,7 +866,7 @@ class MultiDistModel(PtychographyModel):
             what = "unknown_type='real_imag'"
         elif int(cv.get('n_probe_modes') or 1) != 1:
             what = 'n_probe_modes != 1'
-        elif not cv.get('two_d_mode'):
+        elif not cv.get('two_d_mode') and not self.ctf_3d:
             what = 'two_d_mode=False'
         elif self.tile_engine is not None or safe_zone_width not in (0, None) or int(cv.get('safe_zone_width') or 0) > 0:
             what = 'data divided into sub-tiles or safe_zone_width > 0'
@@ -871,14 +879,43 @@ class MultiDistModel(PtychographyModel):
             raise NotImplementedError("forward_algorithm='ctf' with %s is outside the accelerated path" % what)
         if ctf_lg_kappa is None:
             raise ValueError("forward_algorithm='ctf' needs ctf_lg_kappa")
+        if not cv.get('two_d_mode'):
+            # a 3-D object: rotated inside the loop by the projector, on one rank, on a field the CTF engine takes
+            sides = (self.ctf.ny, self.ctf.nx)
+            if cv.get('rotate_out_of_loop'):
+                what = 'two_d_mode=False and rotate_out_of_loop'
+            elif int(cv.get('n_ranks') or 1) > 1:
+                what = 'two_d_mode=False and more than one rank'
+            elif any(n < 16 or n > 2048 or n & (n - 1) for n in sides) or tuple(self.ctf_projector.obj_size[:2]) != sides:
+                what = 'two_d_mode=False and a field of %d x %d on a %d x %d x %d object (sides: powers of two in [16, 2048])' % (
+                    sides + tuple(self.ctf_projector.obj_size))
+            if what is not None:
+                raise NotImplementedError("forward_algorithm='ctf' with %s is outside the accelerated path" % what)
 
     def _run_ctf(self, obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad, grad_obj=None, grad_lg_kappa=None, want_pred=False,
                  overwrite=False):
         """One launch group of adm_ctf_fwd_adj.  The distances are not refined under this model: they go in as host doubles."""
         nd = self.ctf.n_dists
         dists = free_prop_cm.get() if isinstance(free_prop_cm, DeviceArray) else free_prop_cm
+        dists = np.asarray(dists, dtype=np.float64).reshape(nd)
         lgk = self._dev('ctf_lg_kappa', ctf_lg_kappa, (1,))
-        self.ctf.forward_adjoint(obj, np.asarray(dists, dtype=np.float64).reshape(nd), lgk, self._data(this_i_theta), want_grad=want_grad,
+        if self.ctf_3d and not self.common_vars.get('two_d_mode'):
+            # forward_model.py:905-914 + propagate.py:467-476: the rotated object summed along the beam is the model's one slice.
+            # The launch group overwrites the slice's gradient (and kappa's: one launch per evaluation), the back-projection adds it
+            # to grad_obj, which is zero-filled first where it holds garbage (``overwrite``).
+            rp = self.ctf_projector
+            table = self.common_vars['rotation_tables'](int(this_i_theta))
+            proj = rp.project(obj, table)
+            if want_grad and getattr(self, '_gproj', None) is None:
+                self._gproj = self.device.empty(tuple(proj.shape))
+            self.ctf.forward_adjoint(proj, dists, lgk, self._data(this_i_theta), want_grad=want_grad, grad_obj=self._gproj if want_grad else None,
+                                     grad_lg_kappa=grad_lg_kappa, want_pred=want_pred, overwrite=True)
+            if want_grad:
+                if overwrite:
+                    grad_obj.zero_()
+                rp.backproject(self._gproj, table, grad_obj)
+            return
+        self.ctf.forward_adjoint(obj, dists, lgk, self._data(this_i_theta), want_grad=want_grad,
                                  grad_obj=grad_obj, grad_lg_kappa=grad_lg_kappa, want_pred=want_pred, overwrite=overwrite)
 
     # ------------------------------------------------------------------ sub-tiles + safe zone (forward_model.py:884-1034)

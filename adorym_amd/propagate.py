@@ -849,7 +849,11 @@ class ProjectionEngine(object):
     spends a 2-D transform on that pixel; with and without the cache the kernel gives the same bits.
     """
 
-    def __init__(self, ctx, obj_size, probe_size, probe_pos, energy_ev, psize_cm, **kw):
+    def __init__(self, ctx, obj_size, probe_size, probe_pos, energy_ev, psize_cm, fused_rotation=False, **kw):
+        """``fused_rotation``: ``rotate`` and ``rotate_adjoint`` are one kernel each (adm_rotate_project_fwd / _adj) between the
+        object and the slab's one-slice frame; no volume engine is built then, so the two [Z] buffers do not exist (``volume``,
+        ``obj_rot`` and ``grad_rot`` are None), and ``rotate_adjoint`` takes a RotationTable or None."""
+        self.fused_rotation = bool(fused_rotation)
         for name, why in (('slice_pos_cm', 'sparse multislice'), ('exit_shift', 'per-angle projection alignment')):
             if kw.get(name) is not None and kw.get(name) is not False:
                 raise NotImplementedError('ProjectionEngine: %s (%s) with the projection approximation is not implemented' % (name, why))
@@ -865,6 +869,15 @@ class ProjectionEngine(object):
         self.obj_size = tuple(int(v) for v in obj_size)
         Y, X, _ = self.obj_size
         self.slab = MultisliceEngine(ctx, (Y, X, 1), probe_size, probe_pos, energy_ev, psize_cm, transmission_cache=False, **kw)
+        if self.fused_rotation:
+            # no volume engine and none of its [Z] buffers: a bare plan of the volume on the slab's pads is all the two kernels,
+            # the rotation tables and the regularisers ask for
+            p = tuple(min(8, int(v)) for v in probe_size)
+            self.volume = self.obj_rot = self.grad_rot = None
+            self.plan = Plan(ctx, self.obj_size, p, self.slab.plan.pads, 1.0, np.ones(p, complex))
+            if self.plan.rot_shape[1:] != self.slab.plan.rot_shape[1:]:
+                raise RuntimeError('ProjectionEngine: the padded frames of the two plans differ')
+            return
         self.volume = MultisliceEngine(ctx, self.obj_size, probe_size, probe_pos, energy_ev, psize_cm, free_prop_cm=0, streamed='auto',
                                        scale_ri_by_k=kw.get('scale_ri_by_k', True), transmission_cache=False)
         if self.volume.plan.rot_shape[1:] != self.slab.plan.rot_shape[1:] or self.volume.plan.pads != self.slab.plan.pads:
@@ -881,12 +894,22 @@ class ProjectionEngine(object):
     def rotate(self, obj, coords, y_range=None):
         """Rotate the rows, then sum them along the beam into the slab's rotated object."""
         lo, hi = y_range if y_range is not None else (0, self.obj_size[0])
+        if self.fused_rotation:
+            check(self.ctx.lib.adm_rotate_project_fwd(self.plan.handle, obj.ptr, coords.ptr if coords is not None else None,
+                                                      self.slab.obj_rot.ptr, lo, hi))
+            return
         self.volume.rotate(obj, coords, (lo, hi))
         check(self.ctx.lib.adm_project_z(self.plan.handle, self.obj_rot.ptr, lo, hi, self.slab.obj_rot.ptr))
 
     def rotate_adjoint(self, grad_obj, coords, y_range=None):
         """grad_obj += R^T (the slab's overlap-added gradient, copied to every slice)."""
         lo, hi = y_range if y_range is not None else (0, self.obj_size[0])
+        if self.fused_rotation:
+            if coords is not None and not isinstance(coords, RotationTable):
+                raise NotImplementedError('ProjectionEngine(fused_rotation=True): the back-rotation reads the CSR tables of a RotationTable; '
+                                          'a bare coordinate array (the atomic scatter) is not implemented')
+            rotate_project_adjoint(self.ctx, self.plan, self.slab.grad_rot, coords, grad_obj, lo, hi)
+            return
         check(self.ctx.lib.adm_project_z_adj(self.plan.handle, self.slab.grad_rot.ptr, lo, hi, self.grad_rot.ptr))
         self.volume.rotate_adjoint(grad_obj, coords, (lo, hi))
 
@@ -895,7 +918,7 @@ class ProjectionEngine(object):
 
     def close(self):
         self.slab.plan.close()
-        self.volume.plan.close()
+        self.plan.close()
 
     def loss_and_grad(self, obj, grad_obj, coords, probe, pos_batch, target, grad_probe=None, footprint=True):
         """One minibatch: grad_obj += d loss / d obj; returns the (host) loss."""
@@ -905,6 +928,55 @@ class ProjectionEngine(object):
         self.slab.multislice(probe, grad_probe=grad_probe)
         self.rotate_adjoint(grad_obj, coords, yr)
         return self.slab.loss()
+
+
+def rotate_project_adjoint(ctx, plan, grad_proj, table, grad_obj, lo, hi):
+    """grad_obj += (sum along the beam . rotation)^T grad_proj over planes [lo, hi): adm_rotate_project_adj with the CSR tables of
+    ``table`` (a RotationTable, built for ``plan``'s frame) or, with None, no rotation."""
+    if table is None:
+        p = s = w = None
+        lanes_x = 0
+    else:
+        p, s, _, w, _ = [a.ptr for a in table.csr(plan)]
+        lanes_x = int(table.lanes_along_x)
+    check(ctx.lib.adm_rotate_project_adj(plan.handle, grad_proj.ptr, p, s, w, grad_obj.ptr, lo, hi, lanes_x))
+
+
+class RotatedProjector(object):
+    """
+    The rotated object summed along the beam, and the transpose, with no rotated-frame buffer (adorym/forward_model.py:905-914 +
+    w.sum(grid_batch, axis=-2), adorym/propagate.py:467-476: all the 3-D CTF model does to the object per angle):
+
+      obj [Y,X,Z,2] --adm_rotate_project_fwd--> [Y,X,2]            [Y,X,2] --adm_rotate_project_adj--> grad_obj [Y,X,Z,2] (+=)
+
+    It owns a bare plan of the geometry with zero pads (the whole field as one position), which rotation tables and regularisers
+    may ask for (``plan``), and one [Y,X,2] image that ``project`` returns and the next call overwrites.
+    """
+
+    def __init__(self, ctx, obj_size):
+        self.ctx = ctx
+        self.obj_size = tuple(int(v) for v in obj_size)
+        Y, X, _ = self.obj_size
+        p = (min(Y, 8), min(X, 8))          # (the plan launches no multislice kernel: any probe the field holds will do)
+        self.plan = Plan(ctx, self.obj_size, p, ((0, 0), (0, 0)), 1.0, np.ones(p, complex))
+        self._proj = DeviceArray(ctx, (Y, X, 2), np.float32)
+
+    def cacheless_plan(self):
+        return self.plan
+
+    def project(self, obj, table, y_range=None):
+        """obj: DeviceArray [Y,X,Z,2]; table: a RotationTable or None (no rotation) -> DeviceArray [Y,X,2] (this object's own)."""
+        lo, hi = y_range if y_range is not None else (0, self.obj_size[0])
+        check(self.ctx.lib.adm_rotate_project_fwd(self.plan.handle, obj.ptr, table.ptr if table is not None else None, self._proj.ptr, lo, hi))
+        return self._proj
+
+    def backproject(self, grad_proj, table, grad_obj, y_range=None):
+        """grad_obj [Y,X,Z,2] += the transpose of ``project`` applied to grad_proj [Y,X,2]."""
+        lo, hi = y_range if y_range is not None else (0, self.obj_size[0])
+        rotate_project_adjoint(self.ctx, self.plan, grad_proj, table, grad_obj, lo, hi)
+
+    def close(self):
+        self.plan.close()
 
 
 class AngleBatch(object):

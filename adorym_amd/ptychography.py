@@ -326,6 +326,8 @@ class _Run(object):
         self.fanout_free_prop = bool(kwargs.pop('fanout_free_prop', False))
         # optimize_prj_affine for the same data: the holograms registered by kernels of their own (HologramRegistration), on request
         self.fanout_prj_affine = bool(kwargs.pop('fanout_prj_affine', False))
+        # forward_algorithm='ctf' for multi-distance data of a 3-D object (CTF holotomography: RotatedProjector + CTFEngine), on request
+        self.ctf_tomography = bool(kwargs.pop('ctf_tomography', False))
         self.ops = kwargs.pop('ops', None)
         kwargs.pop('probe_size', None)
         self.kwargs = kwargs
@@ -447,7 +449,7 @@ class _Run(object):
                               'shift of the exit wave, so the gradient is zero and the offsets cannot move.', UserWarning)
         self.is_ctf = self.forward_algorithm == 'ctf'
         _not_implemented(self.is_ctf and not self.is_multi_dist, "forward_algorithm='ctf'")
-        self.holo_tiled = self.holo_3d = False
+        self.holo_tiled = self.holo_3d = self.ctf_3d = False
         if self.is_multi_dist:
             # config 5 is one object slice and one undivided field of view (n_blocks == 1) without a safe zone
             free_prop_cm = self.free_prop_cm = np.asarray(self.free_prop_cm, dtype=float).reshape(-1)
@@ -455,10 +457,19 @@ class _Run(object):
             safe_zone_width = self.safe_zone_width = int(self.safe_zone_width or 0)
             if prj.shape[1] != n_dists * len(probe_pos):
                 raise ValueError('multi-distance data: prj.shape[1] = %d is not n_dists x n_blocks = %d x %d' % (prj.shape[1], n_dists, len(probe_pos)))
-            _not_implemented(not self.two_d_mode and self.forward_algorithm == 'ctf', "forward_algorithm='ctf' with two_d_mode=False")
+            # (ctf_tomography=True: the rotated object summed along the beam is the CTF model's one slice, RotatedProjector + CTFEngine)
+            _not_implemented(not self.two_d_mode and self.is_ctf and not self.ctf_tomography, "forward_algorithm='ctf' with two_d_mode=False")
+            self.ctf_3d = self.is_ctf and not self.two_d_mode
+            if self.ctf_3d:
+                what = "forward_algorithm='ctf' with two_d_mode=False and %s"
+                _not_implemented(bool(self.rotate_out_of_loop), what % 'rotate_out_of_loop')
+                _not_implemented(self.n_ranks > 1, what % 'more than one rank')
+                sides = [int(v) for v in obj_size[:2]]
+                _not_implemented(any(n < 16 or n > 2048 or n & (n - 1) for n in sides),
+                                 what % ('a field of %d x %d (sides: powers of two in [16, 2048])' % tuple(sides)))
             # a 3-D object (holotomography, adorym/forward_model.py:905-914, 971-1019): rotate, ONE slice sweep, the exit wave to
             # every distance (MultisliceEngine(detector_fanout=True)); one undivided field of view, fixed distances, no registration
-            self.holo_3d = not self.two_d_mode
+            self.holo_3d = not self.two_d_mode and not self.is_ctf
             if self.holo_3d:
                 what = 'multi-distance holography of a 3-D object with %s'
                 _not_implemented(len(probe_pos) > 1 or safe_zone_width > 0, what % 'data divided into sub-tiles or safe_zone_width > 0')
@@ -531,7 +542,7 @@ class _Run(object):
         self.h = get_kernel(voxel_nm[-1] * self.binning, self.lmbda_nm, voxel_nm, probe_size, fresnel_approx=self.fresnel_approx,
                             sign_convention=self.sign_convention) if (self.holo_3d or not self.is_multi_dist) else None
         self.probe_pos_int = np.round(self.probe_pos).astype(int)
-        self.holo_engine = self.tile_engine = self.ctf_engine = self.registration = None
+        self.holo_engine = self.tile_engine = self.ctf_engine = self.registration = self.ctf_projector = None
         common = dict(sign_convention=self.sign_convention, scale_ri_by_k=self.scale_ri_by_k, unknown_type=self.unknown_type)
         if self.holo_tiled:
             # one engine for all distances: tile = sub-hologram + 2 safe zones at (position - safe zone), every tile listed n_dists
@@ -563,9 +574,15 @@ class _Run(object):
                 from .holography import HolographyEngine
                 self.holo_engine = HolographyEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm,
                                                     raw_data_type=self.raw_data_type, **common)
-            # a minimal multislice plan is still created: it carries the object geometry for the regulariser kernels
-            self.engine = MultisliceEngine(ctx, obj_size, (8, 8), np.zeros((1, 2), int), self.energy_ev, self.psize_cm, free_prop_cm=0,
-                                           max_batch=1, unknown_type=self.unknown_type)
+            if self.ctf_3d:
+                # the projector rotates and sums the object for the CTF engine and takes the gradient back; its bare plan carries
+                # the object geometry for the regulariser kernels and the rotation tables.  No multislice engine, no h.
+                from .propagate import RotatedProjector
+                self.engine = self.ctf_projector = RotatedProjector(ctx, obj_size)
+            else:
+                # a minimal multislice plan is still created: it carries the object geometry for the regulariser kernels
+                self.engine = MultisliceEngine(ctx, obj_size, (8, 8), np.zeros((1, 2), int), self.energy_ev, self.psize_cm, free_prop_cm=0,
+                                               max_batch=1, unknown_type=self.unknown_type)
         else:
             # the projection approximation sums the object along the beam and runs the one-slice problem; an object that HAS one
             # slice is that problem already (the sum of one slice is the slice) and takes the ordinary engine
@@ -698,6 +715,8 @@ class _Run(object):
                            optimize_tilt=False, output_folder=self.output_folder, debug=self.debug)
         if self.registration is not None:
             common_vars['hologram_registration'] = self.registration
+        if self.ctf_projector is not None:
+            common_vars.update(ctf_projector=self.ctf_projector, n_ranks=self.n_ranks)
         fm_args = dict(loss_function_type=self.loss_function_type, distribution_mode=self.distribution_mode, device=ctx,
                        common_vars_dict=common_vars, raw_data_type=self.raw_data_type, run_bfloat16=self.run_bfloat16,
                        run_float64=self.run_float64)
@@ -853,6 +872,11 @@ class _Run(object):
                 if mom_ is not None and 'free_prop_cm_moments' in restored:
                     for m_, h_ in zip(mom_, restored['free_prop_cm_moments']):
                         m_.set(np.asarray(h_, dtype=np.float32).reshape(m_.shape))
+            if self.ctf_3d:
+                mom_ = self._small_moments('ctf_lg_kappa')
+                if mom_ is not None and 'ctf_lg_kappa_moments' in restored:
+                    for m_, h_ in zip(mom_, restored['ctf_lg_kappa_moments']):
+                        m_.set(np.asarray(h_, dtype=np.float32).reshape(m_.shape))
             if self.register_3d:
                 mom_ = self._small_moments('prj_affine_ls')
                 if mom_ is not None and 'prj_affine_ls_moments' in restored:
@@ -891,6 +915,10 @@ class _Run(object):
             mom_ = self._small_moments('free_prop_cm')
             if mom_ is not None:
                 out_['free_prop_cm_moments'] = [m_.get() for m_ in mom_]
+        if self.ctf_3d:
+            mom_ = self._small_moments('ctf_lg_kappa')        # (likewise, for the 3-D CTF run)
+            if mom_ is not None:
+                out_['ctf_lg_kappa_moments'] = [m_.get() for m_ in mom_]
         if self.register_3d:
             mom_ = self._small_moments('prj_affine_ls')       # (likewise)
             if mom_ is not None:
@@ -1365,4 +1393,6 @@ class _Run(object):
                                          else self.ctf_lg_kappa_history[0].get()[:self.ctf_lg_kappa_history[1]]),
                 'losses': self.loss_history, 'output_folder': self.output_folder,
                 # which multislice path served the run
-                'engine_streamed': bool(self.engine.streamed), 'engine_probe_shift': bool(self.engine.probe_shift)}
+                # (a 3-D CTF run has no multislice engine: its projector answers False to both)
+                'engine_streamed': bool(getattr(self.engine, 'streamed', False)),
+                'engine_probe_shift': bool(getattr(self.engine, 'probe_shift', False))}

@@ -306,6 +306,26 @@ int adm_rotation_csr_build(adm_plan* plan, const uint16_t* coords, int32_t* csr_
  * A plan that caches transmissions does not learn of a proj written here: refresh it (adm_transmission_refresh) or leave its cache off. */
 int adm_project_z(adm_plan* plan, const float* obj_rot, int y_lo, int y_hi, float* proj);
 int adm_project_z_adj(adm_plan* plan, const float* grad_proj, int y_lo, int y_hi, float* grad_rot);
+/* The rotation and the sum in one pass, and the transpose of the pair, with no rotated-frame buffer between them (the weak-object
+ * CTF model of a 3-D object, adorym/forward_model.py:905-914 + adorym/propagate.py:467-476, is this sum and nothing else per angle).
+ * adm_rotate_project_fwd: obj device [Y][X][Z][2], coords the fp16 table [X*Z][2] of adm_rotate_fwd (NULL: no rotation), proj device
+ *   [1][Yp][Xp][2] as above.  For the object rows y_lo <= y < y_hi the interior column x' of both channels is written with
+ *   round_fp32(sum over z' of r(y, x', z')), r the border-clamped bilinear sample adm_rotate_fwd stores (same float32 weights and
+ *   indices); the sum is accumulated in double in an order fixed by (X, Z) alone -- not by the range, not by where the lanes of the
+ *   gather run (chosen per launch from the table: along z' when |cos| >= |sin|, else along x') -- with one rounding and no atomics:
+ *   the same call gives the same bits.  The x pads of those rows are written with +0; other rows and the y pads are not touched.
+ * adm_rotate_project_adj: the transpose.  grad_obj[y][t] += sum over the CSR row of t = x * Z + z of csr_w[j] * grad_proj[y][x'_j],
+ *   x'_j = csr_src[j] mod (Yp * Xp) - pad_x0, the tables those of adm_rotation_csr_build / build_rotation_adjoint_csr for this plan;
+ *   the entries in table order from zero, in float32, then one addition to grad_obj: what adm_project_z_adj followed by
+ *   adm_rotate_adj_csr computes.  The three tables NULL: no rotation, the row is added to every z.  Only the interior columns of
+ *   the rows [y_lo, y_hi) of grad_proj are read (each row is staged in LDS: obj_x <= 2048, else ADM_ERR_UNSUPPORTED); planes of
+ *   grad_obj outside the range keep their bits.  Deterministic.  lanes_along_x is taken for symmetry with adm_rotate_adj_csr and
+ *   changes neither the access pattern nor the bits: the gather reads LDS, and the lanes run along z, the fastest axis of grad_obj.
+ * Both are asynchronous on the context's stream and use no scratch; a null pointer (the tables excepted, all three or none) or a
+ * range outside 0 <= y_lo <= y_hi <= obj_y is ADM_ERR_INVALID. */
+int adm_rotate_project_fwd(adm_plan* plan, const float* obj, const uint16_t* coords, float* proj, int y_lo, int y_hi);
+int adm_rotate_project_adj(adm_plan* plan, const float* grad_proj, const int32_t* csr_ptr, const int32_t* csr_src, const float* csr_w,
+                           float* grad_obj, int y_lo, int y_hi, int lanes_along_x);
 
 /* ---- R3,R5-R8,R10  multislice forward + loss + adjoint ------------------------------
  * Replaces, for one minibatch of `batch` probe positions of one rotation angle:
