@@ -9,7 +9,7 @@ from .constants import PI  # noqa: F401
 from . import global_settings  # noqa: F401
 from .device import Context, DeviceArray, Plan, Event, PinnedArray, UploadRing  # noqa: F401
 from .propagate import MultisliceEngine, ProjectionEngine, RotatedProjector, RotationTable, AngleBatch, get_kernel, gen_freq_mesh  # noqa: F401
-from .holography import HolographyEngine, CTFEngine, HologramRegistration  # noqa: F401
+from .holography import HolographyEngine, CTFEngine, CTFInversion, HologramRegistration  # noqa: F401
 
 __version__ = '0.1.0'
 
@@ -23,3 +23,4 @@ from .regularizers import (Regularizer, L1Regularizer, TVRegularizer, Reweighted
                            CorrRegularizer, GradCorrRegularizer)
 from .array_ops import ObjectFunction, Gradient, Mask  # noqa: F401,E402
 from .ptychography import reconstruct_ptychography  # noqa: F401,E402
+from . import conventional  # noqa: F401,E402

@@ -36,6 +36,11 @@ class CtfDesc(C.Structure):
                 ('energy_ev', C.c_double), ('psize_cm', C.c_double)]
 
 
+class CtfInvDesc(C.Structure):
+    _fields_ = [('ny', C.c_int32), ('nx', C.c_int32), ('n_dists', C.c_int32), ('max_batch', C.c_int32),
+                ('energy_ev', C.c_double), ('psize_cm', C.c_double)]
+
+
 class SmallParam(C.Structure):
     _fields_ = [('x', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('n', C.c_uint64), ('step_size', C.c_double),
                 ('center_cols', C.c_int32), ('zero_grad', C.c_int32), ('pin', C.c_void_p), ('pin_n', C.c_uint64)]
@@ -175,6 +180,9 @@ SIGNATURES = {
     'adm_ctf_create': (_I, [_VP, C.POINTER(CtfDesc), C.POINTER(_VP)]),
     'adm_ctf_destroy': (_I, [_VP]),
     'adm_ctf_fwd_adj': (_I, [_VP, _VP, C.POINTER(_D), _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    'adm_ctfinv_create': (_I, [_VP, C.POINTER(CtfInvDesc), _VP, C.POINTER(_VP)]),
+    'adm_ctfinv_destroy': (_I, [_VP]),
+    'adm_ctfinv_run': (_I, [_VP, _VP, _I, C.POINTER(_D), _VP, _VP, _I]),
     'adm_register_create': (_I, [_VP, _I, _I, _I, _I, C.POINTER(_VP)]),
     'adm_register_destroy': (_I, [_VP]),
     'adm_register_targets': (_I, [_VP, _VP, _VP, _VP]),

@@ -191,6 +191,94 @@ class CTFEngine(object):
         return self._pred.get()
 
 
+class CTFInversion(object):
+    """The direct inversion of the CTF model (update_using_external_algorithm='ctf'; adorym/conventional.py:112-152,
+    multidistance_ctf_wrapped): the phase map of an angle from its multi-distance holograms in closed form,
+        phase = Re IFFT2( sum_d w_d FFT2(I_d - 1) / (sum_d 2 w_d^2 + alpha) ),   w_d = sin xi_d + cos xi_d / kappa.
+    See include/adm.h (adm_ctfinv_*) and csrc/adm_ctf_invert.hip.  ``alpha``: None (the reference's 1e-10), a scalar, or an
+    [ny, nx] array in the order of np.fft.fftfreq (the frequency-dependent regulariser of adorym/util.py:1601-1626, which the
+    caller builds); every entry finite and > 0.  ``max_batch``: the angles one launch group takes."""
+
+    def __init__(self, ctx, field_size, n_dists, energy_ev, psize_cm, max_batch=1, alpha=None):
+        from ._lib import CtfInvDesc
+        self.ctx = ctx
+        self.ny, self.nx = int(field_size[0]), int(field_size[1])
+        self.n_dists, self.max_batch = int(n_dists), int(max_batch)
+        desc = CtfInvDesc(ny=self.ny, nx=self.nx, n_dists=self.n_dists, max_batch=self.max_batch, energy_ev=float(energy_ev),
+                          psize_cm=float(psize_cm))
+        table = None
+        if alpha is not None:
+            a = np.asarray(alpha, dtype=np.float32)
+            if a.ndim == 0:
+                a = np.full((self.ny, self.nx), a, dtype=np.float32)
+            if a.shape != (self.ny, self.nx):
+                raise ValueError('CTFInversion: alpha must be a scalar or %r, got %r' % ([self.ny, self.nx], list(a.shape)))
+            table = np.ascontiguousarray(a)
+        h = C.c_void_p()
+        check(ctx.lib.adm_ctfinv_create(ctx.handle, C.byref(desc), table.ctypes.data if table is not None else None, C.byref(h)))
+        self.handle = h
+        self._registration = None
+        self._out = None
+
+    def __del__(self):
+        try:
+            if getattr(self, 'handle', None) and self.ctx.handle:
+                self.ctx.lib.adm_ctfinv_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def _checked(self, a, shapes, name):
+        if not isinstance(a, DeviceArray):
+            raise TypeError('CTFInversion: %s must be a DeviceArray' % name)
+        if a.dtype != np.float32 or tuple(a.shape) not in shapes:
+            raise ValueError('CTFInversion: %s must be float32 %s, got %s %r'
+                             % (name, ' or '.join(repr(list(s)) for s in shapes), np.dtype(a.dtype).name, list(a.shape)))
+        return a
+
+    def retrieve(self, data, dists_cm, lg_kappa, out=None, into_object=False, affine=None):
+        """data [B, D, ny, nx] or [D, ny, nx] raw holograms (used as given: I - 1) and lg_kappa [1] are DeviceArrays; dists_cm is a
+        HOST sequence of D distances in cm.  Returns the phase maps [B, ny, nx]: ``out`` when given, else the engine's own
+        DeviceArray, overwritten by the next call.  B may exceed max_batch: the angles go in rounds of max_batch.
+        ``into_object=True`` (B = 1): ``out`` is an object [ny, nx, (1,) 2] whose delta channel is overwritten; the beta channel is
+        not touched.  ``affine`` [D, 2, 3] (DeviceArray, B = 1): the holograms first pass through a HologramRegistration built with
+        raw_data_type='magnitude' -- bilinear samples of |data| replace the reference's signed sample (holograms are positive).
+        Everything is queued on the stream the context is enqueuing on."""
+        ny, nx, D = self.ny, self.nx, self.n_dists
+        d = np.ascontiguousarray(np.asarray(dists_cm, dtype=np.float64).reshape(-1))
+        if d.size != D:
+            raise ValueError('CTFInversion: %d distances given, %d expected' % (d.size, D))
+        B = int(data.shape[0]) if isinstance(data, DeviceArray) and len(data.shape) == 4 and data.shape[0] >= 1 else 1
+        self._checked(data, [(B, D, ny, nx), (D, ny, nx)], 'data')
+        self._checked(lg_kappa, [(1,)], 'lg_kappa')
+        if affine is not None:
+            if B != 1:
+                raise ValueError('CTFInversion: affine registration takes one angle (B = 1), got B = %d' % B)
+            self._checked(affine, [(D, 2, 3)], 'affine')
+            if self._registration is None:
+                self._registration = HologramRegistration(self.ctx, D, (ny, nx), raw_data_type='magnitude')
+            data = self._registration.targets(data.view(0, (D, ny, nx)), affine)
+        if into_object:
+            if B != 1:
+                raise ValueError('CTFInversion: into_object takes one angle (B = 1), got B = %d' % B)
+            if out is None:
+                raise ValueError('CTFInversion: into_object needs the object as out')
+            self._checked(out, [(ny, nx, 2), (ny, nx, 1, 2)], 'out')
+        elif out is None:
+            if self._out is None or self._out.shape[0] != B:
+                self._out = DeviceArray(self.ctx, (B, ny, nx), np.float32)
+            out = self._out
+        else:
+            self._checked(out, [(B, ny, nx)] + ([(ny, nx)] if B == 1 else []), 'out')
+        dp = d.ctypes.data_as(C.POINTER(C.c_double))
+        n = ny * nx
+        for b0 in range(0, B, self.max_batch):
+            nb = min(self.max_batch, B - b0)
+            check(self.ctx.lib.adm_ctfinv_run(self.handle, data.ptr + 4 * b0 * D * n, nb, dp, lg_kappa.ptr, out.ptr + 4 * b0 * n,
+                                              2 if into_object else 1))
+        return out
+
+
 class HologramRegistration(object):
     """The affine registration of measured holograms as kernels of its own (optimize_prj_affine, adorym/forward_model.py:1066-1072;
     w.affine_transform, wrappers.py:1159-1174) for forward models that are not HolographyEngine's: multi-distance holography of a

@@ -328,7 +328,10 @@ class _Run(object):
         self.fanout_prj_affine = bool(kwargs.pop('fanout_prj_affine', False))
         # forward_algorithm='ctf' for multi-distance data of a 3-D object (CTF holotomography: RotatedProjector + CTFEngine), on request
         self.ctf_tomography = bool(kwargs.pop('ctf_tomography', False))
-        self.ops = kwargs.pop('ops', None)
+        # update_using_external_algorithm='ctf': the delta channel overwritten by the direct CTF inversion in every minibatch
+        # (CTFInversion), on request
+        self.ctf_direct_update = bool(kwargs.pop('ctf_direct_update', False))
+        self.ops =kwargs.pop('ops', None)
         kwargs.pop('probe_size', None)
         self.kwargs = kwargs
         self.n_ranks, self.rank = self.comm.size, self.comm.rank
@@ -368,7 +371,15 @@ class _Run(object):
         _not_implemented(self.is_minus_logged, 'is_minus_logged')
         _not_implemented(not self.common_probe_pos, 'common_probe_pos=False')
         _not_implemented(not self.shared_probe_among_angles, 'shared_probe_among_angles=False')
-        _not_implemented(self.update_using_external_algorithm is not None, 'update_using_external_algorithm')
+        ext = self.update_using_external_algorithm
+        _not_implemented(ext is not None and not self.ctf_direct_update, 'update_using_external_algorithm')
+        # (ctf_direct_update=True: 'ctf' beside the CTF forward model of one slice; what needs the data's shape: read_data)
+        self.ctf_direct = ext is not None
+        if self.ctf_direct:
+            _not_implemented(ext != 'ctf', 'update_using_external_algorithm=%r' % (ext,))
+            what = "update_using_external_algorithm='ctf' with %s"
+            _not_implemented(self.ctf_tomography, what % 'ctf_tomography')
+            _not_implemented(self.forward_algorithm != 'ctf', what % ("forward_algorithm='%s'" % (self.forward_algorithm,)))
         _not_implemented(self.shrink_cycle is not None, 'shrink-wrap mask updates')
         _not_implemented(self.initial_tilt is not None, 'initial_tilt')
         _not_implemented(self.interpolation != 'bilinear', "interpolation='%s'" % self.interpolation)
@@ -450,6 +461,12 @@ class _Run(object):
         self.is_ctf = self.forward_algorithm == 'ctf'
         _not_implemented(self.is_ctf and not self.is_multi_dist, "forward_algorithm='ctf'")
         self.holo_tiled = self.holo_3d = self.ctf_3d = False
+        if self.ctf_direct:
+            what = "update_using_external_algorithm='ctf' with %s"
+            _not_implemented(not self.two_d_mode, what % 'two_d_mode=False')
+            _not_implemented(self.n_ranks > 1, what % 'more than one rank')
+            # (the reference masks the object after the inversion, ptychography.py:1210-1215; the fused update here masks before it)
+            _not_implemented(self.finite_support_mask_path is not None, what % 'a finite support mask')
         if self.is_multi_dist:
             # config 5 is one object slice and one undivided field of view (n_blocks == 1) without a safe zone
             free_prop_cm = self.free_prop_cm = np.asarray(self.free_prop_cm, dtype=float).reshape(-1)
@@ -570,6 +587,10 @@ class _Run(object):
             if self.is_ctf:
                 from .holography import CTFEngine
                 self.ctf_engine = CTFEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm, raw_data_type=self.raw_data_type)
+                if self.ctf_direct:
+                    from .holography import CTFInversion
+                    self.ctf_inversion = CTFInversion(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm)
+                    self.ctf_direct_data = None       # (the holograms of angle 0, raw, on the device from the first minibatch on)
             else:
                 from .holography import HolographyEngine
                 self.holo_engine = HolographyEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm,
@@ -962,7 +983,8 @@ class _Run(object):
         # adam_value in adm_optim.h -- and same step counter) unless the fused holography launch has updated it; these paths are
         # chains of 5-20 us kernels, where a launch saved is 5 % of a minibatch.
         self.obj_with_small = (self.optimize_object and plain_adam([self.opt]) is not None and self.n_ranks == 1 and self.flags == 0
-                               and self.mask is None and self.state.n <= (1 << 22) and not self.restricted_exchange)
+                               and self.mask is None and self.state.n <= (1 << 22) and not self.restricted_exchange
+                               and not self.ctf_direct)      # (the inversion sits between the object's step and kappa's)
         self.stage_next_targets = os.environ.get('ADM_STAGE_TARGETS', '1') == '1'
 
         self.i_epoch = self.starting_epoch
@@ -1015,6 +1037,8 @@ class _Run(object):
             return
         self.initialize_gradients = True
         obj_with_small = self._update_object(i_batch, holo_fused)
+        if self.ctf_direct:
+            self._ctf_direct_update()
         self._update_small_params(i_batch, obj_with_small, holo_fused)
 
         # ---- intermediate output (ptychography.py:1231-1246; util.py:1958-2028, optimizers.py:1111-1160) ----
@@ -1257,6 +1281,17 @@ class _Run(object):
             xkw = dict(touched=(self.touched_planes[0] * plane, self.touched_planes[1] * plane), reg_shard=_reg_shard)
         state.exchange_and_update(self.opt_kind, self.i_opt_batch, o, flags=self.flags, mask=mask, first=first, **xkw)
         return False
+
+    def _ctf_direct_update(self):
+        """update_using_external_algorithm='ctf' (ptychography.py:1135-1163, array_ops.py:274-286): behind the object's step and its
+        constraints the delta channel is overwritten with the direct CTF inversion of angle 0's holograms at the distances given and
+        the CURRENT lg_kappa on the device -- as it was before this minibatch's kappa step.  (The reference reads the function
+        argument ctf_lg_kappa, a float, with [0] there, and never the refined value.)  Beta is not touched."""
+        if self.ctf_direct_data is None:
+            self.ctf_direct_data = self.ctx.array(np.ascontiguousarray(np.asarray(self.prj[0]), dtype=np.float32), np.float32)
+        self.state.finish_update()
+        self.ctf_inversion.retrieve(self.ctf_direct_data, self.free_prop_cm, self.optimizable_params['ctf_lg_kappa'], out=self.obj.arr,
+                                    into_object=True)
 
     def _update_small_params(self, i_batch, obj_with_small, holo_fused):
         """The small parameters (optimizers.py:1022-1083): probe, sub-pixel positions, propagation distances, affine registration.

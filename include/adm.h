@@ -701,6 +701,36 @@ int adm_ctf_destroy(adm_ctf* h);
 int adm_ctf_fwd_adj(adm_ctf* h, const float* obj, const double* dists_cm, const float* lg_kappa, const float* data,
                     int want_grad, float* grad_obj, float* grad_lg_kappa, float* pred, float* loss_sum);
 
+/* ---- f1  the direct inversion of the CTF model (multi-distance phase retrieval in closed form) ---
+ * update_using_external_algorithm='ctf' (adorym/array_ops.py:274-286; conventional.multidistance_ctf_wrapped,
+ * adorym/conventional.py:112-152): the phase map of one angle from its n_dists holograms I_d,
+ *     phase = Re IFFT2( sum_d w_d FFT2(I_d - 1) / (sum_d 2 w_d^2 + alpha) ),   w_d = sin xi_d + cos xi_d / kappa,
+ * with xi_d, kappa = 10^lg_kappa, lambda_nm and (u, v) as in the forward model above; each distance enters as
+ * fl32(PI lambda_nm dist_nm_d), rounded once.  alpha is the reference's 1e-10 or a table per frequency (the frequency-dependent
+ * regulariser of adorym/util.py:1601-1626, built by the caller).  Deviations, stated:
+ *   - the data are used as given (I - 1), whatever raw_data_type is, as the reference does;
+ *   - no registration happens inside (adorym_amd.CTFInversion.retrieve(affine=...) registers |data| in front of the call);
+ *   - safe_zone_width is always 0, as adorym/array_ops.py:282-285 calls it.
+ * Sides are powers of two in [16, 2048] (else ADM_ERR_UNSUPPORTED).  ADM_ERR_INVALID: n_dists outside [1, 64], max_batch < 1 (or so
+ * large that max_batch > 65535 or max_batch n_dists ny > 2^30), n_batch outside [1, max_batch], out_stride not 1 or 2, a NULL
+ * pointer, an alpha entry that is not finite and > 0 (with alpha = 0 the reference divides 0 by 0 at DC for a pure-phase kappa).
+ * The handle owns the work fields T1 [max_batch][n_dists][nx][ny] and T2 [max_batch][ny][nx] (complex), the frequency table, the
+ * alpha table (stored [nx][ny]) and the twiddles.  Three launches per call on the stream the context is enqueuing on, no atomics:
+ * two calls give the same bits. */
+typedef struct adm_ctfinv adm_ctfinv;
+typedef struct adm_ctfinv_desc {
+    int32_t ny, nx, n_dists, max_batch;
+    double  energy_ev, psize_cm;
+} adm_ctfinv_desc;
+/* alpha_host: HOST floats [ny][nx], or NULL = 1e-10 everywhere */
+int adm_ctfinv_create(adm_ctx* ctx, const adm_ctfinv_desc* desc, const float* alpha_host, adm_ctfinv** out);
+int adm_ctfinv_destroy(adm_ctfinv* h);
+/* data [n_batch][n_dists][ny][nx] (raw, used as given), lg_kappa [1], out: device pointers; dists_cm: HOST doubles [n_dists].
+ * out_stride = 1: out is [n_batch][ny][nx].  out_stride = 2: value i goes to out[2 i], the delta channel of [ny][nx][2] objects;
+ * the other channel is not touched. */
+int adm_ctfinv_run(adm_ctfinv* h, const float* data, int n_batch, const double* dists_cm, const float* lg_kappa, float* out,
+                   int out_stride);
+
 /* ---- f1  affine registration of measured holograms, on its own --------------------------
  * optimize_prj_affine (adorym/forward_model.py:1066-1072; w.affine_transform, wrappers.py:1159-1174 = F.affine_grid +
  * F.grid_sample, bilinear, padding_mode='border', align_corners=False) for forward models other than adm_holo_fwd_adj -- a 3-D
