@@ -180,6 +180,7 @@ SIGNATURES = {
     'adm_ctf_create': (_I, [_VP, C.POINTER(CtfDesc), C.POINTER(_VP)]),
     'adm_ctf_destroy': (_I, [_VP]),
     'adm_ctf_fwd_adj': (_I, [_VP, _VP, C.POINTER(_D), _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    'adm_ctfd_fwd_adj': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     'adm_ctfinv_create': (_I, [_VP, C.POINTER(CtfInvDesc), _VP, C.POINTER(_VP)]),
     'adm_ctfinv_destroy': (_I, [_VP]),
     'adm_ctfinv_run': (_I, [_VP, _VP, _I, C.POINTER(_D), _VP, _VP, _I]),

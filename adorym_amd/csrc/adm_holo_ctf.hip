@@ -11,6 +11,7 @@
 //     dL/dD  = Re IFFT2( sum_d osc_d FFT2(q_d) )                       (the operator is real and symmetric: its own adjoint)
 //     dL/dbeta = 0                                                     (the model never reads beta)
 //     dL/dlg_kappa = -(2 ln 10 / kappa) / n  sum_d Re sum_k conj(Q_d) cos xi_d F        Q_d = FFT2(q_d), F = FFT2(D)
+//     dL/dd_d [per cm] = (2 PI lambda_nm 1e7 / n)  Re sum_k conj(Q_d) (cos xi_d - sin xi_d / kappa) (u^2 + v^2) F
 // A pixel with I_d <= 0 predicts 0 and contributes to no gradient (the reference's autograd returns NaN everywhere then).
 //
 // The line machinery -- Stockham passes in LDS, LineGeo, the block-cooperative transposed stores, the LDS twiddle copy -- is the
@@ -20,28 +21,24 @@
 //   C2  lines kx    : FFT_y -> F (kept: Ft[kx][ky]) ; per d: x osc_d -> IFFT_y                   -> W[d][y][kx]
 //   C3  rows (d, y) : IFFT_x / n -> I_d, pred_d, loss partial, q_d -> FFT_x                      -> T3[d][kx][y]
 //   C4  lines kx    : per d: FFT_y -> Q_d ; kappa partial += Re conj(Q_d) cos xi_d F ; G += osc_d Q_d ; IFFT_y -> T4[kx][y]
-//   C5  rows y      : IFFT_x / n -> dL/dD (+= or =) ; the loss and kappa sums of C3 / C4 in a fixed order
+//                     with grad_dists: the line's sum of Re conj(Q_d) (cos xi_d - sin xi_d / kappa) (u^2 + v^2) F -> partd[d][kx]
+//   C5  rows y      : IFFT_x / n -> dL/dD (+= or =) ; the loss and kappa sums of C3 / C4 in a fixed order, then the n_dists
+//                     distance sums of C4
 // A forward-only call stops after C3 and sums with ctf_sums_kernel.
+//
+// The distances come from the host (c[d] = fl32(PI lambda dist_nm_d): the reference's Python double, rounded once where it meets
+// the float32 tensors) or, for a run that refines them, from a float32 device array in cm that the optimiser moves in place.  Then
+//     c_d = fl32( fl32(PI lambda_nm) * fl32(dists_dev[d] * 1e7f) )
+// as the reference's float32 run has it when free_prop_cm is a float32 tensor: dist_nm = free_prop_cm * 1e7 is a float32 product,
+// and PI * lmbda_nm (a Python double) meets that 0-dim tensor as a float32 scalar (adorym/propagate.py:470, 598).
 #include <vector>
 #include <cmath>
 #include <cstring>
-#include "adm_host.h"
+#include "adm_ctf_group.h"
 #include "adm_fft.h"
 #include "adm_ms_math.h"
 
 #define ADM_CTF_MAX_DISTS 64
-
-struct adm_ctf {
-    adm_ctx* ctx;
-    adm_ctf_desc d;
-    float2 *tw_y, *tw_x;      // exp(-2 pi i j / N) for N = ny, nx
-    float* uv2t;              // [nx][ny]: u^2 + v^2 (nm^-2) of frequency (ky, kx) at [kx][ky], fp32 like the reference's tensors
-    float2 *T14, *Ft;         // T14 [nx][ny]: x spectra of the rows (C1 -> C2), later the y-inverse of G (C4 -> C5); Ft [nx][ny] = FFT2(D)
-    float2 *W, *T3;           // [n_dists][ny][nx] / [n_dists][nx][ny] work fields
-    float* part3;             // [n_dists][ny] per-row loss sums
-    double* part4;            // [nx] per-line sums of the kappa gradient
-    float* loss_scratch;      // [n_dists]: where the loss sums go when the caller wants none
-};
 
 namespace adm {
 namespace ctf {
@@ -140,7 +137,17 @@ struct CtfArgs {
     int ny, nx, nd, intensity, set_obj;
     float inv_n, qscale;                            // 1 / n;  1 / (n_dists n)
     float c[ADM_CTF_MAX_DISTS];                     // fl32(PI lambda dist_nm_d): rounded once on the host, like the reference's Python double
+    const float* dists_dev;                         // [nd] cm, or NULL: the distances are c[]
+    float pil;                                      // fl32(PI lambda_nm)
+    double* partd;                                  // [nd][nx]
+    float* grad_dists;                              // [nd] or NULL
+    double dscale;                                  // 2 PI lambda_nm 1e7 / n
 };
+
+// c_d of distance d: the host's, or formed from the device array with the reference's float32 roundings (head comment)
+__device__ __forceinline__ float ctf_c_of(const CtfArgs& A, int d) {
+    return A.dists_dev ? mul_rounded(A.pil, mul_rounded(A.dists_dev[d], 1e7f)) : A.c[d];
+}
 
 // 1 / kappa = 10^-lg_kappa, formed in double and rounded once (the reference keeps ctf_lg_kappa in float64)
 __device__ __forceinline__ double inv_kappa_f64(const float* lg_kappa) { return exp(-2.302585092994045684 * (double)lg_kappa[0]); }
@@ -155,7 +162,9 @@ __device__ __forceinline__ void stage_inv_kappa(float* slot, const float* lg_kap
 __device__ __forceinline__ void ctf_sincos(float uv2, float c, float& sn, float& cs) { sincos_fast(c * uv2, sn, cs); }
 __device__ __forceinline__ float ctf_osc(float sn, float cs, float inv_kappa) { return 2.f * (sn + inv_kappa * cs); }
 
-template <int TPR> __device__ __forceinline__ float line_sum(float v, float* red) {
+// the sum over the TPR threads of a line in a fixed tree: shuffles inside a wave, through `red` (256 entries, free again when the
+// call returns) for lines of several waves; float for the loss, double for the distance gradient
+template <int TPR, typename T> __device__ __forceinline__ T line_sum(T v, T* red) {
     if (TPR <= 64) {
 #pragma unroll
         for (int s = TPR / 2; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
@@ -169,7 +178,7 @@ template <int TPR> __device__ __forceinline__ float line_sum(float v, float* red
         if ((tid % TPR) < s) red[tid] += red[tid + s];
         __syncthreads();
     }
-    const float r = red[tid - tid % TPR];
+    const T r = red[tid - tid % TPR];
     __syncthreads();
     return r;
 }
@@ -213,7 +222,7 @@ template <int NY> __global__ __launch_bounds__(256) void ctf_c2(CtfArgs A) {
     cf* p = (F == a) ? b : a;
     if (ok && d == 0)
         for (int k = t; k < NY; k += LG::TPR) A.Ft[(size_t)kx * NY + k] = F[k];
-    const float c = A.c[d];
+    const float c = ctf_c_of(A, d);
     for (int k = t; k < NY; k += LG::TPR) {
         float sn = 0.f, cs = 0.f;
         if (ok) ctf_sincos(A.uv2t[(size_t)kx * NY + k], c, sn, cs);
@@ -263,7 +272,7 @@ template <int NX, bool GRAD> __global__ __launch_bounds__(256) void ctf_c3(CtfAr
         }
         if (GRAD) oth[x] = make_float2((ok && I > 0.f) ? A.qscale * diff / pr : 0.f, 0.f);
     }
-    const float ls = line_sum<LG::TPR>(lsum, red);
+    const float ls = line_sum<LG::TPR, float>(lsum, red);
     if (ok && t == 0) A.part3[job] = ls;
     if (!GRAD) return;
     line_sync<LG::TPR>();
@@ -273,6 +282,53 @@ template <int NX, bool GRAD> __global__ __launch_bounds__(256) void ctf_c3(CtfAr
         const int j = job0 + c, dd = j / ny, yy = j % ny;          // (the lines of a block may belong to different distances when ny < LPB)
         return T3 + (size_t)dd * NX * ny + (size_t)k * ny + yy;
     });
+}
+
+// C4's rounds over the distances: slot ll owns distance d0 + ll in round d0.  Returns the thread's terms of the kappa gradient.
+// GD: the distance gradient as well, as a code path of its own: a launch without grad_dists executes the instructions it executed
+// before the distances became parameters.  Both instantiations live in the one kernel, so that launch runs with the larger register
+// allocation too, and the split had no measured effect on the group's time (DESIGN.md sections 4 and 5).
+template <int NY, bool GD>
+__device__ __forceinline__ double ctf_c4_rounds(const CtfArgs& A, cf* a, cf* b, cf* GF, const float2* tw, double* redd, const float* ik_s,
+                                                int ll, int t, int kx) {
+    using LG = LineGeo<NY>;
+    // the kappa gradient is a sum of O(n_dists n) terms of mixed sign: every thread adds its terms in double
+    double kacc = 0.0;
+    for (int d0 = 0; d0 < A.nd; d0 += LG::LPB) {
+        const int d = d0 + ll;
+        const bool ok = d < A.nd;
+        for (int j = t; j < NY; j += LG::TPR) a[j] = ok ? A.T3[((size_t)d * A.nx + kx) * NY + j] : make_float2(0.f, 0.f);
+        if (d0 == 0) __syncthreads();                 // (also orders the twiddle copy of stage_twiddles and 1 / kappa before the first pass)
+        else line_sync<LG::TPR>();
+        const float ik = *ik_s;
+        const cf* Q = line_fft<NY, false>(a, b, tw, t);
+        const float c = ok ? ctf_c_of(A, d) : 0.f;
+        double dacc = 0.0;                            // this round's distance: the thread's terms of dL/dd_d, in double like kacc
+        if (ok)
+            for (int k = t; k < NY; k += LG::TPR) {
+                const size_t e = (size_t)kx * NY + k;
+                float sn, cs;
+                const float uv2 = A.uv2t[e];
+                ctf_sincos(uv2, c, sn, cs);
+                const cf q = Q[k];
+                GF[k] = caxpy(GF[k], ctf_osc(sn, cs, ik), q);
+                if (A.grad_lg_kappa) {
+                    const cf f = A.Ft[e];
+                    kacc += (double)(cs * (q.x * f.x + q.y * f.y));         // Re( conj(Q) cos xi F )
+                }
+                if (GD) {
+                    const cf f = A.Ft[e];
+                    dacc += (double)((cs - ik * sn) * uv2) * (double)(q.x * f.x + q.y * f.y);
+                }
+            }
+        if (GD) {
+            // the line's TPR sums in a fixed tree: one partial per (d, kx); an idle slot writes nothing
+            const double s = line_sum<LG::TPR, double>(dacc, redd);
+            if (ok && t == 0) A.partd[(size_t)d * A.nx + kx] = s;
+        }
+        line_sync<LG::TPR>();                         // a / b are refilled by the next round of distances
+    }
+    return kacc;
 }
 
 // One line kx per block; slot s of the block works on distances s, s + LPB, ...  Q_d = FFT_y(T3_d) is the unnormalised FFT2(q_d).
@@ -292,31 +348,8 @@ template <int NY> __global__ __launch_bounds__(256) void ctf_c4(CtfArgs A) {
     __shared__ float ik_s;
     stage_inv_kappa(&ik_s, A.lg_kappa);
     for (int k = t; k < NY; k += LG::TPR) GF[k] = make_float2(0.f, 0.f);
-    // the kappa gradient is a sum of O(n_dists n) terms of mixed sign: every thread adds its terms in double
-    double kacc = 0.0;
-    for (int d0 = 0; d0 < A.nd; d0 += LG::LPB) {
-        const int d = d0 + ll;
-        const bool ok = d < A.nd;
-        for (int j = t; j < NY; j += LG::TPR) a[j] = ok ? A.T3[((size_t)d * A.nx + kx) * NY + j] : make_float2(0.f, 0.f);
-        if (d0 == 0) __syncthreads();                 // (also orders the twiddle copy of stage_twiddles and 1 / kappa before the first pass)
-        else line_sync<LG::TPR>();
-        const float ik = ik_s;
-        const cf* Q = line_fft<NY, false>(a, b, tw, t);
-        const float c = ok ? A.c[d] : 0.f;
-        if (ok)
-            for (int k = t; k < NY; k += LG::TPR) {
-                const size_t e = (size_t)kx * NY + k;
-                float sn, cs;
-                ctf_sincos(A.uv2t[e], c, sn, cs);
-                const cf q = Q[k];
-                GF[k] = caxpy(GF[k], ctf_osc(sn, cs, ik), q);
-                if (A.grad_lg_kappa) {
-                    const cf f = A.Ft[e];
-                    kacc += (double)(cs * (q.x * f.x + q.y * f.y));         // Re( conj(Q) cos xi F )
-                }
-            }
-        line_sync<LG::TPR>();                         // a / b are refilled by the next round of distances
-    }
+    const double kacc = A.grad_dists ? ctf_c4_rounds<NY, true>(A, a, b, GF, tw, redd, &ik_s, ll, t, kx)
+                                     : ctf_c4_rounds<NY, false>(A, a, b, GF, tw, redd, &ik_s, ll, t, kx);
     __syncthreads();                                  // every slot's GF is complete
     if (A.grad_lg_kappa) {
         // the 256 threads' sums in a fixed tree: one slot per line kx
@@ -366,6 +399,18 @@ __device__ __forceinline__ void ctf_sum_one(const CtfArgs& A, bool grad, int o) 
         A.grad_lg_kappa[0] = (A.set_obj ? 0.f : A.grad_lg_kappa[0]) + g;
     }
 }
+// dL/dd_o from C4's per-line sums, by one whole wave: (2 PI lambda_nm 1e7 / n) x the sum, in double, one rounding
+__device__ __forceinline__ void ctf_sum_dist(const CtfArgs& A, int o) {
+    const int lane = threadIdx.x & 63;
+    double s = 0.0;
+    for (int x = lane; x < A.nx; x += 64) s += A.partd[(size_t)o * A.nx + x];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (lane == 0) {
+        const float g = (float)(A.dscale * s);
+        A.grad_dists[o] = (A.set_obj ? 0.f : A.grad_dists[o]) + g;
+    }
+}
 __global__ __launch_bounds__(64) void ctf_sums_kernel(CtfArgs A) { ctf_sum_one(A, false, blockIdx.x); }
 
 template <int NX> __global__ __launch_bounds__(256) void ctf_c5(CtfArgs A) {
@@ -403,8 +448,11 @@ template <int NX> __global__ __launch_bounds__(256) void ctf_c5(CtfArgs A) {
             A.grad_obj[(size_t)y * NX + x] = go;
         }
     // the sums of C3 / C4: output o by wave 0 of block o % gridDim.x
-    if (threadIdx.x < 64)
+    if (threadIdx.x < 64) {
         for (int o = blockIdx.x; o <= A.nd; o += gridDim.x) ctf_sum_one(A, true, o);
+        if (A.grad_dists)
+            for (int o = blockIdx.x; o < A.nd; o += gridDim.x) ctf_sum_dist(A, o);
+    }
 }
 
 #define ADM_CTF_SIZES(X) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048)
@@ -502,18 +550,18 @@ extern "C" int adm_ctf_create(adm_ctx* ctx, const adm_ctf_desc* desc, adm_ctf** 
 
 extern "C" int adm_ctf_destroy(adm_ctf* h) {
     if (!h) return ADM_OK;
-    void* bufs[] = {h->tw_y, h->tw_x, h->uv2t, h->T14, h->Ft, h->W, h->T3, h->part3, h->part4, h->loss_scratch};
+    void* bufs[] = {h->tw_y, h->tw_x, h->uv2t, h->T14, h->Ft, h->W, h->T3, h->part3, h->part4, h->loss_scratch, h->partd};
     for (void* b : bufs)
         if (b) adm_free(h->ctx, b);
     delete h;
     return ADM_OK;
 }
 
-extern "C" int adm_ctf_fwd_adj(adm_ctf* h, const float* obj, const double* dists_cm, const float* lg_kappa, const float* data,
-                               int want_grad, float* grad_obj, float* grad_lg_kappa, float* pred, float* loss_sum) {
-    if (!h || !obj || !dists_cm || !lg_kappa || !data) return fail(ADM_ERR_INVALID, "adm_ctf_fwd_adj: null argument");
-    if (want_grad < 0 || want_grad > 2) return fail(ADM_ERR_INVALID, "adm_ctf_fwd_adj: want_grad must be 0, 1 or 2");
-    if (want_grad && !grad_obj) return fail(ADM_ERR_INVALID, "adm_ctf_fwd_adj: want_grad needs grad_obj");
+int adm::ctf::group_run(adm_ctf* h, const char* who, const float* obj, const double* dists_cm, const float* dists_dev, const float* lg_kappa,
+                        const float* data, int want_grad, float* grad_obj, float* grad_lg_kappa, float* grad_dists, float* pred, float* loss_sum) {
+    if (!h || !obj || (!dists_cm && !dists_dev) || !lg_kappa || !data) return fail(ADM_ERR_INVALID, std::string(who) + ": null argument");
+    if (want_grad < 0 || want_grad > 2) return fail(ADM_ERR_INVALID, std::string(who) + ": want_grad must be 0, 1 or 2");
+    if (want_grad && !grad_obj) return fail(ADM_ERR_INVALID, std::string(who) + ": want_grad needs grad_obj");
     const adm_ctf_desc& d = h->d;
     const size_t n = (size_t)d.ny * d.nx;
     ctf::CtfArgs A;
@@ -524,13 +572,26 @@ extern "C" int adm_ctf_fwd_adj(adm_ctf* h, const float* obj, const double* dists
     A.pred = pred; A.part3 = h->part3; A.part4 = h->part4;
     A.grad_obj = (float2*)grad_obj;
     A.grad_lg_kappa = want_grad ? grad_lg_kappa : nullptr;
+    A.grad_dists = want_grad ? grad_dists : nullptr;
+    A.partd = h->partd;
+    if (A.grad_dists && !A.partd) return fail(ADM_ERR_INVALID, std::string(who) + ": grad_dists without the partial sums' buffer");
     A.loss_sum = loss_sum ? loss_sum : h->loss_scratch;
     A.ny = d.ny; A.nx = d.nx; A.nd = d.n_dists; A.intensity = d.raw_intensity;
     A.set_obj = (want_grad == 2) ? 1 : 0;
     A.inv_n = (float)(1.0 / (double)n);
     A.qscale = (float)(1.0 / ((double)n * d.n_dists));
     const double lambda_nm = 1240.0 / d.energy_ev;
-    for (int i = 0; i < d.n_dists; ++i) A.c[i] = (float)(3.14159265359 * lambda_nm * (dists_cm[i] * 1e7));
+    A.dists_dev = dists_dev;
+    A.pil = (float)(3.14159265359 * lambda_nm);
+    A.dscale = 2.0 * 3.14159265359 * lambda_nm * 1e7 / (double)n;
+    if (!dists_dev)
+        for (int i = 0; i < d.n_dists; ++i) A.c[i] = (float)(3.14159265359 * lambda_nm * (dists_cm[i] * 1e7));
     ADM_HIP(ctf::ctf_run(A, want_grad != 0, h->ctx->stream));
     return ADM_OK;
+}
+
+extern "C" int adm_ctf_fwd_adj(adm_ctf* h, const float* obj, const double* dists_cm, const float* lg_kappa, const float* data,
+                               int want_grad, float* grad_obj, float* grad_lg_kappa, float* pred, float* loss_sum) {
+    if (!dists_cm) return fail(ADM_ERR_INVALID, "adm_ctf_fwd_adj: null argument");
+    return ctf::group_run(h, "adm_ctf_fwd_adj", obj, dists_cm, nullptr, lg_kappa, data, want_grad, grad_obj, grad_lg_kappa, nullptr, pred, loss_sum);
 }

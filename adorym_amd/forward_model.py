@@ -725,6 +725,11 @@ class MultiDistModel(PtychographyModel):
     this model (``two_d_mode=False``: :905-914 rotates it, propagate.py:467-476 sums it along the beam) is served when, and only
     when, ``common_vars_dict['ctf_projector']`` is an adorym_amd.RotatedProjector: the angle's projection (adm_rotate_project_fwd) is
     the engine's one slice and its gradient is back-projected into grad_obj (adm_rotate_project_adj); no rotated-frame buffer.
+    Capability decides here as well, in 2-D and with a projector: a ``ctf_engine`` built with ``refine_distances=True`` serves
+    ``optimize_free_prop`` (``free_prop_cm`` is then the engine's device array ``ctf_engine.dists`` or host values uploaded into
+    it, and the gradient w.r.t. it comes from the same launch group, adm_ctfd_fwd_adj), and
+    ``common_vars_dict['hologram_registration']`` serves ``optimize_prj_affine`` as below; the registered targets are magnitudes
+    already, so that run's ``ctf_engine`` is built with raw_data_type='magnitude' and the registration carries the run's raw type.
 
     A 3-D object (``two_d_mode=False``: holotomography, :905-914, 971-1019), one undivided field of view without a safe zone,
     ``forward_algorithm='fresnel'``: ``common_vars_dict['engine']`` is a MultisliceEngine built with ``detector_fanout=True`` for
@@ -765,8 +770,11 @@ class MultiDistModel(PtychographyModel):
         # ... and holds them as parameters on the device (what the engine can do decides, not a flag of its own)
         self.refine_3d = self.fanout and bool(getattr(self.engine, 'refine_distances', False))
         # ... and the holograms are registered by kernels of their own when the caller brought that engine (likewise)
-        self.registration = common_vars_dict.get('hologram_registration') if self.fanout else None
-        self.register_3d = self.registration is not None
+        self.registration = common_vars_dict.get('hologram_registration') if (self.fanout or self.is_ctf) else None
+        self.register_3d = self.fanout and self.registration is not None
+        # the CTF model likewise: distances on the device when its engine holds them, registration when the caller brought it
+        self.refine_ctf = self.is_ctf and bool(getattr(self.ctf, 'refine_distances', False))
+        self.register_ctf = self.is_ctf and self.registration is not None
 
     def _check(self, safe_zone_width, ctf_lg_kappa, probe_pos_correction):
         cv = self.common_vars
@@ -856,7 +864,8 @@ class MultiDistModel(PtychographyModel):
             self.registration.grad(data, aff, self.engine.pred_device(), self._grad_affine_dev.zero_())
         return out
 
-    # what the CTF model refuses by name: it has no probe, one slice, one undivided field of view, fixed distances and no registration
+    # what the CTF model refuses by name: it has no probe, one slice and one undivided field of view; distances are fixed unless its
+    # engine refines them, and holograms are taken as registered unless the caller brought a HologramRegistration
     CTF_REFUSED_FLAGS = ('optimize_probe', 'optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos')
 
     def _check_ctf(self, safe_zone_width, ctf_lg_kappa):
@@ -873,12 +882,20 @@ class MultiDistModel(PtychographyModel):
         elif self.loss_function_type != 'lsq':
             what = "loss_function_type='%s'" % self.loss_function_type
         for flag in self.CTF_REFUSED_FLAGS:
-            if what is None and cv.get(flag):
+            served = (flag == 'optimize_free_prop' and self.refine_ctf) or (flag == 'optimize_prj_affine' and self.register_ctf)
+            if what is None and cv.get(flag) and not served:
                 what = flag
         if what is not None:
             raise NotImplementedError("forward_algorithm='ctf' with %s is outside the accelerated path" % what)
         if ctf_lg_kappa is None:
             raise ValueError("forward_algorithm='ctf' needs ctf_lg_kappa")
+        if self.register_ctf and cv.get('optimize_prj_affine'):
+            reg, eng = self.registration, self.ctf
+            if (reg.n_dists, reg.ny, reg.nx) != (eng.n_dists, eng.ny, eng.nx) or reg.raw_data_type != self.raw_data_type:
+                raise ValueError('MultiDistModel: hologram_registration was built for another field, number of distances or raw_data_type')
+            if getattr(eng, 'raw_data_type', None) != 'magnitude':
+                raise ValueError("MultiDistModel: forward_algorithm='ctf' with optimize_prj_affine needs a ctf_engine built with "
+                                 "raw_data_type='magnitude' (the registered holograms are magnitudes already)")
         if not cv.get('two_d_mode'):
             # a 3-D object: rotated inside the loop by the projector, on one rank, on a field the CTF engine takes
             sides = (self.ctf.ny, self.ctf.nx)
@@ -893,30 +910,56 @@ class MultiDistModel(PtychographyModel):
                 raise NotImplementedError("forward_algorithm='ctf' with %s is outside the accelerated path" % what)
 
     def _run_ctf(self, obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad, grad_obj=None, grad_lg_kappa=None, want_pred=False,
-                 overwrite=False):
-        """One launch group of adm_ctf_fwd_adj.  The distances are not refined under this model: they go in as host doubles."""
+                 overwrite=False, grad_dists=None, prj_affine_ls=None, want_affine_grad=False):
+        """One launch group of adm_ctf_fwd_adj: the distances go in as host doubles.  An engine that refines them
+        (adm_ctfd_fwd_adj) takes its own device array, or host values that it uploads into it.  With optimize_prj_affine the raw
+        holograms registered by ``prj_affine_ls`` are the launch's data, and its predictions feed dL/d prj_affine_ls
+        (``want_affine_grad``: left in self._grad_affine_dev), exactly as _run_3d does it."""
         nd = self.ctf.n_dists
-        dists = free_prop_cm.get() if isinstance(free_prop_cm, DeviceArray) else free_prop_cm
-        dists = np.asarray(dists, dtype=np.float64).reshape(nd)
+        kw = {}
+        if self.refine_ctf:
+            if isinstance(free_prop_cm, DeviceArray) and free_prop_cm.ptr != self.ctf.dists.ptr:
+                raise ValueError("forward_algorithm='ctf' with refined distances: free_prop_cm on the device must be the engine's own "
+                                 "array (ctf_engine.dists)")
+            dists = free_prop_cm
+            kw['grad_dists'] = grad_dists
+        else:
+            if grad_dists is not None:
+                raise RuntimeError('gradient w.r.t. free_prop_cm requested but the CTF engine does not refine its distances')
+            dists = free_prop_cm.get() if isinstance(free_prop_cm, DeviceArray) else free_prop_cm
+            dists = np.asarray(dists, dtype=np.float64).reshape(nd)
         lgk = self._dev('ctf_lg_kappa', ctf_lg_kappa, (1,))
+        data = raw = self._data(this_i_theta)
+        aff = None
+        if self.register_ctf and self.common_vars.get('optimize_prj_affine'):
+            # forward_model.py:1066-1072: the raw holograms of this angle registered by prj_affine_ls are the launch's data
+            aff = self._dev('prj_affine_ls', prj_affine_ls, (nd, 2, 3))
+            data = self.registration.targets(raw, aff)
+            want_pred = want_pred or want_affine_grad
+        elif want_affine_grad:
+            raise RuntimeError('gradient w.r.t. prj_affine_ls requested but the model registers no holograms')
         if self.ctf_3d and not self.common_vars.get('two_d_mode'):
             # forward_model.py:905-914 + propagate.py:467-476: the rotated object summed along the beam is the model's one slice.
-            # The launch group overwrites the slice's gradient (and kappa's: one launch per evaluation), the back-projection adds it
-            # to grad_obj, which is zero-filled first where it holds garbage (``overwrite``).
+            # The launch group overwrites the slice's gradient (and kappa's and the distances': one launch per evaluation), the
+            # back-projection adds it to grad_obj, which is zero-filled first where it holds garbage (``overwrite``).
             rp = self.ctf_projector
             table = self.common_vars['rotation_tables'](int(this_i_theta))
             proj = rp.project(obj, table)
             if want_grad and getattr(self, '_gproj', None) is None:
                 self._gproj = self.device.empty(tuple(proj.shape))
-            self.ctf.forward_adjoint(proj, dists, lgk, self._data(this_i_theta), want_grad=want_grad, grad_obj=self._gproj if want_grad else None,
-                                     grad_lg_kappa=grad_lg_kappa, want_pred=want_pred, overwrite=True)
+            self.ctf.forward_adjoint(proj, dists, lgk, data, want_grad=want_grad, grad_obj=self._gproj if want_grad else None,
+                                     grad_lg_kappa=grad_lg_kappa, want_pred=want_pred, overwrite=True, **kw)
             if want_grad:
                 if overwrite:
                     grad_obj.zero_()
                 rp.backproject(self._gproj, table, grad_obj)
-            return
-        self.ctf.forward_adjoint(obj, dists, lgk, self._data(this_i_theta), want_grad=want_grad,
-                                 grad_obj=grad_obj, grad_lg_kappa=grad_lg_kappa, want_pred=want_pred, overwrite=overwrite)
+        else:
+            self.ctf.forward_adjoint(obj, dists, lgk, data, want_grad=want_grad,
+                                     grad_obj=grad_obj, grad_lg_kappa=grad_lg_kappa, want_pred=want_pred, overwrite=overwrite, **kw)
+        if want_affine_grad:
+            if getattr(self, '_grad_affine_dev', None) is None:
+                self._grad_affine_dev = self.device.empty((nd, 2, 3))
+            self.registration.grad(raw, aff, self.ctf.pred_device(), self._grad_affine_dev.zero_())
 
     # ------------------------------------------------------------------ sub-tiles + safe zone (forward_model.py:884-1034)
     # One engine serves all distances: its plan holds the n_dists detector-plane kernels and a launch lists every tile of the
@@ -1113,7 +1156,7 @@ class MultiDistModel(PtychographyModel):
                            prj_pos_offset):
             self._check(safe_zone_width, ctf_lg_kappa, probe_pos_correction)
             if self.is_ctf:
-                self._run_ctf(obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad=False)
+                self._run_ctf(obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad=False, prj_affine_ls=prj_affine_ls)
                 self.current_loss = float(self.ctf.loss() + self._regularize(obj, None))
                 return self.current_loss
             if self.fanout:
@@ -1160,20 +1203,26 @@ class MultiDistModel(PtychographyModel):
         if self.is_ctf:
             # as on the undivided Fresnel path below: '=' into a buffer that holds garbage, '+=' otherwise; the regulariser adds
             i_k = self.get_argument_index('ctf_lg_kappa')
+            i_fp, i_af = self.get_argument_index('free_prop_cm'), self.get_argument_index('prj_affine_ls')
             for i in opt_args_ls:
-                if i not in (0, i_k):
+                if i not in (0, i_k) and not (i == i_fp and self.refine_ctf) and not (i == i_af and self.register_ctf):
                     raise NotImplementedError("forward_algorithm='ctf': the gradient w.r.t. '%s' is outside the accelerated path" % self.argument_ls[i])
             gk = None
             if i_k in opt_args_ls:
                 if getattr(self, '_gk', None) is None:
                     self._gk = self.device.empty((1,))
                 gk = self._gk if _init_grad else self._gk.zero_()
+            gd = None
+            if i_fp in opt_args_ls:
+                if getattr(self, '_gd_ctf', None) is None:
+                    self._gd_ctf = self.device.empty((self.ctf.n_dists,))
+                gd = self._gd_ctf if _init_grad else self._gd_ctf.zero_()
             self._run_ctf(obj, this_i_theta, free_prop_cm, ctf_lg_kappa, want_grad=True, grad_obj=grad_obj, grad_lg_kappa=gk,
-                          overwrite=bool(_init_grad))
+                          overwrite=bool(_init_grad), grad_dists=gd, prj_affine_ls=prj_affine_ls, want_affine_grad=i_af in opt_args_ls)
             regv = self._reg_value_async(self._regularize_launch(obj, grad_obj))
             datav = self.ctf.loss_async()
             self._loss_thunk = lambda: datav() + regv()
-            return tuple(grad_obj if i == 0 else gk for i in opt_args_ls)
+            return tuple(grad_obj if i == 0 else gd if i == i_fp else self._grad_affine_dev if i == i_af else gk for i in opt_args_ls)
         if self.tile_engine is not None:
             if list(opt_args_ls) != [0]:
                 raise NotImplementedError('multi-distance data divided into sub-tiles: only the object gradient is on the accelerated path')

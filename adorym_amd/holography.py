@@ -129,9 +129,13 @@ class HolographyEngine(object):
 class CTFEngine(object):
     """The contrast-transfer-function model of multi-distance holography (forward_algorithm='ctf'; adorym/propagate.py:467-476,
     590-606) for one undivided field of view and one object slice in 'delta_beta'.  See include/adm.h (adm_ctf_*) and
-    csrc/adm_holo_ctf.hip.  No probe enters; the gradient w.r.t. beta is exactly zero."""
+    csrc/adm_holo_ctf.hip.  No probe enters; the gradient w.r.t. beta is exactly zero.
 
-    def __init__(self, ctx, field_size, n_dists, energy_ev, psize_cm, raw_data_type='intensity'):
+    ``refine_distances=True``: the distances are parameters (the reference's optimize_free_prop under 'ctf').  ``self.dists``
+    (DeviceArray float32 [n_dists], cm; ``dists_cm`` fills it) is the parameter itself: the kernels read it in every launch, so an
+    optimiser moves it in place, and forward_adjoint takes ``grad_dists`` (adm_ctfd_fwd_adj, csrc/adm_ctf_dist.hip)."""
+
+    def __init__(self, ctx, field_size, n_dists, energy_ev, psize_cm, raw_data_type='intensity', refine_distances=False, dists_cm=None):
         from ._lib import CtfDesc
         from .device import PinnedArray, Event
         self.ctx = ctx
@@ -142,6 +146,14 @@ class CTFEngine(object):
         h = C.c_void_p()
         check(ctx.lib.adm_ctf_create(ctx.handle, C.byref(desc), C.byref(h)))
         self.handle = h
+        self.raw_data_type = raw_data_type
+        self.refine_distances = bool(refine_distances)
+        self.dists = None
+        if self.refine_distances:
+            self.dists = DeviceArray(ctx, (self.n_dists,), np.float32)
+            self.dists.set(self._host_dists(np.zeros(self.n_dists) if dists_cm is None else dists_cm).astype(np.float32))
+        elif dists_cm is not None:
+            raise ValueError('CTFEngine: dists_cm belongs to refine_distances=True (otherwise every call names its distances)')
         # the per-distance loss sums go straight into page-locked host memory, two alternating slots (see HolographyEngine)
         self._pinned = [PinnedArray(ctx, (max(self.n_dists, 16),)) for _ in range(2)]
         self._events = [Event(ctx) for _ in range(2)]
@@ -156,21 +168,44 @@ class CTFEngine(object):
         except Exception:
             pass
 
-    def forward_adjoint(self, obj, dists_cm, lg_kappa, data, want_grad=True, grad_obj=None, grad_lg_kappa=None, want_pred=False,
-                        overwrite=False):
-        """obj [ny,nx,(1,)2], lg_kappa [1], data [n_dists,ny,nx] (raw) are DeviceArrays; dists_cm is a HOST sequence of n_dists
-        distances in cm.  grad_obj's delta channel and grad_lg_kappa are accumulated (+=; the beta channel is left alone), or
-        overwritten with ``overwrite=True`` (beta channel = 0)."""
+    def _host_dists(self, dists_cm):
         d = np.ascontiguousarray(np.asarray(dists_cm, dtype=np.float64).reshape(-1))
         if d.size != self.n_dists:
             raise ValueError('CTFEngine: %d distances given, %d expected' % (d.size, self.n_dists))
+        return d
+
+    def forward_adjoint(self, obj, dists_cm, lg_kappa, data, want_grad=True, grad_obj=None, grad_lg_kappa=None, want_pred=False,
+                        overwrite=False, grad_dists=None):
+        """obj [ny,nx,(1,)2], lg_kappa [1], data [n_dists,ny,nx] (raw) are DeviceArrays; dists_cm is a HOST sequence of n_dists
+        distances in cm.  grad_obj's delta channel and grad_lg_kappa are accumulated (+=; the beta channel is left alone), or
+        overwritten with ``overwrite=True`` (beta channel = 0).
+        An engine with ``refine_distances``: dists_cm is ``self.dists`` itself, or host values that are uploaded into it first;
+        ``grad_dists`` (DeviceArray float32 [n_dists]) takes dL/d dists in 1/cm like the other gradients."""
         if want_pred and self._pred is None:
             self._pred = DeviceArray(self.ctx, (self.n_dists, self.ny, self.nx), np.float32)
         p = lambda a: a.ptr if a is not None else None
+        mode = (2 if overwrite else 1) if want_grad else 0
+        if not self.refine_distances:
+            if grad_dists is not None:
+                raise ValueError('grad_dists: the engine was built without refine_distances=True')
+            if isinstance(dists_cm, DeviceArray):
+                raise ValueError('CTFEngine: distances on the device need refine_distances=True')
+            d = self._host_dists(dists_cm)
+            self._slot ^= 1
+            check(self.ctx.lib.adm_ctf_fwd_adj(self.handle, obj.ptr, d.ctypes.data_as(C.POINTER(C.c_double)), lg_kappa.ptr, data.ptr,
+                                               mode, p(grad_obj), p(grad_lg_kappa),
+                                               self._pred.ptr if want_pred else None, self._pinned[self._slot].handle))
+            return
+        if isinstance(dists_cm, DeviceArray):
+            if dists_cm.ptr != self.dists.ptr:
+                raise ValueError("CTFEngine: with refine_distances the distances on the device are the engine's own array (engine.dists)")
+        else:
+            self.dists.set(self._host_dists(dists_cm).astype(np.float32))
+        if grad_dists is not None and (not isinstance(grad_dists, DeviceArray) or grad_dists.size != self.n_dists or grad_dists.dtype != np.float32):
+            raise ValueError('grad_dists must be a float32 DeviceArray [%d]' % self.n_dists)
         self._slot ^= 1
-        check(self.ctx.lib.adm_ctf_fwd_adj(self.handle, obj.ptr, d.ctypes.data_as(C.POINTER(C.c_double)), lg_kappa.ptr, data.ptr,
-                                           (2 if overwrite else 1) if want_grad else 0, p(grad_obj), p(grad_lg_kappa),
-                                           self._pred.ptr if want_pred else None, self._pinned[self._slot].handle))
+        check(self.ctx.lib.adm_ctfd_fwd_adj(self.handle, obj.ptr, self.dists.ptr, lg_kappa.ptr, data.ptr, mode, p(grad_obj), p(grad_lg_kappa),
+                                            p(grad_dists), self._pred.ptr if want_pred else None, self._pinned[self._slot].handle))
 
     def loss(self):
         """mean over (distance, pixel) of the squared residual of the last launch -- blocks."""
@@ -189,6 +224,10 @@ class CTFEngine(object):
 
     def pred(self):
         return self._pred.get()
+
+    def pred_device(self):
+        """The predictions of the last launch with want_pred, on the device [n_dists, ny, nx]."""
+        return self._pred
 
 
 class CTFInversion(object):

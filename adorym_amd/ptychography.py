@@ -331,6 +331,11 @@ class _Run(object):
         # update_using_external_algorithm='ctf': the delta channel overwritten by the direct CTF inversion in every minibatch
         # (CTFInversion), on request
         self.ctf_direct_update = bool(kwargs.pop('ctf_direct_update', False))
+        # optimize_free_prop under forward_algorithm='ctf': the distances refined on the device (CTFEngine(refine_distances=True)), on request
+        self.ctf_free_prop = bool(kwargs.pop('ctf_free_prop', False))
+        # optimize_prj_affine under forward_algorithm='ctf': the holograms registered in front of the launch group
+        # (HologramRegistration), on request
+        self.ctf_prj_affine = bool(kwargs.pop('ctf_prj_affine', False))
         self.ops =kwargs.pop('ops', None)
         kwargs.pop('probe_size', None)
         self.kwargs = kwargs
@@ -380,6 +385,14 @@ class _Run(object):
             what = "update_using_external_algorithm='ctf' with %s"
             _not_implemented(self.ctf_tomography, what % 'ctf_tomography')
             _not_implemented(self.forward_algorithm != 'ctf', what % ("forward_algorithm='%s'" % (self.forward_algorithm,)))
+            # (the inversion takes its distances from the host, and the raw holograms: the reference hands prj_affine_ls to
+            # multidistance_ctf_wrapped, array_ops.py:281-285, which the driver's call of CTFInversion does not)
+            _not_implemented(self.ctf_free_prop, what % 'ctf_free_prop')
+            _not_implemented(self.ctf_prj_affine, what % 'ctf_prj_affine')
+        for nm in ('ctf_free_prop', 'ctf_prj_affine'):
+            _not_implemented(getattr(self, nm) and self.forward_algorithm != 'ctf',
+                             "%s with forward_algorithm='%s'" % (nm, self.forward_algorithm))
+            _not_implemented(getattr(self, nm) and self.n_ranks > 1, '%s with more than one rank' % nm)
         _not_implemented(self.shrink_cycle is not None, 'shrink-wrap mask updates')
         _not_implemented(self.initial_tilt is not None, 'initial_tilt')
         _not_implemented(self.interpolation != 'bilinear', "interpolation='%s'" % self.interpolation)
@@ -505,11 +518,14 @@ class _Run(object):
             if self.is_ctf:
                 # modulate_and_get_ctf (adorym/propagate.py:467-476): no probe, one slice in delta/beta, one undivided field of view,
                 # fixed distances, no registration of the holograms
+                # (ctf_free_prop=True: the engine holds the distances as parameters, CTFEngine(refine_distances=True))
+                # (ctf_prj_affine=True: the holograms are registered in front of the launch group, HologramRegistration)
                 what = "forward_algorithm='ctf' with %s"
                 _not_implemented(self.unknown_type == 'real_imag', what % "unknown_type='real_imag'")
                 _not_implemented(self.holo_tiled, what % 'data divided into sub-tiles or safe_zone_width > 0')
                 for nm in ('optimize_probe', 'optimize_free_prop', 'optimize_prj_affine', 'optimize_all_probe_pos'):
-                    _not_implemented(bool(getattr(self, nm)), what % nm)
+                    served = (nm == 'optimize_free_prop' and self.ctf_free_prop) or (nm == 'optimize_prj_affine' and self.ctf_prj_affine)
+                    _not_implemented(bool(getattr(self, nm)) and not served, what % nm)
             if self.holo_tiled:
                 # data divided into sub-tiles and / or a safe zone around every tile (adorym/forward_model.py:884-1034)
                 tile_size = self.tile_size = [int(v) + 2 * safe_zone_width for v in prj.shape[-2:]]
@@ -586,7 +602,15 @@ class _Run(object):
         elif self.is_multi_dist:
             if self.is_ctf:
                 from .holography import CTFEngine
-                self.ctf_engine = CTFEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm, raw_data_type=self.raw_data_type)
+                refine = bool(self.optimize_free_prop and self.ctf_free_prop)
+                register = bool(self.optimize_prj_affine and self.ctf_prj_affine)
+                # (registered holograms reach the engine as magnitudes: the registration takes the square root of intensity data)
+                self.ctf_engine = CTFEngine(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm,
+                                            raw_data_type='magnitude' if register else self.raw_data_type, refine_distances=refine,
+                                            dists_cm=self.free_prop_cm if refine else None)
+                if register:
+                    from .holography import HologramRegistration
+                    self.registration = HologramRegistration(ctx, self.n_dists, probe_size, self.raw_data_type)
                 if self.ctf_direct:
                     from .holography import CTFInversion
                     self.ctf_inversion = CTFInversion(ctx, probe_size, self.n_dists, self.energy_ev, self.psize_cm)
@@ -833,6 +857,9 @@ class _Run(object):
         if self.refine_3d_dists:
             # likewise: the engine's distances are the parameter (plain Adam, no pin, no drift guard: optimizers.py:906-917)
             params['free_prop_cm'] = self.engine.dists
+        self.refine_ctf_dists = bool(self.is_multi_dist and self.is_ctf and getattr(self.ctf_engine, 'refine_distances', False))
+        if self.refine_ctf_dists:
+            params['free_prop_cm'] = self.ctf_engine.dists       # (likewise; the CTF kernels read the array in every launch)
         # The optimised ones, in the order of the gradient tuple; one entry each (+ its gradient in the forward model)
         self.small, self.opt_args_ls = [], [0]
         if self.optimize_probe:
@@ -869,6 +896,7 @@ class _Run(object):
         self.prj_pos_offset_history = None    # (likewise: the offsets after every update)
         self.free_prop_cm_history = None      # (likewise: the distances of a 3-D object after every update)
         self.register_3d = bool(self.holo_3d and self.registration is not None)
+        self.register_ctf = bool(self.is_multi_dist and self.is_ctf and self.registration is not None)
         self.prj_affine_history = None        # (likewise: the registration matrices of a 3-D object after every update)
 
         restored = self.restored_params
@@ -887,18 +915,19 @@ class _Run(object):
                         params[k_] = restored[k_]
             if self.is_sparse_multislice:
                 self.engine.slice_pos_changed()
-            if self.refine_3d_dists:
-                self.engine.dists_changed()
+            if self.refine_3d_dists or self.refine_ctf_dists:
+                if self.refine_3d_dists:
+                    self.engine.dists_changed()
                 mom_ = self._small_moments('free_prop_cm')
                 if mom_ is not None and 'free_prop_cm_moments' in restored:
                     for m_, h_ in zip(mom_, restored['free_prop_cm_moments']):
                         m_.set(np.asarray(h_, dtype=np.float32).reshape(m_.shape))
-            if self.ctf_3d:
+            if self.ctf_3d or self.refine_ctf_dists or self.register_ctf:
                 mom_ = self._small_moments('ctf_lg_kappa')
                 if mom_ is not None and 'ctf_lg_kappa_moments' in restored:
                     for m_, h_ in zip(mom_, restored['ctf_lg_kappa_moments']):
                         m_.set(np.asarray(h_, dtype=np.float32).reshape(m_.shape))
-            if self.register_3d:
+            if self.register_3d or self.register_ctf:
                 mom_ = self._small_moments('prj_affine_ls')
                 if mom_ is not None and 'prj_affine_ls_moments' in restored:
                     for m_, h_ in zip(mom_, restored['prj_affine_ls_moments']):
@@ -930,17 +959,17 @@ class _Run(object):
         for k_, v_ in self.optimizable_params.items():
             if k_ not in out_:
                 out_[k_] = _host(v_)
-        if self.refine_3d_dists:
+        if self.refine_3d_dists or self.refine_ctf_dists:
             # (not part of the reference's format: the moments of the distances' optimiser, so that a resumed run continues the
             # uninterrupted one -- the reference restarts them at zero)
             mom_ = self._small_moments('free_prop_cm')
             if mom_ is not None:
                 out_['free_prop_cm_moments'] = [m_.get() for m_ in mom_]
-        if self.ctf_3d:
-            mom_ = self._small_moments('ctf_lg_kappa')        # (likewise, for the 3-D CTF run)
+        if self.ctf_3d or self.refine_ctf_dists or self.register_ctf:
+            mom_ = self._small_moments('ctf_lg_kappa')        # (likewise, for the 3-D CTF run and the CTF runs that refine more)
             if mom_ is not None:
                 out_['ctf_lg_kappa_moments'] = [m_.get() for m_ in mom_]
-        if self.register_3d:
+        if self.register_3d or self.register_ctf:
             mom_ = self._small_moments('prj_affine_ls')       # (likewise)
             if mom_ is not None:
                 out_['prj_affine_ls_moments'] = [m_.get() for m_ in mom_]
@@ -1326,17 +1355,18 @@ class _Run(object):
                 if k < hist.shape[0]:
                     _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * z.size * k, z.ptr, z.nbytes))
                     self.slice_pos_history[1] = k + 1
-        if self.refine_3d_dists and any(p.key == 'free_prop_cm' for p in due):
-            self.engine.dists_changed()           # the detector planes' kernels are rebuilt in front of the next launch
+        if (self.refine_3d_dists or self.refine_ctf_dists) and any(p.key == 'free_prop_cm' for p in due):
+            if self.refine_3d_dists:
+                self.engine.dists_changed()       # the detector planes' kernels are rebuilt in front of the next launch
             if self.return_state and self.n_epochs != 'auto':
-                x = self.engine.dists
+                x = self.optimizable_params['free_prop_cm']       # (the engine's own array)
                 if self.free_prop_cm_history is None:
                     self.free_prop_cm_history = [self.ctx.zeros((int(self.n_epochs) * self.n_batch, x.size)), 0]
                 hist, k = self.free_prop_cm_history
                 if k < hist.shape[0]:
                     _lib.check(self.ctx.lib.adm_d2d(self.ctx.handle, hist.ptr + 4 * x.size * k, x.ptr, x.nbytes))
                     self.free_prop_cm_history[1] = k + 1
-        if self.register_3d and any(p.key == 'prj_affine_ls' for p in due) and self.return_state and self.n_epochs != 'auto':
+        if (self.register_3d or self.register_ctf) and any(p.key == 'prj_affine_ls' for p in due) and self.return_state and self.n_epochs != 'auto':
             x = self.optimizable_params['prj_affine_ls']
             if self.prj_affine_history is None:
                 self.prj_affine_history = [self.ctx.zeros((int(self.n_epochs) * self.n_batch,) + tuple(x.shape)), 0]

@@ -700,6 +700,15 @@ int adm_ctf_destroy(adm_ctf* h);
  * grad_lg_kappa, pred, loss_sum: NULL where not wanted (grad_obj too when want_grad = 0).  Two launches give the same bits. */
 int adm_ctf_fwd_adj(adm_ctf* h, const float* obj, const double* dists_cm, const float* lg_kappa, const float* data,
                     int want_grad, float* grad_obj, float* grad_lg_kappa, float* pred, float* loss_sum);
+/* The same launch group for a run that refines its distances (optimize_free_prop): dists_cm_dev [n_dists] is a DEVICE array of
+ * float32 distances in cm, read by the kernels of every launch (an optimiser moves it in place; nothing is copied or prepared), and
+ * each distance enters as fl32(fl32(PI lambda_nm) * fl32(dist_cm * 1e7f)), the roundings of the reference's float32 run when
+ * free_prop_cm is a float32 tensor.  grad_dists [n_dists] (device, may be NULL) += dL/d dists_cm, or = when want_grad = 2:
+ *     dL/dd_d = (2 PI lambda_nm 1e7 / n) Re sum_k conj(Q_d) (cos xi_d - sin xi_d / kappa) (u^2 + v^2) F,   Q_d = FFT2(dL/dI_d), F = FFT2(D),
+ * summed in double in a fixed order (two launches give the same bits); asking for it changes no bit of any other output.
+ * Everything else, want_grad and the NULL rules included, is as for adm_ctf_fwd_adj; both entries may alternate on one handle. */
+int adm_ctfd_fwd_adj(adm_ctf* h, const float* obj, const float* dists_cm_dev, const float* lg_kappa, const float* data,
+                     int want_grad, float* grad_obj, float* grad_lg_kappa, float* grad_dists, float* pred, float* loss_sum);
 
 /* ---- f1  the direct inversion of the CTF model (multi-distance phase retrieval in closed form) ---
  * update_using_external_algorithm='ctf' (adorym/array_ops.py:274-286; conventional.multidistance_ctf_wrapped,
