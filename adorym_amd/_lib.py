@@ -12,6 +12,9 @@ LOSS_LSQ, LOSS_POISSON = 0, 1
 FLAG_NONNEG, FLAG_ZERO_CH0, FLAG_ZERO_CH1 = 1, 2, 4
 OPT_ADAM, OPT_GD, OPT_MOMENTUM = 0, 1, 2
 P2P_HANDLE_BYTES, P2P_MAX_RANKS = 64, 16
+CG_MAX_BLOCKS = 1024
+CG_SCRATCH_DOUBLES = 3 * CG_MAX_BLOCKS + 8
+CG_SUM_A, CG_SUM_B, CG_SUM_BETA, CG_SUM_C, CG_SUM_E, CG_SUM_D = range(6)
 
 
 class PlanDesc(C.Structure):
@@ -166,6 +169,11 @@ SIGNATURES = {
     'adm_adam_step_small': (_I, [_VP, C.POINTER(SmallParam), _I, _I, _D, _D, _D]),
     'adm_gd_step': (_I, [_VP, _VP, _VP, _SZ, _SZ, _D, _I, _VP]),
     'adm_momentum_step': (_I, [_VP, _VP, _VP, _VP, _SZ, _SZ, _D, _D, _I, _VP]),
+    'adm_cg_beta': (_I, [_VP, _VP, _VP, _SZ, _I, _VP, _VP]),
+    'adm_cg_direction': (_I, [_VP, _VP, _VP, _VP, _SZ, _VP, _VP]),
+    'adm_cg_fallback': (_I, [_VP, _VP, _VP, _SZ]),
+    'adm_cg_trial': (_I, [_VP, _VP, _VP, _F, _VP, _SZ]),
+    'adm_cg_accept': (_I, [_VP, _VP, _VP, _SZ, _SZ, _I, _VP]),
     'adm_rwl1_update': (_I, [_VP, _VP, _VP, _VP]),
     'adm_reg_grad_weighted': (_I, [_VP, _VP, _VP, _F, _F, _VP, _VP]),
     'adm_axpy': (_I, [_VP, _VP, _VP, _F, _SZ]),

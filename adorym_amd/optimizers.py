@@ -14,6 +14,7 @@ import numpy as np
 from ._lib import check
 from .device import DeviceArray
 from .array_ops import Gradient
+from .linesearch import BackTrackingLineSearch, AdaptiveLineSearch
 
 
 class Optimizer(object):
@@ -124,6 +125,87 @@ class MomentumOptimizer(Optimizer):
         return x
 
 
+class CGOptimizer(Optimizer):
+    """adorym/optimizers.py:594-704: Polak-Ribiere conjugate gradient with a backtracking line search, for the object.
+
+    One update is: adm_cg_beta (beta stays on the device), adm_cg_direction (s, descent_dir_old and the sums the search starts
+    from), one read of the page-locked sums block, adm_cg_fallback when the direction does not descend; then per trial one
+    adm_cg_trial launch into a buffer of the optimiser's and one loss-only evaluation of the forward model
+    (``forward_model.get_loss_function()`` on ``forward_model.loss_args`` with the trial point in the place of ``name``); then
+    adm_cg_accept, which applies the constraints and the support mask to the accepted point -- or to ``x`` itself when the search
+    found nothing.  A new line-search object is built in every call, as in the reference, so every search starts from
+    ``step_size / |s|``.  ``beta`` is 0 when ``i_batch`` is 0 whatever the state holds; where the reference divides by a zero
+    ``sum descent_dir_old^2`` and carries a NaN, beta is 0 here.  ``_diag_precondition_t`` is never set in the reference: there is
+    no preconditioner.  The record of the last update (beta, the descent check, f0, df0, the norm, every trial) is ``self.last``."""
+
+    linesearch_map = {'backtracking': BackTrackingLineSearch, 'adaptive': AdaptiveLineSearch}
+
+    def __init__(self, name, output_folder='.', distribution_mode=None, options_dict=None, forward_model=None):
+        super(CGOptimizer, self).__init__(name, output_folder=output_folder, params_list=['descent_dir_old', 's'],
+                                          distribution_mode=distribution_mode, options_dict=options_dict, forward_model=forward_model)
+        self.i_line_search_step = 0
+        self._diag_precondition_t = None
+        self._linesearch = None
+        self._x_trial = self._scratch = self._sums = None
+        self.last = None
+
+    def _buffers(self, x):
+        from ._lib import CG_SCRATCH_DOUBLES
+        from .device import MappedArray
+        ctx = x.ctx
+        if self._x_trial is None or self._x_trial.size != x.size or self._x_trial.ctx is not ctx:
+            self._x_trial = ctx.empty((x.size,))
+            self._scratch = ctx.empty((CG_SCRATCH_DOUBLES,), np.float64)
+            self._sums = MappedArray(ctx, (8,), np.float64)
+        return self._x_trial, self._scratch, self._sums
+
+    def apply_gradient(self, x, gradient, i_batch=None, step_size=1., linesearch_type='adaptive', max_backtracking_iter=None,
+                       normalize_alpha=True, flags=0, mask=None, **kwargs):
+        from . import _lib as L
+        from .forward_model import ForwardModel
+        g = self.convert_gradient(gradient)
+        forward_model = getattr(gradient, 'forward_model', None)
+        if forward_model is None:
+            forward_model = self.forward_model
+        if not isinstance(forward_model, ForwardModel):
+            raise ValueError('ForwardModel must be supplied either through Gradient object or upon optimizer instantiation.')
+        if self.name not in forward_model.loss_args:
+            raise ValueError("CGOptimizer: '%s' is not an argument of the forward model's loss (only the object is searched)" % self.name)
+        loss_kwargs = forward_model.loss_args
+        loss_fn = forward_model.get_loss_function()
+        f0 = float(forward_model.current_loss)
+        ctx, lib, n = x.ctx, x.ctx.lib, x.size
+        d_old, s = self.params_whole_array_dict['descent_dir_old'], self.params_whole_array_dict['s']
+        x_trial, scratch, sums = self._buffers(x)
+        self._linesearch = self.linesearch_map[linesearch_type](maxiter=max_backtracking_iter, initial_stepsize=step_size,
+                                                                normalize_alpha=normalize_alpha)
+        this_i_batch = int(i_batch if i_batch is not None else self.i_batch)
+        check(lib.adm_cg_beta(ctx.handle, g.ptr, d_old.ptr, n, this_i_batch, scratch.ptr, sums.ptr))
+        check(lib.adm_cg_direction(ctx.handle, g.ptr, s.ptr, d_old.ptr, n, scratch.ptr, sums.ptr))
+        v = sums.get()                      # the one read of an update: waits for the stream
+        a_sum, b_sum, beta = float(v[L.CG_SUM_A]), float(v[L.CG_SUM_B]), float(v[L.CG_SUM_BETA])
+        df0, norm2 = float(v[L.CG_SUM_C]), float(v[L.CG_SUM_E])
+        descends = df0 < 0
+        if not descends:                    # (optimizers.py:672-674)
+            check(lib.adm_cg_fallback(ctx.handle, g.ptr, s.ptr, n))
+            df0, norm2 = -float(v[L.CG_SUM_D]), float(v[L.CG_SUM_D])
+        view = x_trial.view(0, x.shape)
+
+        def trial(alpha):
+            check(lib.adm_cg_trial(ctx.handle, x.ptr, s.ptr, float(alpha), x_trial.ptr, n))
+            return float(loss_fn(**{**loss_kwargs, self.name: view})), x_trial
+
+        out = self._linesearch.search_values(trial, f0, df0, float(np.sqrt(norm2)), x0=x)
+        check(lib.adm_cg_accept(ctx.handle, x.ptr, out.newx.ptr, 0, n, int(flags), mask.ptr if mask is not None else None))
+        self.last = dict(i_batch=this_i_batch, beta_raw=(a_sum / b_sum if (this_i_batch > 0 and b_sum > 0) else 0.), beta=beta,
+                         descent_check=float(v[L.CG_SUM_C]), descends=bool(descends), f0=f0, df0=df0, norm=float(np.sqrt(norm2)),
+                         trials=list(self._linesearch.trials), alpha=float(out.alpha), newf=float(out.newf),
+                         step_count=int(out.step_count), sums=np.array(v))
+        self.i_batch += 1
+        self.i_line_search_step += out.step_count
+        return x
+
+
 def plain_adam(opts):
     """The (b1, b2, eps) that ``opts`` share when every one of them is a plain AdamOptimizer (no option beyond step_size, b1, b2,
     eps), else None.  Under this rule alone a fused launch that updates several arrays gives the bits of their own apply_gradient."""
@@ -193,5 +275,4 @@ def _unsupported(name):
 
 
 CurveballOptimizer = _unsupported('CurveballOptimizer')
-CGOptimizer = _unsupported('CGOptimizer')
 ScipyOptimizer = _unsupported('ScipyOptimizer')

@@ -33,7 +33,7 @@ from .device import Context, DeviceArray
 from .differentiator import Differentiator
 from .dp import DataParallelObject, HipOps, constraint_flags
 from .forward_model import PtychographyModel, MultiDistModel, SparseMultisliceModel
-from .optimizers import Optimizer, AdamOptimizer, GDOptimizer, MomentumOptimizer, apply_small_params, plain_adam
+from .optimizers import Optimizer, AdamOptimizer, GDOptimizer, MomentumOptimizer, CGOptimizer, apply_small_params, plain_adam
 from .propagate import MultisliceEngine, ProjectionEngine, RotationTable, get_kernel
 from .regularizers import L1Regularizer, TVRegularizer, ReweightedL1Regularizer, combined_weights
 from ._io import DataFile, write_tiff, read_tiff
@@ -336,6 +336,8 @@ class _Run(object):
         # optimize_prj_affine under forward_algorithm='ctf': the holograms registered in front of the launch group
         # (HologramRegistration), on request
         self.ctf_prj_affine = bool(kwargs.pop('ctf_prj_affine', False))
+        # optimizer='cg': conjugate gradient with a line search for the object (CGOptimizer), on request
+        self.device_cg = bool(kwargs.pop('device_cg', False))
         self.ops =kwargs.pop('ops', None)
         kwargs.pop('probe_size', None)
         self.kwargs = kwargs
@@ -350,6 +352,21 @@ class _Run(object):
             warnings.warn("adorym_amd has a single backend ('hip'); backend='%s' is ignored." % self.backend)
         global_settings.backend = 'hip'
         _not_implemented(self.distribution_mode is not None, "distribution_mode='%s'" % self.distribution_mode)
+        # conjugate gradient (CGOptimizer: an instance, or optimizer='cg' with device_cg=True) searches along a line with the loss of
+        # the minibatch whose gradient it was handed: one rank, an update per minibatch, the object in its own frame, and the object only
+        self.is_cg = isinstance(self.optimizer, CGOptimizer) or (self.optimizer == 'cg' and self.device_cg)
+        if self.is_cg:
+            what = 'CGOptimizer with %s'
+            _not_implemented(self.n_ranks > 1, what % 'more than one rank (user-defined object optimizers with more than one rank)')
+            # (the reference would judge a gradient accumulated over an angle by the loss of the angle's last minibatch)
+            _not_implemented(self.update_scheme == 'per angle', what % "update_scheme='per angle'")
+            _not_implemented(bool(self.rotate_out_of_loop), what % 'rotate_out_of_loop')
+            _not_implemented(self.update_using_external_algorithm is not None, what % 'update_using_external_algorithm')
+        for nm in ('probe', 'probe_defocusing', 'probe_pos_offset', 'prj_pos_offset', 'all_probe_pos', 'slice_pos', 'free_prop', 'prj_affine',
+                   'tilt', 'ctf_lg_kappa'):
+            # (self.name == 'probe' in the reference's CGOptimizer is dead code in its driver: no small parameter's update hands it a loss)
+            _not_implemented(isinstance(getattr(self, 'optimizer_' + nm), CGOptimizer),
+                             'CGOptimizer as optimizer_%s (it serves the object only)' % nm)
         if self.cpu_only:
             # (demos/2d_ptychography_w_position_correction.py asks for it; there is no CPU path here and none is substituted)
             warnings.warn('cpu_only=True is ignored: adorym_amd computes on the GPU only.')
@@ -676,6 +693,9 @@ class _Run(object):
                           'momentum': (MomentumOptimizer, {})}[optimizer]
             opt = cls('obj', output_folder=self.output_folder, distribution_mode=self.distribution_mode,
                       options_dict=dict(step_size=self.learning_rate, **extra))
+        elif optimizer == 'cg' and self.device_cg:      # (ptychography.py:435-438)
+            opt = CGOptimizer('obj', output_folder=self.output_folder, distribution_mode=self.distribution_mode,
+                              options_dict=dict(step_size=self.learning_rate))
         elif optimizer in ('curveball', 'cg', 'scipy'):
             raise NotImplementedError("optimizer '%s' is outside the accelerated path" % optimizer)
         else:
@@ -684,15 +704,20 @@ class _Run(object):
         self.opt = opt
         self.fused = type(opt) in (AdamOptimizer, GDOptimizer, MomentumOptimizer)
         _not_implemented(not self.fused and self.n_ranks > 1, 'user-defined object optimizers with more than one rank')
-        self.opt_kind = 'adam' if isinstance(opt, AdamOptimizer) else ('momentum' if isinstance(opt, MomentumOptimizer) else 'gd')
+        self.opt_kind = 'adam' if isinstance(opt, AdamOptimizer) else ('momentum' if isinstance(opt, MomentumOptimizer) else
+                                                                     ('cg' if isinstance(opt, CGOptimizer) else 'gd'))
 
         self.ops = self.ops or HipOps(ctx)
-        state = self.state = DataParallelObject(self.ops, comm, [*obj_size, 2], n_moments={'adam': 2, 'momentum': 1, 'gd': 0}[self.opt_kind])
+        state = self.state = DataParallelObject(self.ops, comm, [*obj_size, 2], n_moments={'adam': 2, 'momentum': 1, 'gd': 0, 'cg': 2}[self.opt_kind])
         if self.fused:
             if self.opt_kind == 'adam':
                 opt.params_whole_array_dict = {'m': state.moments[0], 'v': state.moments[1]}   # shard-sized under DP
             elif self.opt_kind == 'momentum':
                 opt.params_whole_array_dict = {'v': state.moments[0]}
+        elif self.opt_kind == 'cg':
+            # the two state arrays are the run's moment buffers: checkpoints and a resume carry them like Adam's m and v
+            opt.whole_object_size, opt.ctx = [*obj_size, 2], ctx
+            opt.params_whole_array_dict = {'descent_dir_old': state.moments[0], 's': state.moments[1]}
         else:
             opt.create_container([*obj_size, 2], self.use_checkpoint, ctx)
         obj = self.obj = ObjectFunction([*obj_size, 2], distribution_mode=self.distribution_mode, output_folder=self.output_folder,
@@ -772,6 +797,8 @@ class _Run(object):
             self.forward_model = self.forward_model(**fm_args)
         fm = self.forward_model
         self.builtin_model = type(fm) in (PtychographyModel, MultiDistModel, SparseMultisliceModel)
+        if self.opt_kind == 'cg':
+            self.gradient.forward_model = fm        # the line search takes its loss function from there (optimizers.py:644-652)
         self.rool = bool(self.rotate_out_of_loop) and not self.two_d_mode and not self.is_multi_dist
         if self.rool:
             _not_implemented(not isinstance(fm, PtychographyModel), 'rotate_out_of_loop with a user-defined forward model')

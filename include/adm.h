@@ -601,6 +601,33 @@ int adm_gd_step(adm_ctx* ctx, float* x, const float* g, size_t lo, size_t hi, do
 /* MomentumOptimizer.apply_gradient (adorym/optimizers.py:376-411): v = gamma*v + step*g; x = x - v; + constraints */
 int adm_momentum_step(adm_ctx* ctx, float* x, const float* g, float* v, size_t lo, size_t hi, double step_size, double gamma,
                       int flags, const float* mask);
+/* CGOptimizer.apply_gradient (adorym/optimizers.py:594-704, adorym/linesearch.py): the device side of one update of a flat float32
+ * array of n >= 1 elements (g gradient, d_old and s the optimiser's two state arrays, x the unknowns).  No pointer needs more than
+ * 4-byte alignment; 16-byte accesses are used when every array of a call is 16-byte aligned.
+ *   adm_cg_beta       A = sum d (d - d_old), B = sum d_old^2 with d = -g;  beta = max(A / B, 0) when i_batch > 0 and B > 0, else 0
+ *                     (the reference divides by B = 0).  beta stays on the device for adm_cg_direction: no host round trip between.
+ *   adm_cg_direction  s <- d + beta s, d_old <- d, and in the same pass C = sum s_new g (the descent check and df0),
+ *                     E = sum s_new^2 (the norm of the direction), D = sum g^2.
+ *   adm_cg_fallback   s <- -g: called by the host when C >= 0; then df0 = -D and the norm is sqrt(D).
+ *   adm_cg_trial      x_trial <- x0 + alpha s, a trial point of the line search (unconstrained, like the reference's).
+ *   adm_cg_accept     x[i] <- constrain(x_src[i]) for i in [lo, hi): flags and mask as in adm_adam_step, the channel is the parity
+ *                     of i and the mask entry i / 2.  x_src may be x (a failed search: only the constraints act).
+ * scratch: ADM_CG_SCRATCH_DOUBLES doubles on the device, the caller's; sums_host: 8 doubles of page-locked host memory
+ * (adm_host_alloc) that the finishing kernels write in place: [ADM_CG_SUM_A, _B, _BETA, _C, _E, _D], valid once the stream has
+ * reached that point.  Sums: products in double from the float inputs, fixed order, no atomics -- the same inputs give the same bits. */
+#define ADM_CG_MAX_BLOCKS 1024
+#define ADM_CG_SCRATCH_DOUBLES (3 * ADM_CG_MAX_BLOCKS + 8)
+#define ADM_CG_SUM_A 0
+#define ADM_CG_SUM_B 1
+#define ADM_CG_SUM_BETA 2
+#define ADM_CG_SUM_C 3
+#define ADM_CG_SUM_E 4
+#define ADM_CG_SUM_D 5
+int adm_cg_beta(adm_ctx* ctx, const float* g, const float* d_old, size_t n, int i_batch, double* scratch, double* sums_host);
+int adm_cg_direction(adm_ctx* ctx, const float* g, float* s, float* d_old, size_t n, double* scratch, double* sums_host);
+int adm_cg_fallback(adm_ctx* ctx, const float* g, float* s, size_t n);
+int adm_cg_trial(adm_ctx* ctx, const float* x0, const float* s, float alpha, float* x_trial, size_t n);
+int adm_cg_accept(adm_ctx* ctx, float* x, const float* x_src, size_t lo, size_t hi, int flags, const float* mask);
 /* Reweighted L1 (adorym/regularizers.py:49-84).  adm_rwl1_update: weight = max(obj) / (|obj| + 1e-4*mean(obj)) over both
  * channels jointly (adorym/ptychography.py:995-1000); scratch = device float[2*1024+2].  adm_reg_grad_weighted:
  * grad_obj += alpha_c * weight * sign(obj) / V, reg_value += alpha_d*mean(w_d|delta|) + alpha_b*mean(w_b|beta|).
