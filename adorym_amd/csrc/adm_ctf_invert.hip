@@ -7,7 +7,8 @@
 //     phase = Re IFFT2( sum_d w_d FFT2(I_d - 1) / (sum_d 2 w_d^2 + alpha) )
 // The data are used as given, no sqrt, no loss.  A batch of angles goes through one launch group.
 //
-// The line machinery is adm_line_fft.h (the set adm_holo_ctf.hip restates for itself).  Three launches per call, no atomics:
+// The line machinery is adm_line_fft.h, its host setup adm_line_host.h (both shared with adm_holo.hip and adm_holo_ctf.hip).  Three
+// launches per call, no atomics:
 //   I1  rows (b, d, y) : I_d row - 1 (imag = 0)   -> FFT_x                                              -> T1[b][d][kx][y]
 //   I2  lines (b, kx)  : per d: FFT_y -> F_d ; num += w_d F_d ; den += 2 w_d^2  (registers) ;
 //                        A = num / (den + alpha)  -> IFFT_y                                             -> T2[b][y][kx]
@@ -16,7 +17,7 @@
 #include <vector>
 #include <cmath>
 #include <cstring>
-#include "adm_host.h"
+#include "adm_line_host.h"
 #include "adm_line_fft.h"
 #include "adm_ms_math.h"
 
@@ -34,7 +35,7 @@ struct adm_ctfinv {
 namespace adm {
 namespace ctfinv {
 
-using namespace adm::linefft;
+using namespace linefft;
 
 struct InvArgs {
     const float *data, *uv2t, *alpha_t, *lg_kappa;  // data [nb][nd][ny][nx]; uv2t, alpha_t [nx][ny]
@@ -160,17 +161,13 @@ template <int NX> __global__ __launch_bounds__(256) void ctfinv_i3(InvArgs A) {
         for (int x = t; x < NX; x += LG::TPR) A.out[(row + x) * A.out_stride] = res[x].x * A.inv_n;
 }
 
-#define ADM_CTFINV_SIZES(X) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048)
-
-template <int N> static int blocks_for(int lines) { return (lines + LineGeo<N>::LPB - 1) / LineGeo<N>::LPB; }
-
 static hipError_t ctfinv_run(const InvArgs& A, hipStream_t st) {
 #define I1(N_) case N_: hipLaunchKernelGGL((ctfinv_i1<N_>), dim3(blocks_for<N_>(A.nb * A.nd * A.ny)), dim3(256), 0, st, A); break;
 #define I2(N_) case N_: hipLaunchKernelGGL((ctfinv_i2<N_>), dim3(blocks_for<N_>(A.nx), A.nb), dim3(256), 0, st, A); break;
 #define I3(N_) case N_: hipLaunchKernelGGL((ctfinv_i3<N_>), dim3(blocks_for<N_>(A.nb * A.ny)), dim3(256), 0, st, A); break;
-    switch (A.nx) { ADM_CTFINV_SIZES(I1) default: return hipErrorInvalidValue; }
-    switch (A.ny) { ADM_CTFINV_SIZES(I2) default: return hipErrorInvalidValue; }
-    switch (A.nx) { ADM_CTFINV_SIZES(I3) default: return hipErrorInvalidValue; }
+    switch (A.nx) { ADM_LINE_SIZES(I1) default: return hipErrorInvalidValue; }
+    switch (A.ny) { ADM_LINE_SIZES(I2) default: return hipErrorInvalidValue; }
+    switch (A.nx) { ADM_LINE_SIZES(I3) default: return hipErrorInvalidValue; }
 #undef I1
 #undef I2
 #undef I3
@@ -182,23 +179,10 @@ static hipError_t ctfinv_run(const InvArgs& A, hipStream_t st) {
 
 using namespace adm;
 
-static int ctfinv_upload_twiddles(adm_ctx* ctx, int N, float2** out) {
-    std::vector<float2> t(N);
-    for (int j = 0; j < N; ++j) {
-        const double a = -2.0 * M_PI * (double)j / (double)N;
-        t[j] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    int rc = adm_malloc(ctx, N * sizeof(float2), (void**)out);
-    if (rc) return rc;
-    return adm_h2d(ctx, *out, t.data(), N * sizeof(float2));
-}
-
-static bool ctfinv_side_ok(int n) { return n >= 16 && n <= 2048 && (n & (n - 1)) == 0; }
-
 extern "C" int adm_ctfinv_create(adm_ctx* ctx, const adm_ctfinv_desc* desc, const float* alpha_host, adm_ctfinv** out) {
     if (!ctx || !desc || !out) return fail(ADM_ERR_INVALID, "adm_ctfinv_create: null argument");
     const adm_ctfinv_desc& d = *desc;
-    if (!ctfinv_side_ok(d.ny) || !ctfinv_side_ok(d.nx))
+    if (!line_side_ok(d.ny) || !line_side_ok(d.nx))
         return fail(ADM_ERR_UNSUPPORTED, "adm_ctfinv_create: field sizes must be powers of two in [16, 2048]");
     if (d.n_dists < 1 || d.n_dists > ADM_CTFINV_MAX_DISTS) return fail(ADM_ERR_INVALID, "adm_ctfinv_create: n_dists must be in [1, 64]");
     if (d.max_batch < 1) return fail(ADM_ERR_INVALID, "adm_ctfinv_create: max_batch must be at least 1");
@@ -221,23 +205,9 @@ extern "C" int adm_ctfinv_create(adm_ctx* ctx, const adm_ctfinv_desc* desc, cons
     h->ctx = ctx;
     h->d = d;
     const double voxel_nm = d.psize_cm * 1e7;
-    int rc = ctfinv_upload_twiddles(ctx, d.ny, &h->tw_y);
-    if (!rc) rc = ctfinv_upload_twiddles(ctx, d.nx, &h->tw_x);
-    if (!rc) {
-        // gen_freq_mesh (adorym/propagate.py:54-60): u along y, v along x; cast to fp32 before squaring like the tensors
-        std::vector<float> uv(n);
-        for (int y = 0; y < d.ny; ++y) {
-            const int ky = y < (d.ny + 1) / 2 ? y : y - d.ny;
-            const float u = (float)(((double)ky / d.ny) / voxel_nm);
-            for (int x = 0; x < d.nx; ++x) {
-                const int kx = x < (d.nx + 1) / 2 ? x : x - d.nx;
-                const float v = (float)(((double)kx / d.nx) / voxel_nm);
-                uv[(size_t)x * d.ny + y] = u * u + v * v;
-            }
-        }
-        rc = adm_malloc(ctx, n * sizeof(float), (void**)&h->uv2t);
-        if (!rc) rc = adm_h2d(ctx, h->uv2t, uv.data(), n * sizeof(float));
-    }
+    int rc = line_upload_twiddles(ctx, d.ny, &h->tw_y);
+    if (!rc) rc = line_upload_twiddles(ctx, d.nx, &h->tw_x);
+    if (!rc) rc = line_upload_uv2t(ctx, d.ny, d.nx, voxel_nm, voxel_nm, &h->uv2t);
     if (!rc) rc = adm_malloc(ctx, n * sizeof(float), (void**)&h->alpha_t);
     if (!rc) rc = adm_h2d(ctx, h->alpha_t, al.data(), n * sizeof(float));
     if (!rc) rc = adm_malloc(ctx, n * d.n_dists * d.max_batch * sizeof(float2), (void**)&h->T1);

@@ -11,13 +11,14 @@
 // The fields are far larger than the LDS-resident tiles of the multislice kernel (512^2 * 8 B = 2 MB), so the 2-D transforms
 // run as line transforms (Stockham radix-8/4/2 in LDS, lines of N = 16 ... 2048) with transposed stores between the x and the y
 // stage.  All traffic stays in L2 / Infinity Cache at these sizes; the path is bound by launch latency, so the element-wise
-// stages are fused into the transforms: five kernels per minibatch (below).
+// stages are fused into the transforms: five kernels per minibatch (below).  The line machinery itself -- the passes, LineGeo, the
+// transposed store, the twiddle copy, the sums over a line -- is adm_line_fft.h, its host setup adm_line_host.h.
 #include <vector>
 #include <cmath>
 #include <cstring>
-#include "adm_host.h"
+#include "adm_line_host.h"
 #include "adm_optim.h"
-#include "adm_fft.h"
+#include "adm_line_fft.h"
 #include "adm_ms_math.h"
 
 struct adm_holo {
@@ -42,62 +43,13 @@ struct adm_holo {
 
 namespace adm {
 
-// ---------------------------------------------------------------------------------------------------------------
-// batched row FFT with transposed store
-// ---------------------------------------------------------------------------------------------------------------
-template <int N, int NS, int R, bool INV, int TPR>
-__device__ __forceinline__ void stockham_pass(const cf* __restrict__ src, cf* __restrict__ dst, const float2* __restrict__ tw, int t) {
-    constexpr int NB = N / R;                 // butterflies per row
-    constexpr int TWS = N / (NS * R);         // twiddle table stride
-    for (int j = t; j < NB; j += TPR) {
-        const int k = j % NS;
-        cf v[R];
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            v[q] = src[j + q * NB];
-            if (NS > 1 && q > 0) {
-                const cf w = tw[q * k * TWS];
-                v[q] = INV ? cmulc(v[q], w) : cmul(v[q], w);
-            }
-        }
-        Dft<R, INV>::run(v);
-        const int j0 = (j / NS) * NS * R + k;
-#pragma unroll
-        for (int q = 0; q < R; ++q) dst[j0 + q * NS] = v[q];
-    }
-}
-
-// The TPR threads of a line are one wave or part of one when TPR <= 64 (lines of up to 512 points): LDS operations of a wave
-// execute in order, so ordering the compiler is all a line-local exchange needs -- no workgroup barrier between the passes of a
-// transform, the four lines of a block run at their own pace.  Longer lines span two or four waves and keep the barrier.
-template <int TPR> __device__ __forceinline__ void line_sync() {
-    if (TPR <= 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-template <int N, int NS, bool INV, int TPR> struct Passes {
-    static __device__ __forceinline__ int run(cf* a, cf* b, const float2* tw, int t) {
-        constexpr int REM = N / NS;
-        constexpr int R = REM >= 8 ? 8 : REM;
-        stockham_pass<N, NS, R, INV, TPR>(a, b, tw, t);
-        line_sync<TPR>();
-        return 1 + Passes<N, NS * R, INV, TPR>::run(b, a, tw, t);
-    }
-};
-template <int N, bool INV, int TPR> struct Passes<N, N, INV, TPR> {
-    static __device__ __forceinline__ int run(cf*, cf*, const float2*, int) { return 0; }
-};
+using namespace linefft;
 
 // ---------------------------------------------------------------------------------------------------------------
 // Five kernels per minibatch.  Every stage is "lines of length N through LDS": a block of 256 threads works on LPB = 256 / (N / 8)
-// lines at once (N / 8 threads per line, Stockham passes above), and everything element-wise -- slice modulation, transfer
-// functions of all distances, loss and its derivative, the sums over distances, the object / probe gradient -- runs on the line
-// while it is in LDS, between two transforms:
+// lines at once (N / 8 threads per line, the Stockham passes of adm_line_fft.h), and everything element-wise -- slice modulation,
+// transfer functions of all distances, loss and its derivative, the sums over distances, the object / probe gradient -- runs on
+// the line while it is in LDS, between two transforms:
 //   K1  rows y      : psi = probe * c(obj)                      -> FFT_x                       -> T1[kx][y]
 //   K2  lines kx    : FFT_y -> F (kept: Ft[kx][ky])  ; per d: x H_d -> IFFT_y                  -> Wq[d][y][kx]
 //   K3  rows (d, y) : IFFT_x / n -> Psi_d, loss, affine-gradient sums, dL/dPsi -> FFT_x        -> T3[d][kx][y]
@@ -107,58 +59,12 @@ template <int N, bool INV, int TPR> struct Passes<N, N, INV, TPR> {
 // Partial sums: one slot per line (K3: per (d, y), 8 floats; K4: per (d, kx)), summed by K5's block 0 -- or by
 // holo_sums_kernel when no gradient is wanted -- in a fixed order: bit-reproducible.
 // ---------------------------------------------------------------------------------------------------------------
-template <int N> struct LineGeo {
-    static constexpr int TPR = N / 8;             // threads per line
-    static constexpr int LPB = 256 / TPR;         // lines per block
-    // pitch of a line's LDS buffer: N + 32 / min(LPB, 32) elements, so that the block-wide transposed read of
-    // store_lines_transposed (a half wave = min(LPB, 32) lines x 32 / min(LPB, 32) consecutive points) touches 32 different
-    // 8-byte bank pairs
-    static constexpr int LP = N + (LPB > 1 ? 32 / (LPB < 32 ? LPB : 32) : 0);
-};
-
-// The x and y stages of a 2-D transform hand their results over transposed.  A line's own threads would store its points 8 bytes
-// at a time, pitch * 8 bytes apart: one L2 write transaction per point (1 M of them per K2 / K3 launch at 512 x 512 x 4 -- the
-// store-ablated build of round 6 is 15 us of 76 faster).  Instead the block stores its LPB adjacent lines together: thread e writes
-// point e / LPB of line e % LPB, so LPB consecutive lanes fill LPB * 8 contiguous bytes (32 B at N = 512: a quarter of the
-// transactions).  `base`: LDS address of line 0's result (all lines of a block finish in the same buffer); at(r, c): destination
-// of point r of line c.
-template <int N, typename At> __device__ __forceinline__ void store_lines_transposed(const cf* base, int n_lines, At at) {
-    using LG = LineGeo<N>;
-    __syncthreads();                               // every line of the block is complete
-    for (int e = threadIdx.x; e < N * LG::LPB; e += 256) {
-        const int c = e % LG::LPB, r = e / LG::LPB;
-        if (c < n_lines) *at(r, c) = base[c * LG::LP + r];
-    }
-}
-// The passes read 7 twiddles per butterfly: from an LDS copy of the table (N <= 1024; the caller's next barrier orders the copy
-// before the first pass), from global memory otherwise (the line buffers of N = 2048 leave no room).
-template <int N> struct TwLds {
-    static constexpr bool USE = (N <= 1024);
-    static constexpr int SIZE = USE ? N : 1;
-};
-template <int N> __device__ __forceinline__ const float2* stage_twiddles(float2* lds, const float2* __restrict__ tw) {
-    if (!TwLds<N>::USE) return tw;
-    for (int j = threadIdx.x; j < N; j += 256) lds[j] = tw[j];
-    return lds;
-}
-// transform the line in `a` (filled, block synchronised); returns the buffer that holds the result (block synchronised)
-template <int N, bool INV> __device__ __forceinline__ cf* line_fft(cf* a, cf* b, const float2* __restrict__ tw, int t) {
-    const int np = Passes<N, 1, INV, LineGeo<N>::TPR>::run(a, b, tw, t);
-    return (np & 1) ? b : a;
-}
-
 __device__ __forceinline__ cf holo_transmission(float2 o, int real_imag, float k1, float sigma) {
     if (real_imag) return o;
     const float e = expf(-k1 * o.y);
     float sn, cs;
     sincosf(-sigma * k1 * o.x, &sn, &cs);
     return make_float2(e * cs, e * sn);
-}
-// a * b rounded on its own: with contraction off the product cannot merge with a following addition into one fused multiply-add,
-// so that `old + mul_rounded(a, b)` adds the very float an overwriting launch stores (accumulated = seeded + overwritten, bit for bit)
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
 }
 __device__ __forceinline__ cf holo_h(float uv2, float dist_cm, float c1) {
     // -sigma*PI*lambda (c1, rounded once on the host) * dist_nm * (u^2+v^2), every product in fp32 like the reference
@@ -210,55 +116,6 @@ struct HoloArgs {
     AdamScalars adam;                               // step of the object; the other two step sizes below
     float step_d, step_a;
 };
-
-// sum of v over the TPR threads of a line group (TPR a power of two <= 256); every thread of the block calls it.  A line of up to
-// 64 threads is (part of) one wave: a fixed shuffle tree, no LDS, no workgroup barrier (the lines of a block stay independent);
-// longer lines go through red ([256] floats of LDS).  Either way the order of the additions is fixed: bit-reproducible.
-template <int TPR> __device__ __forceinline__ float line_sum(float v, float* red) {
-    if (TPR <= 64) {
-#pragma unroll
-        for (int s = TPR / 2; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-        return v;
-    }
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = TPR / 2; s > 0; s >>= 1) {
-        if ((tid % TPR) < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const float r = red[tid - tid % TPR];
-    __syncthreads();
-    return r;
-}
-
-// the same for Q quantities at once (one set of barriers); red: [Q][256]
-template <int TPR, int Q> __device__ __forceinline__ void line_sums(float (&v)[Q], float (*red)[256]) {
-    if (TPR <= 64) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-#pragma unroll
-            for (int s = TPR / 2; s > 0; s >>= 1) v[q] += __shfl_xor(v[q], s, 64);
-        }
-        return;
-    }
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) red[q][tid] = v[q];
-    __syncthreads();
-#pragma unroll
-    for (int s = TPR / 2; s > 0; s >>= 1) {
-        if ((tid % TPR) < s) {
-#pragma unroll
-            for (int q = 0; q < Q; ++q) red[q][tid] += red[q][tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < Q; ++q) v[q] = red[q][tid - tid % TPR];
-    __syncthreads();
-}
 
 template <int NX> __global__ __launch_bounds__(256) void holo_k1(HoloArgs A) {
     using LG = LineGeo<NX>;
@@ -585,7 +442,6 @@ template <int NX, bool FUSE> __global__ __launch_bounds__(256) void holo_k5(Holo
         for (int o = blockIdx.x; o < A.nd * 8; o += gridDim.x) holo_sum_one<FUSE>(A, true, o);
 }
 
-#define ADM_HOLO_SIZES(X) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048)
 // ---------------------------------------------------------------------------------------------------------------
 // Per-distance shift refinement of the measured holograms (optimize_all_probe_pos with multi-distance data,
 // adorym/forward_model.py:1075-1085; demos/2d_multidist_holography_w_position_correction.py): the loss compares with
@@ -734,8 +590,6 @@ template <int NX> __global__ __launch_bounds__(256) void holo_sri(ShiftArgs A) {
         for (int x = t; x < NX; x += LG::TPR) A.out[row + x] = res[x].x * A.inv_n;
 }
 
-template <int N> static int blocks_for(int lines) { return (lines + LineGeo<N>::LPB - 1) / LineGeo<N>::LPB; }
-
 static hipError_t holo_run(const HoloArgs& A, bool want_grad, hipStream_t st, bool fuse = false) {
 #define K_X(KERNEL, N_, LINES) case N_: hipLaunchKernelGGL((KERNEL<N_>), dim3(blocks_for<N_>(LINES)), dim3(256), 0, st, A); break;
 #define K1(N_) K_X(holo_k1, N_, A.ny)
@@ -745,14 +599,14 @@ static hipError_t holo_run(const HoloArgs& A, bool want_grad, hipStream_t st, bo
                          else hipLaunchKernelGGL((holo_k5<N_, false>), dim3(blocks_for<N_>(A.ny)), dim3(256), 0, st, A); break;
 #define K3G(N_) case N_: hipLaunchKernelGGL((holo_k3<N_, true>), dim3(blocks_for<N_>(A.nd * A.ny)), dim3(256), 0, st, A); break;
 #define K3N(N_) case N_: hipLaunchKernelGGL((holo_k3<N_, false>), dim3(blocks_for<N_>(A.nd * A.ny)), dim3(256), 0, st, A); break;
-    switch (A.nx) { ADM_HOLO_SIZES(K1) default: return hipErrorInvalidValue; }
-    switch (A.ny) { ADM_HOLO_SIZES(K2) default: return hipErrorInvalidValue; }
+    switch (A.nx) { ADM_LINE_SIZES(K1) default: return hipErrorInvalidValue; }
+    switch (A.ny) { ADM_LINE_SIZES(K2) default: return hipErrorInvalidValue; }
     if (want_grad) {
-        switch (A.nx) { ADM_HOLO_SIZES(K3G) default: return hipErrorInvalidValue; }
-        switch (A.ny) { ADM_HOLO_SIZES(K4) default: return hipErrorInvalidValue; }
-        switch (A.nx) { ADM_HOLO_SIZES(K5) default: return hipErrorInvalidValue; }
+        switch (A.nx) { ADM_LINE_SIZES(K3G) default: return hipErrorInvalidValue; }
+        switch (A.ny) { ADM_LINE_SIZES(K4) default: return hipErrorInvalidValue; }
+        switch (A.nx) { ADM_LINE_SIZES(K5) default: return hipErrorInvalidValue; }
     } else {
-        switch (A.nx) { ADM_HOLO_SIZES(K3N) default: return hipErrorInvalidValue; }
+        switch (A.nx) { ADM_LINE_SIZES(K3N) default: return hipErrorInvalidValue; }
         hipLaunchKernelGGL(holo_sums_kernel, dim3(A.nd * 8), dim3(64), 0, st, A);
     }
 #undef K_X
@@ -769,23 +623,10 @@ static hipError_t holo_run(const HoloArgs& A, bool want_grad, hipStream_t st, bo
 
 using namespace adm;
 
-static int upload_twiddles(adm_ctx* ctx, int N, float2** out) {
-    std::vector<float2> t(N);
-    for (int j = 0; j < N; ++j) {
-        const double a = -2.0 * M_PI * (double)j / (double)N;
-        t[j] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    int rc = adm_malloc(ctx, N * sizeof(float2), (void**)out);
-    if (rc) return rc;
-    return adm_h2d(ctx, *out, t.data(), N * sizeof(float2));
-}
-
-static bool pow2_in_range(int n) { return n >= 16 && n <= 2048 && (n & (n - 1)) == 0; }
-
 extern "C" int adm_holo_create(adm_ctx* ctx, const adm_holo_desc* desc, adm_holo** out) {
     if (!ctx || !desc || !out) return fail(ADM_ERR_INVALID, "adm_holo_create: null argument");
     const adm_holo_desc& d = *desc;
-    if (!pow2_in_range(d.ny) || !pow2_in_range(d.nx))
+    if (!line_side_ok(d.ny) || !line_side_ok(d.nx))
         return fail(ADM_ERR_UNSUPPORTED, "adm_holo_create: field sizes must be powers of two in [16, 2048]");
     if (d.n_dists < 1 || d.n_dists > 64) return fail(ADM_ERR_INVALID, "adm_holo_create: n_dists must be in [1, 64]");
     if (d.sign_convention != 1 && d.sign_convention != -1) return fail(ADM_ERR_INVALID, "adm_holo_create: sign_convention must be +-1");
@@ -794,23 +635,9 @@ extern "C" int adm_holo_create(adm_ctx* ctx, const adm_holo_desc* desc, adm_holo
     h->ctx = ctx;
     h->d = d;
     const size_t n = (size_t)d.ny * d.nx;
-    int rc = upload_twiddles(ctx, d.ny, &h->tw_y);
-    if (!rc) rc = upload_twiddles(ctx, d.nx, &h->tw_x);
-    if (!rc) {
-        // gen_freq_mesh (adorym/propagate.py:54-60): u along y, v along x; cast to fp32 before squaring like the tensors
-        std::vector<float> uv(n);
-        for (int y = 0; y < d.ny; ++y) {
-            const int ky = y < (d.ny + 1) / 2 ? y : y - d.ny;
-            const float u = (float)(((double)ky / d.ny) / d.voxel_nm_y);
-            for (int x = 0; x < d.nx; ++x) {
-                const int kx = x < (d.nx + 1) / 2 ? x : x - d.nx;
-                const float v = (float)(((double)kx / d.nx) / d.voxel_nm_x);
-                uv[(size_t)x * d.ny + y] = u * u + v * v;
-            }
-        }
-        rc = adm_malloc(ctx, n * sizeof(float), (void**)&h->uv2t);
-        if (!rc) rc = adm_h2d(ctx, h->uv2t, uv.data(), n * sizeof(float));
-    }
+    int rc = line_upload_twiddles(ctx, d.ny, &h->tw_y);
+    if (!rc) rc = line_upload_twiddles(ctx, d.nx, &h->tw_x);
+    if (!rc) rc = line_upload_uv2t(ctx, d.ny, d.nx, d.voxel_nm_y, d.voxel_nm_x, &h->uv2t);
     if (!rc) rc = adm_malloc(ctx, n * sizeof(float2), (void**)&h->T14);
     if (!rc) rc = adm_malloc(ctx, n * sizeof(float2), (void**)&h->Ft);
     if (!rc) rc = adm_malloc(ctx, n * d.n_dists * sizeof(float2), (void**)&h->Wq);
@@ -910,25 +737,25 @@ static void shift_args(const adm_holo* h, ShiftArgs& S) {
 }
 static hipError_t launch_sr(const ShiftArgs& S, hipStream_t st) {
 #define X(N_) case N_: hipLaunchKernelGGL((holo_sr<N_>), dim3(blocks_for<N_>(S.ny), S.nd), dim3(256), 0, st, S); break;
-    switch (S.nx) { ADM_HOLO_SIZES(X) default: return hipErrorInvalidValue; }
+    switch (S.nx) { ADM_LINE_SIZES(X) default: return hipErrorInvalidValue; }
 #undef X
     return hipGetLastError();
 }
 template <int MODE> static hipError_t launch_slf(const ShiftArgs& S, hipStream_t st) {
 #define X(N_) case N_: hipLaunchKernelGGL((holo_slf<N_, MODE>), dim3(blocks_for<N_>(S.nx), S.nd), dim3(256), 0, st, S); break;
-    switch (S.ny) { ADM_HOLO_SIZES(X) default: return hipErrorInvalidValue; }
+    switch (S.ny) { ADM_LINE_SIZES(X) default: return hipErrorInvalidValue; }
 #undef X
     return hipGetLastError();
 }
 static hipError_t launch_sli(const ShiftArgs& S, hipStream_t st) {
 #define X(N_) case N_: hipLaunchKernelGGL((holo_sli<N_>), dim3(blocks_for<N_>(S.nx), S.nd), dim3(256), 0, st, S); break;
-    switch (S.ny) { ADM_HOLO_SIZES(X) default: return hipErrorInvalidValue; }
+    switch (S.ny) { ADM_LINE_SIZES(X) default: return hipErrorInvalidValue; }
 #undef X
     return hipGetLastError();
 }
 static hipError_t launch_sri(const ShiftArgs& S, hipStream_t st) {
 #define X(N_) case N_: hipLaunchKernelGGL((holo_sri<N_>), dim3(blocks_for<N_>(S.ny), S.nd), dim3(256), 0, st, S); break;
-    switch (S.nx) { ADM_HOLO_SIZES(X) default: return hipErrorInvalidValue; }
+    switch (S.nx) { ADM_LINE_SIZES(X) default: return hipErrorInvalidValue; }
 #undef X
     return hipGetLastError();
 }

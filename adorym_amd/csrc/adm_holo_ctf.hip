@@ -14,9 +14,9 @@
 //     dL/dd_d [per cm] = (2 PI lambda_nm 1e7 / n)  Re sum_k conj(Q_d) (cos xi_d - sin xi_d / kappa) (u^2 + v^2) F
 // A pixel with I_d <= 0 predicts 0 and contributes to no gradient (the reference's autograd returns NaN everywhere then).
 //
-// The line machinery -- Stockham passes in LDS, LineGeo, the block-cooperative transposed stores, the LDS twiddle copy -- is the
-// one of adm_holo.hip, restated here: tests/test_holo_matrix_coverage.py pins the text of that file, so it cannot be moved into a
-// header both include.  Five launches per minibatch, like the Fresnel path:
+// The line machinery -- Stockham passes in LDS, LineGeo, the block-cooperative transposed stores, the LDS twiddle copy, the sums
+// over a line -- is adm_line_fft.h, shared with adm_holo.hip and adm_ctf_invert.hip; its host setup is adm_line_host.h (DESIGN.md
+// section 4).  Five launches per minibatch, like the Fresnel path:
 //   C1  rows y      : D row (imag = 0)               -> FFT_x                                    -> T1[kx][y]
 //   C2  lines kx    : FFT_y -> F (kept: Ft[kx][ky]) ; per d: x osc_d -> IFFT_y                   -> W[d][y][kx]
 //   C3  rows (d, y) : IFFT_x / n -> I_d, pred_d, loss partial, q_d -> FFT_x                      -> T3[d][kx][y]
@@ -35,7 +35,8 @@
 #include <cmath>
 #include <cstring>
 #include "adm_ctf_group.h"
-#include "adm_fft.h"
+#include "adm_line_host.h"
+#include "adm_line_fft.h"
 #include "adm_ms_math.h"
 
 #define ADM_CTF_MAX_DISTS 64
@@ -43,87 +44,7 @@
 namespace adm {
 namespace ctf {
 
-template <int N, int NS, int R, bool INV, int TPR>
-__device__ __forceinline__ void stockham_pass(const cf* __restrict__ src, cf* __restrict__ dst, const float2* __restrict__ tw, int t) {
-    constexpr int NB = N / R;                 // butterflies per row
-    constexpr int TWS = N / (NS * R);         // twiddle table stride
-    for (int j = t; j < NB; j += TPR) {
-        const int k = j % NS;
-        cf v[R];
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            v[q] = src[j + q * NB];
-            if (NS > 1 && q > 0) {
-                const cf w = tw[q * k * TWS];
-                v[q] = INV ? cmulc(v[q], w) : cmul(v[q], w);
-            }
-        }
-        Dft<R, INV>::run(v);
-        const int j0 = (j / NS) * NS * R + k;
-#pragma unroll
-        for (int q = 0; q < R; ++q) dst[j0 + q * NS] = v[q];
-    }
-}
-
-// lines of up to 64 threads are (part of) one wave: ordering the compiler is all a line-local exchange needs
-template <int TPR> __device__ __forceinline__ void line_sync() {
-    if (TPR <= 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-template <int N, int NS, bool INV, int TPR> struct Passes {
-    static __device__ __forceinline__ int run(cf* a, cf* b, const float2* tw, int t) {
-        constexpr int REM = N / NS;
-        constexpr int R = REM >= 8 ? 8 : REM;
-        stockham_pass<N, NS, R, INV, TPR>(a, b, tw, t);
-        line_sync<TPR>();
-        return 1 + Passes<N, NS * R, INV, TPR>::run(b, a, tw, t);
-    }
-};
-template <int N, bool INV, int TPR> struct Passes<N, N, INV, TPR> {
-    static __device__ __forceinline__ int run(cf*, cf*, const float2*, int) { return 0; }
-};
-
-template <int N> struct LineGeo {
-    static constexpr int TPR = N / 8;             // threads per line
-    static constexpr int LPB = 256 / TPR;         // lines per block
-    static constexpr int LP = N + (LPB > 1 ? 32 / (LPB < 32 ? LPB : 32) : 0);      // LDS pitch of a line (bank spread of the transposed read)
-};
-
-// the block stores its LPB adjacent lines together: thread e writes point e / LPB of line e % LPB
-template <int N, typename At> __device__ __forceinline__ void store_lines_transposed(const cf* base, int n_lines, At at) {
-    using LG = LineGeo<N>;
-    __syncthreads();                               // every line of the block is complete
-    for (int e = threadIdx.x; e < N * LG::LPB; e += 256) {
-        const int c = e % LG::LPB, r = e / LG::LPB;
-        if (c < n_lines) *at(r, c) = base[c * LG::LP + r];
-    }
-}
-template <int N> struct TwLds {
-    static constexpr bool USE = (N <= 1024);
-    static constexpr int SIZE = USE ? N : 1;
-};
-template <int N> __device__ __forceinline__ const float2* stage_twiddles(float2* lds, const float2* __restrict__ tw) {
-    if (!TwLds<N>::USE) return tw;
-    for (int j = threadIdx.x; j < N; j += 256) lds[j] = tw[j];
-    return lds;
-}
-// transform the line in `a` (filled, block synchronised); returns the buffer that holds the result
-template <int N, bool INV> __device__ __forceinline__ cf* line_fft(cf* a, cf* b, const float2* __restrict__ tw, int t) {
-    const int np = Passes<N, 1, INV, LineGeo<N>::TPR>::run(a, b, tw, t);
-    return (np & 1) ? b : a;
-}
-
-// a * b rounded on its own, so that `old + mul_rounded(a, b)` adds the very float an overwriting launch stores
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
+using namespace linefft;
 
 struct CtfArgs {
     const float2* obj;                              // [ny][nx] (delta, beta)
@@ -161,27 +82,6 @@ __device__ __forceinline__ void stage_inv_kappa(float* slot, const float* lg_kap
 // sine and cosine of xi_d = c_d (u^2 + v^2), the product in fp32 like the reference's tensors
 __device__ __forceinline__ void ctf_sincos(float uv2, float c, float& sn, float& cs) { sincos_fast(c * uv2, sn, cs); }
 __device__ __forceinline__ float ctf_osc(float sn, float cs, float inv_kappa) { return 2.f * (sn + inv_kappa * cs); }
-
-// the sum over the TPR threads of a line in a fixed tree: shuffles inside a wave, through `red` (256 entries, free again when the
-// call returns) for lines of several waves; float for the loss, double for the distance gradient
-template <int TPR, typename T> __device__ __forceinline__ T line_sum(T v, T* red) {
-    if (TPR <= 64) {
-#pragma unroll
-        for (int s = TPR / 2; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-        return v;
-    }
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = TPR / 2; s > 0; s >>= 1) {
-        if ((tid % TPR) < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const T r = red[tid - tid % TPR];
-    __syncthreads();
-    return r;
-}
 
 template <int NX> __global__ __launch_bounds__(256) void ctf_c1(CtfArgs A) {
     using LG = LineGeo<NX>;
@@ -455,10 +355,6 @@ template <int NX> __global__ __launch_bounds__(256) void ctf_c5(CtfArgs A) {
     }
 }
 
-#define ADM_CTF_SIZES(X) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048)
-
-template <int N> static int blocks_for(int lines) { return (lines + LineGeo<N>::LPB - 1) / LineGeo<N>::LPB; }
-
 static hipError_t ctf_run(const CtfArgs& A, bool want_grad, hipStream_t st) {
 #define C1(N_) case N_: hipLaunchKernelGGL((ctf_c1<N_>), dim3(blocks_for<N_>(A.ny)), dim3(256), 0, st, A); break;
 #define C2(N_) case N_: hipLaunchKernelGGL((ctf_c2<N_>), dim3(blocks_for<N_>(A.nx), A.nd), dim3(256), 0, st, A); break;
@@ -466,14 +362,14 @@ static hipError_t ctf_run(const CtfArgs& A, bool want_grad, hipStream_t st) {
 #define C3N(N_) case N_: hipLaunchKernelGGL((ctf_c3<N_, false>), dim3(blocks_for<N_>(A.nd * A.ny)), dim3(256), 0, st, A); break;
 #define C4(N_) case N_: hipLaunchKernelGGL((ctf_c4<N_>), dim3(A.nx), dim3(256), 0, st, A); break;
 #define C5(N_) case N_: hipLaunchKernelGGL((ctf_c5<N_>), dim3(blocks_for<N_>(A.ny)), dim3(256), 0, st, A); break;
-    switch (A.nx) { ADM_CTF_SIZES(C1) default: return hipErrorInvalidValue; }
-    switch (A.ny) { ADM_CTF_SIZES(C2) default: return hipErrorInvalidValue; }
+    switch (A.nx) { ADM_LINE_SIZES(C1) default: return hipErrorInvalidValue; }
+    switch (A.ny) { ADM_LINE_SIZES(C2) default: return hipErrorInvalidValue; }
     if (want_grad) {
-        switch (A.nx) { ADM_CTF_SIZES(C3G) default: return hipErrorInvalidValue; }
-        switch (A.ny) { ADM_CTF_SIZES(C4) default: return hipErrorInvalidValue; }
-        switch (A.nx) { ADM_CTF_SIZES(C5) default: return hipErrorInvalidValue; }
+        switch (A.nx) { ADM_LINE_SIZES(C3G) default: return hipErrorInvalidValue; }
+        switch (A.ny) { ADM_LINE_SIZES(C4) default: return hipErrorInvalidValue; }
+        switch (A.nx) { ADM_LINE_SIZES(C5) default: return hipErrorInvalidValue; }
     } else {
-        switch (A.nx) { ADM_CTF_SIZES(C3N) default: return hipErrorInvalidValue; }
+        switch (A.nx) { ADM_LINE_SIZES(C3N) default: return hipErrorInvalidValue; }
         hipLaunchKernelGGL(ctf_sums_kernel, dim3(A.nd), dim3(64), 0, st, A);
     }
 #undef C1
@@ -490,23 +386,10 @@ static hipError_t ctf_run(const CtfArgs& A, bool want_grad, hipStream_t st) {
 
 using namespace adm;
 
-static int ctf_upload_twiddles(adm_ctx* ctx, int N, float2** out) {
-    std::vector<float2> t(N);
-    for (int j = 0; j < N; ++j) {
-        const double a = -2.0 * M_PI * (double)j / (double)N;
-        t[j] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    int rc = adm_malloc(ctx, N * sizeof(float2), (void**)out);
-    if (rc) return rc;
-    return adm_h2d(ctx, *out, t.data(), N * sizeof(float2));
-}
-
-static bool ctf_side_ok(int n) { return n >= 16 && n <= 2048 && (n & (n - 1)) == 0; }
-
 extern "C" int adm_ctf_create(adm_ctx* ctx, const adm_ctf_desc* desc, adm_ctf** out) {
     if (!ctx || !desc || !out) return fail(ADM_ERR_INVALID, "adm_ctf_create: null argument");
     const adm_ctf_desc& d = *desc;
-    if (!ctf_side_ok(d.ny) || !ctf_side_ok(d.nx))
+    if (!line_side_ok(d.ny) || !line_side_ok(d.nx))
         return fail(ADM_ERR_UNSUPPORTED, "adm_ctf_create: field sizes must be powers of two in [16, 2048]");
     if (d.n_dists < 1 || d.n_dists > ADM_CTF_MAX_DISTS) return fail(ADM_ERR_UNSUPPORTED, "adm_ctf_create: n_dists must be in [1, 64]");
     if (!(d.energy_ev > 0.0) || !(d.psize_cm > 0.0)) return fail(ADM_ERR_INVALID, "adm_ctf_create: energy_ev and psize_cm must be positive");
@@ -516,23 +399,9 @@ extern "C" int adm_ctf_create(adm_ctx* ctx, const adm_ctf_desc* desc, adm_ctf** 
     h->d = d;
     const size_t n = (size_t)d.ny * d.nx;
     const double voxel_nm = d.psize_cm * 1e7;
-    int rc = ctf_upload_twiddles(ctx, d.ny, &h->tw_y);
-    if (!rc) rc = ctf_upload_twiddles(ctx, d.nx, &h->tw_x);
-    if (!rc) {
-        // gen_freq_mesh (adorym/propagate.py:54-60): u along y, v along x; cast to fp32 before squaring like the tensors
-        std::vector<float> uv(n);
-        for (int y = 0; y < d.ny; ++y) {
-            const int ky = y < (d.ny + 1) / 2 ? y : y - d.ny;
-            const float u = (float)(((double)ky / d.ny) / voxel_nm);
-            for (int x = 0; x < d.nx; ++x) {
-                const int kx = x < (d.nx + 1) / 2 ? x : x - d.nx;
-                const float v = (float)(((double)kx / d.nx) / voxel_nm);
-                uv[(size_t)x * d.ny + y] = u * u + v * v;
-            }
-        }
-        rc = adm_malloc(ctx, n * sizeof(float), (void**)&h->uv2t);
-        if (!rc) rc = adm_h2d(ctx, h->uv2t, uv.data(), n * sizeof(float));
-    }
+    int rc = line_upload_twiddles(ctx, d.ny, &h->tw_y);
+    if (!rc) rc = line_upload_twiddles(ctx, d.nx, &h->tw_x);
+    if (!rc) rc = line_upload_uv2t(ctx, d.ny, d.nx, voxel_nm, voxel_nm, &h->uv2t);
     if (!rc) rc = adm_malloc(ctx, n * sizeof(float2), (void**)&h->T14);
     if (!rc) rc = adm_malloc(ctx, n * sizeof(float2), (void**)&h->Ft);
     if (!rc) rc = adm_malloc(ctx, n * d.n_dists * sizeof(float2), (void**)&h->W);

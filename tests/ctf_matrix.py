@@ -1,6 +1,6 @@
 """Tables, mirrors and references of the CTF matrix (tests/test_gpu_ctf.py; importable without a GPU).
 
-adm_holo_ctf.hip compiles every line kernel for the eight line lengths of ADM_CTF_SIZES; the length that instantiates a kernel is
+adm_holo_ctf.hip compiles every line kernel for the eight line lengths of ADM_LINE_SIZES; the length that instantiates a kernel is
 the field's nx (rows: C1, C3, C5) or its ny (lines kx: C2, C4).  ``geometry`` restates the launch arithmetic (LineGeo, blocks_for,
 C3's jobs, C4's rounds, the outputs of ctf_sum_one), ``KERNELS`` and ``ENTRY_POINTS`` name every kernel family and entry point
 with the tests that run it, ``FIELDS`` the fields that put every length in both roles and reach every class of ``ALL_CLASSES``.

@@ -1,7 +1,7 @@
 """Tables, mirrors and references of the CTF inversion matrix (tests/test_gpu_ctfinv.py, tests/test_gpu_ctfinv_driver.py; importable
 without a GPU).
 
-adm_ctf_invert.hip compiles its three line kernels for the eight line lengths of ADM_CTFINV_SIZES; the length that instantiates
+adm_ctf_invert.hip compiles its three line kernels for the eight line lengths of ADM_LINE_SIZES; the length that instantiates
 a kernel is the field's nx (rows: I1, I3) or its ny (lines kx: I2).  ``geometry`` restates the launch arithmetic (LineGeo,
 blocks_for, I1's jobs (b, d, y), I2's grid (kx blocks, b), I3's jobs (b, y), the rounds of CTFInversion.retrieve), ``KERNELS`` and
 ``ENTRY_POINTS`` name every kernel family and entry point with the tests that run it, ``CASES`` the launches that put every length

@@ -1,6 +1,6 @@
 """Tables, mirrors and references of the holography matrix (tests/test_gpu_holo_matrix.py; importable without a GPU).
 
-adm_holo.hip compiles every line kernel for the eight line lengths of ADM_HOLO_SIZES; which length a kernel is instantiated by
+adm_holo.hip compiles every line kernel for the eight line lengths of ADM_LINE_SIZES; which length a kernel is instantiated by
 is the field's nx (rows: K1, K3, K5, SR, SRI) or its ny (lines kx: K2, K4, SLF, SLI).  ``line_geo`` / ``geometry`` restate the
 launch arithmetic (LineGeo, blocks_for, K3's jobs, K4's rounds), ``KERNELS`` names every instantiation family and the tests that
 run it, ``FIELDS`` is the smallest set of fields that puts every length in both roles and reaches every class of ``ALL_CLASSES``,

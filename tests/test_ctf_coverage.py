@@ -1,4 +1,5 @@
-"""CPU: the tables of tests/ctf_matrix.py against the text of adorym_amd/csrc/adm_holo_ctf.hip.  Fails when a __global__ kernel, an
+"""CPU: the tables of tests/ctf_matrix.py against the text of adorym_amd/csrc/adm_holo_ctf.hip and of the line machinery it includes
+(adm_line_fft.h, adm_line_host.h).  Fails when a __global__ kernel, an
 extern "C" entry point, an accepted size or a class of the mirror lacks a row or a test, or when the mirror's launch arithmetic
 no longer restates the source's."""
 import os
@@ -15,6 +16,8 @@ def _read(*p):
 
 
 SRC = _read('adorym_amd', 'csrc', 'adm_holo_ctf.hip')
+HDR = _read('adorym_amd', 'csrc', 'adm_line_fft.h')
+HOST = _read('adorym_amd', 'csrc', 'adm_line_host.h')
 CODE = re.sub(r'//[^\n]*', '', SRC)
 GPU_TESTS = set(re.findall(r'^def (test_\w+)\(', _read('tests', 'test_gpu_ctf.py'), re.M))
 
@@ -55,15 +58,17 @@ def test_every_entry_point_has_a_row():
 
 
 def test_every_accepted_size_is_launched_in_both_roles():
-    sizes = tuple(int(v) for v in re.findall(r'X\((\d+)\)', re.search(r'#define ADM_CTF_SIZES\(X\)([^\n]*)', SRC).group(1)))
+    sizes = tuple(int(v) for v in re.findall(r'X\((\d+)\)', re.search(r'#define ADM_LINE_SIZES\(X\)([^\n]*)', HDR).group(1)))
     assert sizes == CM.SIZES
     assert all(CM.pow2_in_range(n) for n in sizes) and not CM.pow2_in_range(sizes[0] // 2) and not CM.pow2_in_range(sizes[-1] * 2)
-    assert re.search(r'n >= 16 && n <= 2048 && \(n & \(n - 1\)\) == 0', SRC)
+    assert re.search(r'ADM_LINE_MIN_SIDE = 16, ADM_LINE_MAX_SIDE = 2048;', HOST)
+    assert re.search(r'n >= ADM_LINE_MIN_SIDE && n <= ADM_LINE_MAX_SIDE && \(n & \(n - 1\)\) == 0', HOST)
+    assert re.search(r'if \(!line_side_ok\(d\.ny\) \|\| !line_side_ok\(d\.nx\)\)', SRC)
     assert re.search(r'#define ADM_CTF_MAX_DISTS 64', SRC) and CM.MAX_DISTS == 64
     want = {(k, n) for k, (axis, _) in CM.KERNELS.items() for n in (sizes if axis else (0,))}
     assert CM.reached() == want, sorted(want - CM.reached())
     # every switch of ctf_run dispatches over the whole list
-    assert len(re.findall(r'ADM_CTF_SIZES\(C\w+\)', SRC)) == 6
+    assert len(re.findall(r'ADM_LINE_SIZES\(C\w+\)', SRC)) == 6
 
 
 def test_every_class_is_reached_and_every_field_is_small():
@@ -82,10 +87,10 @@ def test_every_class_is_reached_and_every_field_is_small():
 
 
 def test_the_mirror_restates_the_launch_arithmetic():
-    assert re.search(r'TPR = N / 8;', SRC) and re.search(r'LPB = 256 / TPR;', SRC)
-    assert re.search(r'LP = N \+ \(LPB > 1 \? 32 / \(LPB < 32 \? LPB : 32\) : 0\);', SRC)
-    assert re.search(r'USE = \(N <= 1024\);', SRC)
-    assert re.search(r'return \(lines \+ LineGeo<N>::LPB - 1\) / LineGeo<N>::LPB;', SRC)
+    assert re.search(r'TPR = N / 8;', HDR) and re.search(r'LPB = 256 / TPR;', HDR)
+    assert re.search(r'LP = N \+ \(LPB > 1 \? 32 / \(LPB < 32 \? LPB : 32\) : 0\);', HDR)
+    assert re.search(r'USE = \(N <= 1024\);', HDR)
+    assert re.search(r'return \(lines \+ LineGeo<N>::LPB - 1\) / LineGeo<N>::LPB;', HDR)
     launches = dict(re.findall(r'#define (C\w+)\(N_\) case N_: hipLaunchKernelGGL\(\(ctf_c\d<N_(?:, \w+)?>\), (dim3\(.*?\)), dim3\(256\)', SRC))
     assert launches == {'C1': 'dim3(blocks_for<N_>(A.ny))', 'C2': 'dim3(blocks_for<N_>(A.nx), A.nd)',
                         'C3G': 'dim3(blocks_for<N_>(A.nd * A.ny))', 'C3N': 'dim3(blocks_for<N_>(A.nd * A.ny))',

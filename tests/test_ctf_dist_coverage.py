@@ -28,7 +28,7 @@ def test_the_entry_point_has_a_row_a_declaration_and_a_binding():
     assert re.search(r'\badm_ctfd_fwd_adj\s*\(', header)
     assert "'adm_ctfd_fwd_adj'" in _read('adorym_amd', '_lib.py')
     assert 'adm_ctfd_fwd_adj' in _read('INTEGRATION.md')
-    # no kernel and no copy of the line machinery outside adm_holo_ctf.hip
+    # no kernel and no use of the line machinery (adm_line_fft.h) outside adm_holo_ctf.hip
     for n in ('adm_ctf_dist.hip', 'adm_ctf_group.h'):
         assert '__global__' not in SRC[n] and 'line_fft' not in SRC[n] and 'stockham' not in SRC[n], n
     from adorym_amd.csrc import build
@@ -67,6 +67,8 @@ def test_the_kernel_file_keeps_its_shape():
     code = re.sub(r'//[^\n]*', '', SRC['adm_holo_ctf.hip'])
     assert len(re.findall(r'__global__', code)) == 6
     assert len(re.findall(r'^extern "C"', SRC['adm_holo_ctf.hip'], re.M)) == 3
-    assert 'adm_line_fft.h' not in SRC['adm_holo_ctf.hip'] and 'adm_line_fft.h' not in SRC['adm_ctf_dist.hip']
+    # the line machinery is the header's, included by the kernel file alone of the three
+    assert '#include "adm_line_fft.h"' in SRC['adm_holo_ctf.hip'] and 'stockham' not in code
+    assert 'adm_line_fft.h' not in SRC['adm_ctf_dist.hip'] and 'adm_line_fft.h' not in SRC['adm_ctf_group.h']
     assert re.search(r'static_assert\(3 \* LG::LPB \* LG::LP \* sizeof\(cf\) \+ 256 \* sizeof\(double\)', SRC['adm_holo_ctf.hip'])
     assert not re.search(r'\batomic\w*\s*\(', code)          # every sum has a fixed order

@@ -1,4 +1,5 @@
-"""CPU: the tables of tests/ctfinv_matrix.py against the text of adorym_amd/csrc/adm_ctf_invert.hip and adm_line_fft.h.  Fails when a
+"""CPU: the tables of tests/ctfinv_matrix.py against the text of adorym_amd/csrc/adm_ctf_invert.hip and of the line machinery it
+includes (adm_line_fft.h, adm_line_host.h), and the layout of that machinery: one definition of each piece.  Fails when a
 __global__ kernel, an extern "C" entry point, an accepted size or a class of the mirror lacks a row or a test, or when the mirror's
 launch arithmetic no longer restates the source's."""
 import os
@@ -16,6 +17,7 @@ def _read(*p):
 
 SRC = _read('adorym_amd', 'csrc', 'adm_ctf_invert.hip')
 HDR = _read('adorym_amd', 'csrc', 'adm_line_fft.h')
+HOST = _read('adorym_amd', 'csrc', 'adm_line_host.h')
 CODE = re.sub(r'//[^\n]*', '', SRC)
 GPU_TESTS = set(re.findall(r'^def (test_\w+)\(', _read('tests', 'test_gpu_ctfinv.py'), re.M))
 
@@ -56,15 +58,17 @@ def test_every_entry_point_has_a_row():
 
 
 def test_every_accepted_size_is_launched_in_both_roles():
-    sizes = tuple(int(v) for v in re.findall(r'X\((\d+)\)', re.search(r'#define ADM_CTFINV_SIZES\(X\)([^\n]*)', SRC).group(1)))
+    sizes = tuple(int(v) for v in re.findall(r'X\((\d+)\)', re.search(r'#define ADM_LINE_SIZES\(X\)([^\n]*)', HDR).group(1)))
     assert sizes == M.SIZES
     assert all(M.pow2_in_range(n) for n in sizes) and not M.pow2_in_range(sizes[0] // 2) and not M.pow2_in_range(sizes[-1] * 2)
-    assert re.search(r'n >= 16 && n <= 2048 && \(n & \(n - 1\)\) == 0', SRC)
+    assert re.search(r'ADM_LINE_MIN_SIDE = 16, ADM_LINE_MAX_SIDE = 2048;', HOST)
+    assert re.search(r'n >= ADM_LINE_MIN_SIDE && n <= ADM_LINE_MAX_SIDE && \(n & \(n - 1\)\) == 0', HOST)
+    assert re.search(r'if \(!line_side_ok\(d\.ny\) \|\| !line_side_ok\(d\.nx\)\)', SRC)
     assert re.search(r'#define ADM_CTFINV_MAX_DISTS 64', SRC) and M.MAX_DISTS == 64
     want = {(k, n) for k in M.KERNELS for n in sizes}
     assert M.reached() == want, sorted(want - M.reached())
     # every switch of ctfinv_run dispatches over the whole list
-    assert len(re.findall(r'ADM_CTFINV_SIZES\(I\d\)', SRC)) == 3
+    assert len(re.findall(r'ADM_LINE_SIZES\(I\d\)', SRC)) == 3
 
 
 def test_every_class_is_reached_and_every_field_is_small():
@@ -92,7 +96,7 @@ def test_the_mirror_restates_the_launch_arithmetic():
     assert re.search(r'TPR = N / 8;', HDR) and re.search(r'LPB = 256 / TPR;', HDR)
     assert re.search(r'LP = N \+ \(LPB > 1 \? 32 / \(LPB < 32 \? LPB : 32\) : 0\);', HDR)
     assert re.search(r'USE = \(N <= 1024\);', HDR)
-    assert re.search(r'return \(lines \+ LineGeo<N>::LPB - 1\) / LineGeo<N>::LPB;', SRC)
+    assert re.search(r'return \(lines \+ LineGeo<N>::LPB - 1\) / LineGeo<N>::LPB;', HDR)
     launches = dict(re.findall(r'#define (I\d)\(N_\) case N_: hipLaunchKernelGGL\(\(ctfinv_i\d<N_>\), (dim3\(.*?\)), dim3\(256\)', SRC))
     assert launches == {'I1': 'dim3(blocks_for<N_>(A.nb * A.nd * A.ny))', 'I2': 'dim3(blocks_for<N_>(A.nx), A.nb)',
                         'I3': 'dim3(blocks_for<N_>(A.nb * A.ny))'}, launches
@@ -104,13 +108,35 @@ def test_the_mirror_restates_the_launch_arithmetic():
     assert (len(g['i1_blocks']), len(g['i3_blocks']), g['i2_grid']) == (6, 2, (1, 2))
 
 
-def test_the_line_machinery_is_a_header_of_the_new_file_alone():
+# definition-shaped: what opens the one definition of each piece of the line machinery (a call, a use or a comment does not match)
+PIECES = {
+    'stockham_pass': r'void stockham_pass\(', 'line_sync': r'void line_sync\(', 'Passes': r'struct Passes \{', 'LineGeo': r'struct LineGeo \{',
+    'store_lines_transposed': r'void store_lines_transposed\(', 'TwLds': r'struct TwLds \{', 'stage_twiddles': r'const float2\* stage_twiddles\(',
+    'line_fft': r'cf\* line_fft\(', 'line_sum': r'\w+ line_sum\(', 'line_sums': r'void line_sums\(', 'mul_rounded': r'float mul_rounded\(',
+    'blocks_for': r'int blocks_for\(',
+}
+HOST_PIECES = {
+    'the twiddle loop': r'-2\.0 \* M_PI \* \(double\)j / \(double\)N', 'the frequency mesh': r'uv\[\(size_t\)x \* ny \+ y\] = u \* u \+ v \* v;',
+    'line_side_ok': r'bool line_side_ok\(', 'line_upload_twiddles': r'int line_upload_twiddles\(', 'line_upload_uv2t': r'int line_upload_uv2t\(',
+}
+
+
+def test_the_line_machinery_is_one_header_of_the_three_files():
     from adorym_amd.csrc import build
-    assert 'adm_ctf_invert.hip' in build.SRCS and 'adm_line_fft.h' in build.HDRS
-    users = [n for n in build.SRCS + [h for h in build.HDRS if os.sep not in h] if '"adm_line_fft.h"' in _read('adorym_amd', 'csrc', n)]
-    assert users == ['adm_ctf_invert.hip'], users
-    first = HDR.split('#pragma once')[0]
-    assert 'adm_holo.hip' in first and 'adm_holo_ctf.hip' in first and 'pin' in first
-    # the set the issue names
-    for piece in ('stockham_pass', 'line_sync', 'struct Passes', 'struct LineGeo', 'store_lines_transposed', 'struct TwLds', 'stage_twiddles', 'line_fft'):
-        assert piece in HDR, piece
+    assert 'adm_ctf_invert.hip' in build.SRCS and 'adm_line_fft.h' in build.HDRS and 'adm_line_host.h' in build.HDRS
+    names = sorted(n for n in os.listdir(os.path.join(ROOT, 'adorym_amd', 'csrc')) if n.endswith(('.hip', '.h')))
+    assert set(build.SRCS + [h for h in build.HDRS if os.sep not in h]) <= set(names)
+    text = {n: re.sub(r'//[^\n]*', '', _read('adorym_amd', 'csrc', n)) for n in names}
+    for hdr in ('adm_line_fft.h', 'adm_line_host.h'):
+        users = sorted(n for n in names if '"%s"' % hdr in text[n])
+        assert users == ['adm_ctf_invert.hip', 'adm_holo.hip', 'adm_holo_ctf.hip'], (hdr, users)
+    for n in ('adm_ctf_invert.hip', 'adm_holo.hip', 'adm_holo_ctf.hip'):
+        assert len(re.findall(r'^using namespace linefft;$', text[n], re.M)) == 1, n
+    # every piece is defined exactly once under adorym_amd/csrc, in its header
+    for table, home in ((PIECES, 'adm_line_fft.h'), (HOST_PIECES, 'adm_line_host.h')):
+        for piece, shape in table.items():
+            where = {n: len(re.findall(shape, t)) for n, t in text.items() if n != 'adm_api.hip' or table is PIECES}
+            assert {n: c for n, c in where.items() if c} == {home: 1}, (piece, where)
+    # one size list
+    lists = {n: len(re.findall(r'X\(16\) X\(32\) X\(64\) X\(128\) X\(256\) X\(512\) X\(1024\) X\(2048\)', t)) for n, t in text.items()}
+    assert {n: c for n, c in lists.items() if c} == {'adm_line_fft.h': 1}, lists

@@ -1,4 +1,4 @@
-"""The CTF forward model's kernels (adm_holo_ctf.hip: five line-kernel templates at the eight line lengths of ADM_CTF_SIZES, one
+"""The CTF forward model's kernels (adm_holo_ctf.hip: five line-kernel templates at the eight line lengths of ADM_LINE_SIZES, one
 fixed kernel, three ABI entry points) through the C ABI against tests/ctf_ref.py in fp64 (pytest -m gpu).  tests/ctf_matrix.py
 holds the fields, the mirror of the launch geometry, the variants and the references; tests/test_ctf_coverage.py ties those tables
 to the kernel source, tests/test_ctf_ref_vs_golden.py the reference to golden F26 and every case here to its conditions.

@@ -1,5 +1,5 @@
 """The direct CTF inversion's kernels (adm_ctf_invert.hip: three line-kernel templates at the eight line lengths of
-ADM_CTFINV_SIZES, three ABI entry points) through adorym_amd.CTFInversion and the C ABI against tests/ctfinv_ref.py in fp64
+ADM_LINE_SIZES, three ABI entry points) through adorym_amd.CTFInversion and the C ABI against tests/ctfinv_ref.py in fp64
 (pytest -m gpu).  tests/ctfinv_matrix.py holds the cases, the mirror of the launch geometry and the references;
 tests/test_ctfinv_coverage.py ties those tables to the kernel source, tests/test_ctfinv_ref_vs_golden.py the reference to golden
 F31 and every case here to its conditions.

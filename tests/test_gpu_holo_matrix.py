@@ -1,5 +1,5 @@
 """Every instantiation of the holography kernels (adm_holo.hip: nine line-kernel templates at the eight line lengths of
-ADM_HOLO_SIZES, two fixed kernels, seven ABI entry points) against the fp64 oracle (pytest -m gpu).  tests/holo_matrix.py holds
+ADM_LINE_SIZES, two fixed kernels, seven ABI entry points) against the fp64 oracle (pytest -m gpu).  tests/holo_matrix.py holds
 the fields, the mirror of the launch geometry, the variants and the references; tests/test_holo_matrix_coverage.py ties those
 tables to the kernel source.
 

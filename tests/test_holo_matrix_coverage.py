@@ -1,7 +1,8 @@
 """The holography matrix (tests/test_gpu_holo_matrix.py) covers what adm_holo.hip compiles and launches: tests/holo_matrix.py
-mirrors its launch arithmetic, and this CPU test parses the source -- ADM_HOLO_SIZES, the LineGeo expressions, TwLds::USE,
-pow2_in_range, the n_dists limit, every __global__ kernel and the switch over nx or ny that instantiates it -- so that a new size,
-a new kernel or a deleted field fails here until the tables follow.  It also checks the delta/beta wrapper of the oracle against
+mirrors its launch arithmetic, and this CPU test parses the source -- ADM_LINE_SIZES, the LineGeo expressions, TwLds::USE and
+blocks_for in adm_line_fft.h, line_side_ok and its bounds in adm_line_host.h, the n_dists limit, every __global__ kernel and the
+switch over nx or ny that instantiates it in adm_holo.hip -- so that a new size, a new kernel or a deleted field fails here until
+the tables follow.  It also checks the delta/beta wrapper of the oracle against
 finite differences and, for every field, what the oracle pair alone decides: the ill-conditioning guard and the 5 % cap on
 bands without signal."""
 import os
@@ -15,8 +16,8 @@ from tests import holo_matrix as HM
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def source():
-    with open(os.path.join(ROOT, 'adorym_amd', 'csrc', 'adm_holo.hip')) as f:
+def source(name='adm_holo.hip'):
+    with open(os.path.join(ROOT, 'adorym_amd', 'csrc', name)) as f:
         return f.read()
 
 
@@ -52,17 +53,19 @@ def c_expr(expr, env):
     return eval(c_to_py(expr).replace('/', '//'), {'__builtins__': {}}, dict(env))
 
 
-def sizes(src):
-    m = re.search(r'#define\s+ADM_HOLO_SIZES\(X\)((?:\s*X\(\d+\))+)', src)
-    assert m, 'ADM_HOLO_SIZES'
+def sizes():
+    m = re.search(r'#define\s+ADM_LINE_SIZES\(X\)((?:\s*X\(\d+\))+)', source('adm_line_fft.h'))
+    assert m, 'ADM_LINE_SIZES'
     return tuple(int(v) for v in re.findall(r'X\((\d+)\)', m.group(1)))
 
 
 def test_the_mirror_uses_the_sizes_and_limits_of_the_source():
-    src = source()
-    assert sizes(src) == HM.SIZES
-    m = re.search(r'static bool pow2_in_range\(int n\) \{ return n >= (\d+) && n <= (\d+) && \(n & \(n - 1\)\) == 0; \}', src)
+    src, host = source(), source('adm_line_host.h')
+    assert sizes() == HM.SIZES
+    m = re.search(r'constexpr int ADM_LINE_MIN_SIDE = (\d+), ADM_LINE_MAX_SIDE = (\d+);', host)
     assert m and (int(m.group(1)), int(m.group(2))) == (HM.MIN_SIDE, HM.MAX_SIDE)
+    assert 'inline bool line_side_ok(int n) { return n >= ADM_LINE_MIN_SIDE && n <= ADM_LINE_MAX_SIDE && (n & (n - 1)) == 0; }' in host
+    assert 'if (!line_side_ok(d.ny) || !line_side_ok(d.nx))' in src
     assert HM.SIZES == tuple(n for n in range(1, 5000) if HM.pow2_in_range(n))          # every accepted side has its instantiation
     m = re.search(r'if \(d\.n_dists < 1 \|\| d\.n_dists > (\d+)\)', src)
     assert m and int(m.group(1)) == HM.MAX_DISTS
@@ -71,10 +74,10 @@ def test_the_mirror_uses_the_sizes_and_limits_of_the_source():
 
 
 def test_the_mirror_follows_linegeo_and_twlds():
-    src = source()
-    geo = re.search(r'template <int N> struct LineGeo \{(.*?)\n\};', src, re.S).group(1)
+    src, hdr = source(), source('adm_line_fft.h')
+    geo = re.search(r'template <int N> struct LineGeo \{(.*?)\n\};', hdr, re.S).group(1)
     ex = {n: re.search(r'static constexpr int %s = ([^;]+);' % n, geo).group(1) for n in ('TPR', 'LPB', 'LP')}
-    use = re.search(r'template <int N> struct TwLds \{\s*static constexpr bool USE = ([^;]+);', src).group(1)
+    use = re.search(r'template <int N> struct TwLds \{\s*static constexpr bool USE = ([^;]+);', hdr).group(1)
     for n in HM.SIZES:
         env = dict(N=n)
         for k in ('TPR', 'LPB', 'LP'):
@@ -86,7 +89,7 @@ def test_the_mirror_follows_linegeo_and_twlds():
     assert [HM.line_geo(n)['LPB'] for n in HM.SIZES] == [128, 64, 32, 16, 8, 4, 2, 1]
     assert [HM.line_geo(n)['LP'] - n for n in HM.SIZES] == [1, 1, 1, 2, 4, 8, 16, 0]
     # blocks_for, K3's jobs, K4's one block per line and its rounds
-    assert 'static int blocks_for(int lines) { return (lines + LineGeo<N>::LPB - 1) / LineGeo<N>::LPB; }' in src
+    assert 'static int blocks_for(int lines) { return (lines + LineGeo<N>::LPB - 1) / LineGeo<N>::LPB; }' in hdr
     assert 'const int job0 = blockIdx.x * LG::LPB, job = job0 + ll;' in src and 'const int d = ok ? job / A.ny : 0, y = ok ? job % A.ny : 0;' in src
     assert 'for (int d0 = 0; d0 < A.nd; d0 += LG::LPB) {' in src and 'const int kx = blockIdx.x;' in src
     g = HM.geometry(64, 16, 3)
@@ -124,7 +127,7 @@ def launched_by(src):
     macros, out = {}, {}
     modes = sorted(set(re.findall(r'launch_slf<(\d)>\(', src)))
     text = src.replace('\\\n', ' ')
-    for m in re.finditer(r'#define (\w+)\(N_\) (.*)|switch \([AS]\.(nx|ny)\) \{ ADM_HOLO_SIZES\((\w+)\)', text):
+    for m in re.finditer(r'#define (\w+)\(N_\) (.*)|switch \([AS]\.(nx|ny)\) \{ ADM_LINE_SIZES\((\w+)\)', text):
         if m.group(1):
             body = m.group(2)
             ks = re.findall(r'\(\((holo_\w+)<N_(?:, (\w+))?>\)', body) + [(k, '') for k in re.findall(r'K_X\((holo_\w+), N_', body)]
@@ -160,7 +163,7 @@ def test_the_matrix_names_exactly_the_kernels_of_the_source():
 
 
 def test_every_instantiation_is_reached():
-    want = {(k, n if '<' in k else 0) for k in HM.KERNELS for n in sizes(source())}
+    want = {(k, n if '<' in k else 0) for k in HM.KERNELS for n in sizes()}
     missing = sorted(want - HM.reached())
     assert not missing, 'instantiations no field launches: %s' % missing
     assert len(want) == 12 * 8 + 2
