@@ -20,6 +20,7 @@ import copy
 import numpy as np
 
 from oracle import adorym_oracle as O
+from tests.sparse_ref import masked_loss
 
 
 def round32(dists_cm):
@@ -50,8 +51,10 @@ def exit_waves(tiles, probes, phys, dtype):
     return np.stack([O.multislice_forward(tiles, p, q, dtype) for p in np.asarray(probes)])
 
 
-def forward_dist_grad(tiles, probes, meas, phys, dists_cm, dtype='float64', raw_data_type='magnitude'):
-    """tiles [B,Py,Px,S,2], probes complex [M,Py,Px], meas [B*D,Py,Px] position-major (entry b * D + d), LSQ loss.
+def forward_dist_grad(tiles, probes, meas, phys, dists_cm, dtype='float64', raw_data_type='magnitude', loss_function_type='lsq',
+                      poisson_multiplier=1., beamstop=None):
+    """tiles [B,Py,Px,S,2], probes complex [M,Py,Px], meas [B*D,Py,Px] position-major (entry b * D + d); the loss arguments and
+    ``beamstop`` [Py,Px] as O.forward_adjoint_tiles takes them.
     Returns loss, pred [B*D,Py,Px], dL/d free_prop_cm [D] (per cm) and its per-field terms [B, M, D] (their sum over the first two
     axes is the gradient)."""
     dt = np.dtype(dtype)
@@ -69,8 +72,8 @@ def forward_dist_grad(tiles, probes, meas, phys, dists_cm, dtype='float64', raw_
     pred = np.abs(fields[0]) if M == 1 else np.sqrt((fields.real ** 2 + fields.imag ** 2).sum(axis=0))
     pred = pred.reshape(B * D, Py, Px).astype(dt)
     meas = np.asarray(meas).astype(dt, copy=False)
-    loss = O.mismatch_loss(pred, meas, 'lsq', raw_data_type)
-    dldp = O._dloss_dpred(pred, meas, 'lsq', raw_data_type, 1.).astype(dt).reshape(B, D, Py, Px)
+    loss, dldp = masked_loss(pred, meas, dt, loss_function_type, raw_data_type, poisson_multiplier, beamstop)
+    dldp = dldp.reshape(B, D, Py, Px)
     with np.errstate(divide='ignore', invalid='ignore'):
         unit = fields / pred.reshape(B, D, Py, Px)[None]
         if M == 1:
@@ -82,10 +85,11 @@ def forward_dist_grad(tiles, probes, meas, phys, dists_cm, dtype='float64', raw_
     return loss, pred, terms.sum(axis=(0, 1)), terms
 
 
-def forward_dist_grad_object(obj, coords_fp16, probes, pos_batch, meas, phys, dists_cm, dtype='float64', raw_data_type='magnitude'):
+def forward_dist_grad_object(obj, coords_fp16, probes, pos_batch, meas, phys, dists_cm, dtype='float64', raw_data_type='magnitude',
+                             loss_function_type='lsq', poisson_multiplier=1., beamstop=None):
     """Rotate, cut the tiles, evaluate.  Returns loss, pred, dL/d free_prop_cm [D] and the per-field terms [B, M, D]."""
     dt = np.dtype(dtype)
     obj = obj.astype(dt, copy=False)
     rot = O.rotate_fwd(obj, coords_fp16, dt) if coords_fp16 is not None else obj
     tiles, _ = O.extract_tiles(rot, pos_batch, phys.probe_size, phys.unknown_type)
-    return forward_dist_grad(tiles, probes, meas, phys, dists_cm, dt, raw_data_type)
+    return forward_dist_grad(tiles, probes, meas, phys, dists_cm, dt, raw_data_type, loss_function_type, poisson_multiplier, beamstop)

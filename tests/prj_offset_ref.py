@@ -23,6 +23,7 @@ import copy
 import numpy as np
 
 from oracle import adorym_oracle as O
+from tests.sparse_ref import masked_loss
 
 PI = O.PI
 
@@ -40,9 +41,10 @@ def shifted_physics(phys, shifts_b, dtype='float64'):
     return q
 
 
-def forward_adjoint_tiles(tiles, probes, meas, phys, shifts, index=None, dtype='float64', raw_data_type='magnitude'):
-    """Loss, prediction [B,Py,Px], grad_tiles [B,Py,Px,S,2], grad_probes complex [M,Py,Px] (O.forward_adjoint_tiles, LSQ loss) and
-    dL/dshifts [n_entries, 2].  ``shifts`` [n_entries, 2] = (s_y, s_x); ``index`` [B] or None = b."""
+def forward_adjoint_tiles(tiles, probes, meas, phys, shifts, index=None, dtype='float64', raw_data_type='magnitude',
+                          loss_function_type='lsq', poisson_multiplier=1., beamstop=None):
+    """Loss, prediction [B,Py,Px], grad_tiles [B,Py,Px,S,2], grad_probes complex [M,Py,Px] (O.forward_adjoint_tiles, its loss
+    arguments and ``beamstop`` included) and dL/dshifts [n_entries, 2].  ``shifts`` [n_entries, 2] = (s_y, s_x); ``index`` [B] or None = b."""
     dt = np.dtype(dtype)
     cdt = O._cdtype(dt)
     probes = np.asarray(probes)
@@ -53,13 +55,15 @@ def forward_adjoint_tiles(tiles, probes, meas, phys, shifts, index=None, dtype='
     index = np.arange(B) if index is None else np.asarray(index).astype(int)
     q = shifted_physics(phys, shifts[index], dt)
     gs = np.zeros(shifts.shape, dtype=dt)
+    loss_kw = dict(raw_data_type=raw_data_type, loss_function_type=loss_function_type, poisson_multiplier=poisson_multiplier,
+                   beamstop=beamstop)
     if q is None:
-        return O.forward_adjoint_tiles(tiles, probes, meas, phys, dt, raw_data_type=raw_data_type) + (gs,)
-    loss, pred, gt, gp = O.forward_adjoint_tiles(tiles, probes, meas, q, dt, raw_data_type=raw_data_type)
+        return O.forward_adjoint_tiles(tiles, probes, meas, phys, dt, **loss_kw) + (gs,)
+    loss, pred, gt, gp = O.forward_adjoint_tiles(tiles, probes, meas, q, dt, **loss_kw)
     # the shift gradient: the exit waves once more (the oracle does not hand them out), then the sums above
     bare = copy.copy(phys)
     bare.det_mode, bare.h_free = 'none', None
-    dldp = O._dloss_dpred(pred, np.asarray(meas).astype(dt, copy=False), 'lsq', raw_data_type, 1.).astype(dt)
+    dldp = masked_loss(pred, np.asarray(meas).astype(dt, copy=False), dt, loss_function_type, raw_data_type, poisson_multiplier, beamstop)[1]
     fy = np.fft.fftfreq(Py, 1).astype(dt)[:, None]
     fx = np.fft.fftfreq(Px, 1).astype(dt)[None, :]
     hq = q.h_free_cast(dt)
@@ -83,14 +87,16 @@ def predict(tiles, probes, phys, shifts, index=None, dtype='float64'):
     return O.predict(tiles, probes, q if q is not None else phys, dtype)[0]
 
 
-def forward_adjoint_object(obj, coords_fp16, probes, pos_batch, meas, phys, shifts, index=None, dtype='float64', raw_data_type='magnitude'):
+def forward_adjoint_object(obj, coords_fp16, probes, pos_batch, meas, phys, shifts, index=None, dtype='float64', raw_data_type='magnitude',
+                           loss_function_type='lsq', poisson_multiplier=1., beamstop=None):
     """O.forward_adjoint_object with the offsets: rotate, cut tiles, evaluate, scatter, rotate back.  Returns loss, pred, the object
     gradient [Y,X,S,2], the probe gradient and dL/dshifts."""
     dt = np.dtype(dtype)
     obj = obj.astype(dt, copy=False)
     rot = O.rotate_fwd(obj, coords_fp16, dt) if coords_fp16 is not None else obj
     tiles, _ = O.extract_tiles(rot, pos_batch, phys.probe_size, phys.unknown_type)
-    loss, pred, gt, gp, gs = forward_adjoint_tiles(tiles, probes, meas, phys, shifts, index, dt, raw_data_type=raw_data_type)
+    loss, pred, gt, gp, gs = forward_adjoint_tiles(tiles, probes, meas, phys, shifts, index, dt, raw_data_type=raw_data_type,
+                                                   loss_function_type=loss_function_type, poisson_multiplier=poisson_multiplier, beamstop=beamstop)
     g = O.scatter_tiles_adj(gt, pos_batch, obj.shape)
     if coords_fp16 is not None:
         g = O.rotate_adj(g, coords_fp16, dt)

@@ -46,10 +46,24 @@ def gap_kernels(phys, z_cm, dtype='float64'):
     return (np.stack(hs) if hs else np.zeros((0,) + tuple(phys.probe_size), cdt)), d
 
 
-def forward_adjoint_tiles(tiles, probes, meas, phys, z_cm, dtype='float64', raw_data_type='magnitude', want_grad=True):
+def masked_loss(pred, meas, dtype, loss_function_type='lsq', raw_data_type='magnitude', poisson_multiplier=1., beamstop=None):
+    """The loss and dL/dpred exactly as O.forward_adjoint_tiles forms them: with a ``beamstop`` [Py,Px] only the pixels with
+    beamstop >= 1e-5 enter the mean, and dL/dpred is zero elsewhere.  pred, meas [N,Py,Px]."""
+    if beamstop is None:
+        loss = O.mismatch_loss(pred, meas, loss_function_type, raw_data_type, poisson_multiplier)
+        return loss, O._dloss_dpred(pred, meas, loss_function_type, raw_data_type, poisson_multiplier).astype(dtype)
+    keep = np.asarray(beamstop) >= 1e-5
+    loss = O.mismatch_loss(pred[:, keep], meas[:, keep], loss_function_type, raw_data_type, poisson_multiplier)
+    dldp = np.zeros_like(pred)
+    dldp[:, keep] = O._dloss_dpred(pred[:, keep], meas[:, keep], loss_function_type, raw_data_type, poisson_multiplier)
+    return loss, dldp
+
+
+def forward_adjoint_tiles(tiles, probes, meas, phys, z_cm, dtype='float64', raw_data_type='magnitude', want_grad=True,
+                          loss_function_type='lsq', poisson_multiplier=1., beamstop=None):
     """Loss, prediction [B,Py,Px], grad_tiles [B,Py,Px,S,2], grad_probes complex [M,Py,Px] (the conventions of
-    O.forward_adjoint_tiles, LSQ loss) and dL/dz [S] in 1/cm, for slices at ``z_cm``.  ``phys``: O.Physics with binning 1 (its own
-    slice kernel ``h`` is not used)."""
+    O.forward_adjoint_tiles, its loss arguments and ``beamstop`` included) and dL/dz [S] in 1/cm, for slices at ``z_cm``.
+    ``phys``: O.Physics with binning 1 (its own slice kernel ``h`` is not used)."""
     dt = np.dtype(dtype)
     cdt = O._cdtype(dt)
     assert phys.binning == 1
@@ -78,10 +92,9 @@ def forward_adjoint_tiles(tiles, probes, meas, phys, z_cm, dtype='float64', raw_
         specs.append(spec)
     pred = np.abs(fields[0]) if len(fields) == 1 else np.sqrt(sum((f.real ** 2 + f.imag ** 2) for f in fields))
     meas = np.asarray(meas).astype(dt, copy=False)
-    loss = O.mismatch_loss(pred, meas, 'lsq', raw_data_type, 1.)
+    loss, dldp = masked_loss(pred, meas, dt, loss_function_type, raw_data_type, poisson_multiplier, beamstop)
     if not want_grad:
         return loss, pred
-    dldp = O._dloss_dpred(pred, meas, 'lsq', raw_data_type, 1.).astype(dt)
     grad_tiles = np.zeros_like(tiles)
     grad_probes = np.zeros(probes.shape, dtype=cdt)
     gd_gap = np.zeros(max(S - 1, 0), dtype=dt)
@@ -116,14 +129,17 @@ def predict(tiles, probes, phys, z_cm, dtype='float64'):
     return forward_adjoint_tiles(tiles, probes, np.zeros(tiles.shape[:3]), phys, z_cm, dtype, want_grad=False)[1]
 
 
-def forward_adjoint_object(obj, coords_fp16, probes, pos_batch, meas, phys, z_cm, dtype='float64', raw_data_type='magnitude'):
+def forward_adjoint_object(obj, coords_fp16, probes, pos_batch, meas, phys, z_cm, dtype='float64', raw_data_type='magnitude',
+                           loss_function_type='lsq', poisson_multiplier=1., beamstop=None):
     """O.forward_adjoint_object for the sparse model: rotate, cut tiles, evaluate, scatter, rotate back.  Returns loss, pred, the
     object gradient [Y,X,S,2], the probe gradient and dL/dz."""
     dt = np.dtype(dtype)
     obj = obj.astype(dt, copy=False)
     rot = O.rotate_fwd(obj, coords_fp16, dt) if coords_fp16 is not None else obj
     tiles, _ = O.extract_tiles(rot, pos_batch, phys.probe_size, phys.unknown_type)
-    loss, pred, gt, gp, gz = forward_adjoint_tiles(tiles, probes, meas, phys, z_cm, dt, raw_data_type=raw_data_type)
+    loss, pred, gt, gp, gz = forward_adjoint_tiles(tiles, probes, meas, phys, z_cm, dt, raw_data_type=raw_data_type,
+                                                   loss_function_type=loss_function_type, poisson_multiplier=poisson_multiplier,
+                                                   beamstop=beamstop)
     g = O.scatter_tiles_adj(gt, pos_batch, obj.shape)
     if coords_fp16 is not None:
         g = O.rotate_adj(g, coords_fp16, dt)

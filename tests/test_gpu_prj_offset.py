@@ -160,7 +160,10 @@ def make_case(P, S=2, B=5, M=1, shared=False, unknown_type='delta_beta', free_pr
     Py, Px = (P, P) if np.isscalar(P) else tuple(P)
     r = np.random.default_rng([Py, Px, S, B, M, seed])
     Y, X = Py + 9, Px + 13
-    mk = lambda c: np.stack([2e-3 * c * r.uniform(size=(Y, X, S)), 2e-4 * c * r.uniform(size=(Y, X, S))], -1)
+    if unknown_type == 'delta_beta':
+        mk = lambda c: np.stack([2e-3 * c * r.uniform(size=(Y, X, S)), 2e-4 * c * r.uniform(size=(Y, X, S))], -1)
+    else:           # (a transmission near 1, as make_case of test_gpu_sparse_multislice.py)
+        mk = lambda c: np.stack([1 + 1e-2 * c * r.standard_normal((Y, X, S)), 2e-2 * c * r.standard_normal((Y, X, S))], -1)
     obj, truth = mk(1).astype(np.float32), mk(10).astype(np.float32)
     pos = MM.edge_positions(r, B, Y, X, Py, Px)
     probes = ((0.5 + r.uniform(0, 1, (M, Py, Px))) * np.exp(1j * r.uniform(-np.pi, np.pi, (M, Py, Px)))).astype(np.complex64)

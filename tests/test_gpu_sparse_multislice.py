@@ -129,9 +129,9 @@ def test_engine_vs_reference(A, ctx, F, name):
 
 
 # --------------------------------------------------------------------------------- 2. sizes the fixture does not hold (restatement)
-def make_case(P, S=3, B=11, M=1, unknown_type='delta_beta', free_prop='inf', sign_convention=1, seed=0):
+def make_case(P, S=3, B=11, M=1, unknown_type='delta_beta', free_prop='inf', sign_convention=1, seed=0, z=None):
     """Built like ms_matrix.oracle_case: positions hanging over all four edges, a truth with ten times the guess's contrast (and
-    slice positions 3 % away) makes the data."""
+    slice positions 3 % away) makes the data.  ``z`` [S] (cm): slice positions in place of the ones drawn."""
     Py, Px = (P, P) if np.isscalar(P) else tuple(P)
     r = np.random.default_rng([Py, Px, S, B, M, seed])
     Y, X = Py + 9, Px + 13
@@ -142,7 +142,8 @@ def make_case(P, S=3, B=11, M=1, unknown_type='delta_beta', free_prop='inf', sig
     obj, truth = mk(1).astype(np.float32), mk(10).astype(np.float32)
     pos = MM.edge_positions(r, B, Y, X, Py, Px)
     probes = ((0.5 + r.uniform(0, 1, (M, Py, Px))) * np.exp(1j * r.uniform(-np.pi, np.pi, (M, Py, Px)))).astype(np.complex64)
-    z = np.concatenate([[0.], np.cumsum(r.uniform(3e-4, 3e-3, S - 1))]).astype(np.float32)          # unequal gaps, 3 - 30 um
+    drawn = np.concatenate([[0.], np.cumsum(r.uniform(3e-4, 3e-3, S - 1))]).astype(np.float32)      # unequal gaps, 3 - 30 um
+    z = drawn if z is None else np.asarray(z, np.float32)
     phys = O.Physics((Py, Px), ENERGY_EV, PSIZE_CM, free_prop_cm=free_prop, sign_convention=sign_convention, unknown_type=unknown_type)
     tiles, _ = O.extract_tiles(truth.astype(np.float64), pos, (Py, Px), unknown_type)
     meas = SR.predict(tiles, probes.astype(np.complex128), phys, (z * np.float32(1.03)).astype(np.float64))
