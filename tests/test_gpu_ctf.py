@@ -36,11 +36,11 @@ def ctx(A):
 
 # ------------------------------------------------------------------------------------------------------------ one launch
 class Handle(object):
-    def __init__(self, ctx, ny, nx, nd, raw='intensity'):
+    def __init__(self, ctx, ny, nx, nd, raw='intensity', energy_ev=CM.ENERGY_EV, psize_cm=CM.PSIZE_CM):
         from adorym_amd._lib import CtfDesc, check
         self.ctx, self.check = ctx, check
         self.h = C.c_void_p()
-        desc = CtfDesc(ny=ny, nx=nx, n_dists=nd, raw_intensity=1 if raw == 'intensity' else 0, energy_ev=CM.ENERGY_EV, psize_cm=CM.PSIZE_CM)
+        desc = CtfDesc(ny=ny, nx=nx, n_dists=nd, raw_intensity=1 if raw == 'intensity' else 0, energy_ev=energy_ev, psize_cm=psize_cm)
         check(ctx.lib.adm_ctf_create(ctx.handle, C.byref(desc), C.byref(self.h)))
 
     def close(self):
@@ -50,11 +50,13 @@ class Handle(object):
 
 
 def seeds(c, kind, like=None):
-    """The gradient buffers before the launch: zeros; 'sentinel': a finite pattern of mixed signs and magnitudes over 2^+-12;
+    """The gradient buffers before the launch: zeros; 'nan': NaN; 'sentinel': a finite pattern of mixed signs and magnitudes over 2^+-12;
     'seeded': values of mixed signs within a factor of two of the rms of the gradients ``like`` (an earlier launch's)."""
     shapes = dict(g_obj=(c['ny'], c['nx'], 2), g_kappa=(1,))
     if kind is None:
         return {k: np.zeros(s, np.float32) for k, s in shapes.items()}
+    if kind == 'nan':
+        return {k: np.full(s, np.nan, np.float32) for k, s in shapes.items()}
     if kind == 'sentinel':
         return {k: CM.sentinel(s, 41 + n) for n, (k, s) in enumerate(shapes.items())}
     r = CM.cases.rng(29)
@@ -77,7 +79,7 @@ def launch(ctx, c, h=None, want_grad=True, overwrite=False, seed=None, like=None
                                     (2 if overwrite else 1) if want_grad else 0, d['g_obj'].ptr if want_obj else None,
                                     p(d['g_kappa']) if want_kappa else None,
                                     p(pred), p(loss)))
-    out = dict(pred=pred.get() if want_pred else None, seeds=s0,
+    out = dict(pred=pred.get() if want_pred else None, seeds=s0, loss_d=loss.get() if want_loss else None,
                loss=float(loss.get().astype(np.float64).sum() / c['data'].size) if want_loss else None)
     out.update({k: v.get() for k, v in d.items()})
     if own:

@@ -64,7 +64,7 @@ def launch(ctx, c, h=None, want_grad=True, overwrite=False, seed=None, like=None
     for _ in range(n_launches):
         h.check(ctx.lib.adm_ctfd_fwd_adj(h.h, obj.ptr, dd.ptr, lgk.ptr, data.ptr, (2 if overwrite else 1) if want_grad else 0,
                                          d['g_obj'].ptr, d['g_kappa'].ptr, d['g_dists'].ptr if want_dists else None, pred.ptr, loss.ptr))
-    out = dict(pred=pred.get(), seeds=s0, loss=float(loss.get().astype(np.float64).sum() / c['data'].size))
+    out = dict(pred=pred.get(), seeds=s0, loss_d=loss.get(), loss=float(loss.get().astype(np.float64).sum() / c['data'].size))
     out.update({k: v.get() for k, v in d.items()})
     if own:
         h.close()
