@@ -9,7 +9,7 @@ from .constants import PI  # noqa: F401
 from . import global_settings  # noqa: F401
 from .device import Context, DeviceArray, Plan, Event, PinnedArray, UploadRing  # noqa: F401
 from .propagate import MultisliceEngine, ProjectionEngine, RotatedProjector, RotationTable, AngleBatch, get_kernel, gen_freq_mesh  # noqa: F401
-from .holography import HolographyEngine, CTFEngine, CTFInversion, HologramRegistration  # noqa: F401
+from .holography import HolographyEngine, CTFEngine, CTFInversion, HologramRegistration, HomogeneousObject  # noqa: F401
 
 __version__ = '0.1.0'
 

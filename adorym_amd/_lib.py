@@ -14,6 +14,7 @@ OPT_ADAM, OPT_GD, OPT_MOMENTUM = 0, 1, 2
 P2P_HANDLE_BYTES, P2P_MAX_RANKS = 64, 16
 CG_MAX_BLOCKS = 1024
 CG_SCRATCH_DOUBLES = 3 * CG_MAX_BLOCKS + 8
+KAPPA_SCRATCH_DOUBLES = CG_MAX_BLOCKS + 1
 CG_SUM_A, CG_SUM_B, CG_SUM_BETA, CG_SUM_C, CG_SUM_E, CG_SUM_D = range(6)
 
 
@@ -174,6 +175,8 @@ SIGNATURES = {
     'adm_cg_fallback': (_I, [_VP, _VP, _VP, _SZ]),
     'adm_cg_trial': (_I, [_VP, _VP, _VP, _F, _VP, _SZ]),
     'adm_cg_accept': (_I, [_VP, _VP, _VP, _SZ, _SZ, _I, _VP]),
+    'adm_kappa_tie': (_I, [_VP, _VP, _VP, _SZ, _VP]),
+    'adm_kappa_fold': (_I, [_VP, _VP, _VP, _VP, _SZ, _I, _VP, _VP, _VP]),
     'adm_rwl1_update': (_I, [_VP, _VP, _VP, _VP]),
     'adm_reg_grad_weighted': (_I, [_VP, _VP, _VP, _F, _F, _VP, _VP]),
     'adm_axpy': (_I, [_VP, _VP, _VP, _F, _SZ]),

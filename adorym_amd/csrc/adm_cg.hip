@@ -10,47 +10,10 @@
 #include "adm_optim.h"
 
 namespace adm {
-#define CG_THREADS 256
+// (the walk over the flat arrays, the grid, the alignment test and the workgroup's double sum: adm_optim.h, shared with adm_kappa_tie.hip)
+#define CG_THREADS FLAT_THREADS
 // sums block (device: scratch[0 .. 8), host: sums_host[0 .. 8)), then the partials
 enum { CG_A = 0, CG_B = 1, CG_BETA = 2, CG_C = 3, CG_E = 4, CG_D = 5, CG_SUMS = 8 };
-
-static inline int cg_grid(size_t n) {       // 16 elements per thread until the cap: ADM_CG_MAX_BLOCKS = 4 workgroups per CU
-    size_t b = (n + 16 * CG_THREADS - 1) / (16 * CG_THREADS);
-    return (int)(b > ADM_CG_MAX_BLOCKS ? ADM_CG_MAX_BLOCKS : (b ? b : 1));
-}
-static inline bool cg_aligned(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
-}
-
-// the sum of one double per thread over the workgroup, on thread 0; red: CG_THREADS / 64 doubles of LDS
-__device__ __forceinline__ double cg_block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0) {
-        t = red[0];
-        for (int w = 1; w < CG_THREADS / 64; ++w) t += red[w];
-    }
-    __syncthreads();
-    return t;
-}
-
-// Every kernel walks its n elements the same way: VEC, float4 q of thread t, t + T, ... (T = all threads of the grid), then the
-// n % 4 last elements one each on the first threads; otherwise element by element.  `one(i)` handles element i, `four(q)` elements 4q ... 4q + 3.
-template <bool VEC, class One, class Four>
-__device__ __forceinline__ void cg_walk(size_t n, One one, Four four) {
-    const size_t t = (size_t)blockIdx.x * CG_THREADS + threadIdx.x, T = (size_t)gridDim.x * CG_THREADS;
-    if (VEC) {
-        const size_t n4 = n >> 2;
-        for (size_t q = t; q < n4; q += T) four(q);
-        const size_t i = (n4 << 2) + t;
-        if (i < n) one(i);
-    } else {
-        for (size_t i = t; i < n; i += T) one(i);
-    }
-}
 
 // A = sum d (d - d_old), B = sum d_old^2 with d = -g   (_calculate_PR_beta, adorym/optimizers.py:606-628)
 template <bool VEC>
@@ -63,12 +26,12 @@ __global__ __launch_bounds__(CG_THREADS) void cg_beta_kernel(const float* __rest
         a += d * (d - o);
         b += o * o;
     };
-    cg_walk<VEC>(n, [&](size_t i) { term(g[i], d_old[i]); },
+    flat_walk<VEC>(n, [&](size_t i) { term(g[i], d_old[i]); },
                  [&](size_t q) {
                      const float4 gv = ((const float4*)g)[q], ov = ((const float4*)d_old)[q];
                      term(gv.x, ov.x); term(gv.y, ov.y); term(gv.z, ov.z); term(gv.w, ov.w);
                  });
-    const double ta = cg_block_sum(a, red), tb = cg_block_sum(b, red);
+    const double ta = flat_block_sum(a, red), tb = flat_block_sum(b, red);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = ta; part[2 * blockIdx.x + 1] = tb; }
 }
 
@@ -88,13 +51,13 @@ __global__ __launch_bounds__(CG_THREADS) void cg_direction_kernel(const float* _
         dd += g64 * g64;
         return sn;
     };
-    cg_walk<VEC>(n, [&](size_t i) { const float gv = g[i]; s[i] = term(gv, s[i]); d_old[i] = -gv; },
+    flat_walk<VEC>(n, [&](size_t i) { const float gv = g[i]; s[i] = term(gv, s[i]); d_old[i] = -gv; },
                  [&](size_t q) {
                      const float4 gv = ((const float4*)g)[q], sv = ((const float4*)s)[q];
                      ((float4*)s)[q] = make_float4(term(gv.x, sv.x), term(gv.y, sv.y), term(gv.z, sv.z), term(gv.w, sv.w));
                      ((float4*)d_old)[q] = make_float4(-gv.x, -gv.y, -gv.z, -gv.w);
                  });
-    const double tc = cg_block_sum(c, red), te = cg_block_sum(e, red), td = cg_block_sum(dd, red);
+    const double tc = flat_block_sum(c, red), te = flat_block_sum(e, red), td = flat_block_sum(dd, red);
     if (threadIdx.x == 0) { part[3 * blockIdx.x] = tc; part[3 * blockIdx.x + 1] = te; part[3 * blockIdx.x + 2] = td; }
 }
 
@@ -127,7 +90,7 @@ __global__ __launch_bounds__(CG_THREADS) void cg_finish_kernel(const double* __r
 // s <- -g: the direction when the conjugate one does not descend (optimizers.py:672-674)
 template <bool VEC>
 __global__ __launch_bounds__(CG_THREADS) void cg_fallback_kernel(const float* __restrict__ g, float* __restrict__ s, size_t n) {
-    cg_walk<VEC>(n, [&](size_t i) { s[i] = -g[i]; },
+    flat_walk<VEC>(n, [&](size_t i) { s[i] = -g[i]; },
                  [&](size_t q) { const float4 gv = ((const float4*)g)[q]; ((float4*)s)[q] = make_float4(-gv.x, -gv.y, -gv.z, -gv.w); });
 }
 
@@ -135,7 +98,7 @@ __global__ __launch_bounds__(CG_THREADS) void cg_fallback_kernel(const float* __
 template <bool VEC>
 __global__ __launch_bounds__(CG_THREADS) void cg_trial_kernel(const float* __restrict__ x0, const float* __restrict__ s, float alpha,
                                                               float* __restrict__ xt, size_t n) {
-    cg_walk<VEC>(n, [&](size_t i) { xt[i] = x0[i] + alpha * s[i]; },
+    flat_walk<VEC>(n, [&](size_t i) { xt[i] = x0[i] + alpha * s[i]; },
                  [&](size_t q) {
                      const float4 xv = ((const float4*)x0)[q], sv = ((const float4*)s)[q];
                      ((float4*)xt)[q] = make_float4(xv.x + alpha * sv.x, xv.y + alpha * sv.y, xv.z + alpha * sv.z, xv.w + alpha * sv.w);
@@ -149,7 +112,7 @@ __global__ __launch_bounds__(CG_THREADS) void cg_accept_kernel(float* x, const f
                                                                const float* __restrict__ mask) {
     float* xl = x + lo;
     const float* sl = src + lo;
-    cg_walk<VEC>(n, [&](size_t i) { xl[i] = constrain(sl[i], lo + i, flags, mask); },
+    flat_walk<VEC>(n, [&](size_t i) { xl[i] = constrain(sl[i], lo + i, flags, mask); },
                  [&](size_t q) {
                      const float4 v = ((const float4*)sl)[q];
                      const size_t i = lo + 4 * q;
@@ -162,8 +125,8 @@ using namespace adm;
 
 #define CG_LAUNCH(kernel, vec, n, ...)                                                                                     \
     do {                                                                                                                   \
-        if (vec) hipLaunchKernelGGL(kernel<true>, dim3(cg_grid(n)), dim3(CG_THREADS), 0, ctx->stream, __VA_ARGS__);        \
-        else hipLaunchKernelGGL(kernel<false>, dim3(cg_grid(n)), dim3(CG_THREADS), 0, ctx->stream, __VA_ARGS__);           \
+        if (vec) hipLaunchKernelGGL(kernel<true>, dim3(flat_grid(n)), dim3(CG_THREADS), 0, ctx->stream, __VA_ARGS__);        \
+        else hipLaunchKernelGGL(kernel<false>, dim3(flat_grid(n)), dim3(CG_THREADS), 0, ctx->stream, __VA_ARGS__);           \
         ADM_HIP(hipGetLastError());                                                                                        \
     } while (0)
 
@@ -171,8 +134,8 @@ extern "C" int adm_cg_beta(adm_ctx* ctx, const float* g, const float* d_old, siz
     if (!ctx || !g || !d_old || !scratch || !sums_host) return fail(ADM_ERR_INVALID, "adm_cg_beta: null argument");
     if (!n) return fail(ADM_ERR_INVALID, "adm_cg_beta: n = 0");
     double* part = scratch + CG_SUMS;
-    CG_LAUNCH(cg_beta_kernel, cg_aligned(g, d_old), n, g, d_old, n, part);
-    hipLaunchKernelGGL(cg_finish_kernel, dim3(1), dim3(CG_THREADS), 0, ctx->stream, (const double*)part, cg_grid(n), 2, (int)CG_A, i_batch, scratch,
+    CG_LAUNCH(cg_beta_kernel, flat_aligned(g, d_old), n, g, d_old, n, part);
+    hipLaunchKernelGGL(cg_finish_kernel, dim3(1), dim3(CG_THREADS), 0, ctx->stream, (const double*)part, flat_grid(n), 2, (int)CG_A, i_batch, scratch,
                        sums_host);
     ADM_HIP(hipGetLastError());
     return ADM_OK;
@@ -182,8 +145,8 @@ extern "C" int adm_cg_direction(adm_ctx* ctx, const float* g, float* s, float* d
     if (!ctx || !g || !s || !d_old || !scratch || !sums_host) return fail(ADM_ERR_INVALID, "adm_cg_direction: null argument");
     if (!n) return fail(ADM_ERR_INVALID, "adm_cg_direction: n = 0");
     double* part = scratch + CG_SUMS;
-    CG_LAUNCH(cg_direction_kernel, cg_aligned(g, s, d_old), n, g, s, d_old, (const double*)scratch, n, part);
-    hipLaunchKernelGGL(cg_finish_kernel, dim3(1), dim3(CG_THREADS), 0, ctx->stream, (const double*)part, cg_grid(n), 3, (int)CG_C, 0, scratch,
+    CG_LAUNCH(cg_direction_kernel, flat_aligned(g, s, d_old), n, g, s, d_old, (const double*)scratch, n, part);
+    hipLaunchKernelGGL(cg_finish_kernel, dim3(1), dim3(CG_THREADS), 0, ctx->stream, (const double*)part, flat_grid(n), 3, (int)CG_C, 0, scratch,
                        sums_host);
     ADM_HIP(hipGetLastError());
     return ADM_OK;
@@ -192,20 +155,20 @@ extern "C" int adm_cg_direction(adm_ctx* ctx, const float* g, float* s, float* d
 extern "C" int adm_cg_fallback(adm_ctx* ctx, const float* g, float* s, size_t n) {
     if (!ctx || !g || !s) return fail(ADM_ERR_INVALID, "adm_cg_fallback: null argument");
     if (!n) return ADM_OK;
-    CG_LAUNCH(cg_fallback_kernel, cg_aligned(g, s), n, g, s, n);
+    CG_LAUNCH(cg_fallback_kernel, flat_aligned(g, s), n, g, s, n);
     return ADM_OK;
 }
 
 extern "C" int adm_cg_trial(adm_ctx* ctx, const float* x0, const float* s, float alpha, float* x_trial, size_t n) {
     if (!ctx || !x0 || !s || !x_trial) return fail(ADM_ERR_INVALID, "adm_cg_trial: null argument");
     if (!n) return ADM_OK;
-    CG_LAUNCH(cg_trial_kernel, cg_aligned(x0, s, x_trial), n, x0, s, alpha, x_trial, n);
+    CG_LAUNCH(cg_trial_kernel, flat_aligned(x0, s, x_trial), n, x0, s, alpha, x_trial, n);
     return ADM_OK;
 }
 
 extern "C" int adm_cg_accept(adm_ctx* ctx, float* x, const float* x_src, size_t lo, size_t hi, int flags, const float* mask) {
     if (!ctx || !x || !x_src) return fail(ADM_ERR_INVALID, "adm_cg_accept: null argument");
     if (hi <= lo) return ADM_OK;
-    CG_LAUNCH(cg_accept_kernel, cg_aligned(x + lo, x_src + lo) && !(lo & 3), hi - lo, x, x_src, lo, hi - lo, flags, mask);
+    CG_LAUNCH(cg_accept_kernel, flat_aligned(x + lo, x_src + lo) && !(lo & 3), hi - lo, x, x_src, lo, hi - lo, flags, mask);
     return ADM_OK;
 }

@@ -56,6 +56,49 @@ __device__ __forceinline__ float momentum_value(float xv, float gv, float v_in, 
     return constrain(xv - vv, i, flags, mask);
 }
 
+// ---- streaming kernels over flat float32 arrays (adm_cg.hip, adm_kappa_tie.hip): FLAT_THREADS threads, a grid sized to the chip,
+// wide accesses when every pointer of a call is 16-byte aligned, a workgroup's double sum in a fixed order
+#define FLAT_THREADS 256
+
+static inline int flat_grid(size_t n) {     // 16 elements per thread until the cap: ADM_CG_MAX_BLOCKS = 4 workgroups per CU
+    size_t b = (n + 16 * FLAT_THREADS - 1) / (16 * FLAT_THREADS);
+    return (int)(b > ADM_CG_MAX_BLOCKS ? ADM_CG_MAX_BLOCKS : (b ? b : 1));
+}
+static inline bool flat_aligned(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
+
+// the sum of one double per thread over the workgroup, on thread 0; red: FLAT_THREADS / 64 doubles of LDS
+__device__ __forceinline__ double flat_block_sum(double v, double* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0) {
+        t = red[0];
+        for (int w = 1; w < FLAT_THREADS / 64; ++w) t += red[w];
+    }
+    __syncthreads();
+    return t;
+}
+
+// Every kernel walks its n elements the same way: VEC, group q (W elements, one wide access) of thread t, t + T, ... (T = all
+// threads of the grid), then the n % W last elements one each on the first threads; otherwise element by element.  `one(i)` handles
+// element i, `wide(q)` elements W q ... W q + W - 1.
+template <bool VEC, int W = 4, class One, class Wide>
+__device__ __forceinline__ void flat_walk(size_t n, One one, Wide wide) {
+    const size_t t = (size_t)blockIdx.x * FLAT_THREADS + threadIdx.x, T = (size_t)gridDim.x * FLAT_THREADS;
+    if (VEC) {
+        const size_t nw = n / W;
+        for (size_t q = t; q < nw; q += T) wide(q);
+        const size_t i = nw * W + t;
+        if (i < n) one(i);
+    } else {
+        for (size_t i = t; i < n; i += T) one(i);
+    }
+}
+
 static inline AdamScalars adam_scalars(int i_batch, double step_size, double b1, double b2, double eps, int flags, const float* mask) {
     // the reference evaluates the scalars in Python doubles and torch casts them to fp32 at the op
     AdamScalars a;

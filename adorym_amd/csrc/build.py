@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, 'libadm.so')
-SRCS = ['adm_api.hip', 'adm_rotate.hip', 'adm_overlap_add.hip', 'adm_regularize.hip', 'adm_optimize.hip', 'adm_cg.hip', 'adm_multislice.hip', 'adm_ms_generic.hip', 'adm_ms_streamed.hip', 'adm_ms_exitshift.hip', 'adm_ms_probeshift.hip', 'adm_ms_multidist.hip', 'adm_rotcsr.hip', 'adm_project.hip', 'adm_rotate_project.hip', 'adm_comm.hip', 'adm_p2p.hip', 'adm_holo.hip', 'adm_holo_ctf.hip', 'adm_ctf_dist.hip', 'adm_register.hip', 'adm_ctf_invert.hip']
+SRCS = ['adm_api.hip', 'adm_rotate.hip', 'adm_overlap_add.hip', 'adm_regularize.hip', 'adm_optimize.hip', 'adm_cg.hip', 'adm_kappa_tie.hip', 'adm_multislice.hip', 'adm_ms_generic.hip', 'adm_ms_streamed.hip', 'adm_ms_exitshift.hip', 'adm_ms_probeshift.hip', 'adm_ms_multidist.hip', 'adm_rotcsr.hip', 'adm_project.hip', 'adm_rotate_project.hip', 'adm_comm.hip', 'adm_p2p.hip', 'adm_holo.hip', 'adm_holo_ctf.hip', 'adm_ctf_dist.hip', 'adm_register.hip', 'adm_ctf_invert.hip']
 HDRS = ['adm_common.h', 'adm_host.h', 'adm_fft.h', 'adm_ms_math.h', 'adm_ms_gen.h', 'adm_ms_col.h', 'adm_optim.h', 'adm_block_sum.h', 'adm_rot_bilin.h', 'adm_line_fft.h', 'adm_line_host.h', 'adm_ctf_group.h', os.path.join('..', '..', 'include', 'adm.h')]
 
 

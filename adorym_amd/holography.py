@@ -6,7 +6,7 @@ Multi-distance near-field holography on the GPU: the en
 import ctypes as C
 import numpy as np
 
-from ._lib import HoloDesc, check
+from ._lib import HoloDesc, KAPPA_SCRATCH_DOUBLES, check
 from .constants import PI
 from .device import DeviceArray
 
@@ -367,3 +367,50 @@ class HologramRegistration(object):
         check(self.ctx.lib.adm_register_grad(self.handle, self._checked(data, shape, 'data'), self._checked(affine, (self.n_dists, 2, 3), 'affine'),
                                              self._checked(pred, shape, 'pred'), float(grad_scale),
                                              self._checked(grad_affine, (self.n_dists, 2, 3), 'grad_affine')))
+
+
+class HomogeneousObject(object):
+    """The single-material constraint of Fresnel multi-distance holography (optimize_ctf_lg_kappa with forward_algorithm='fresnel':
+    multislice_propagate_batch(..., kappa=10^ctf_lg_kappa[0]), adorym/propagate.py:223-225): the forward model sees the TIED object
+    (delta, kappa delta) in place of the user's (delta, beta), and the gradient w.r.t. the tied object is folded back into the
+    gradients w.r.t. delta and ctf_lg_kappa.  Owns the tied object, the tied gradient and the partial sums; ``obj_shape`` is the
+    object's, [Y, X, Z, 2] or [Y, X, 2] ('delta_beta' unknowns).  See include/adm.h (adm_kappa_*) and csrc/adm_kappa_tie.hip.
+    NOTE the sense: beta = kappa delta here, cos(xi) / kappa in the CTF model (CTFEngine) -- the reference's two meanings."""
+
+    def __init__(self, ctx, obj_shape):
+        shape = tuple(int(s) for s in obj_shape)
+        if len(shape) < 2 or shape[-1] != 2 or min(shape) < 1:
+            raise ValueError('HomogeneousObject: obj_shape must end in the (delta, beta) axis of length 2, got %r' % (list(obj_shape),))
+        self.ctx, self.shape = ctx, shape
+        self.n_vox = int(np.prod(shape[:-1]))
+        self._tied = DeviceArray(ctx, shape, np.float32)
+        self._grad = DeviceArray(ctx, shape, np.float32)
+        self._scratch = DeviceArray(ctx, (KAPPA_SCRATCH_DOUBLES,), np.float64)
+
+    def _checked(self, a, name, size=None):
+        size = 2 * self.n_vox if size is None else size
+        if not isinstance(a, DeviceArray):
+            raise TypeError('HomogeneousObject: %s must be a DeviceArray' % name)
+        if a.dtype != np.float32 or a.size != size:
+            raise ValueError('HomogeneousObject: %s must be float32 of %d values, got %s %r' % (name, size, np.dtype(a.dtype).name, list(a.shape)))
+        return a.ptr
+
+    def tie(self, obj, lg_kappa):
+        """The tied object (delta, fl32(kappa) delta) of ``obj`` under ``lg_kappa`` (DeviceArray [1]): the engine's own DeviceArray,
+        overwritten by the next call; queued on the stream the context is enqueuing on.  obj's beta channel is not read."""
+        check(self.ctx.lib.adm_kappa_tie(self.ctx.handle, self._checked(obj, 'obj'), self._checked(lg_kappa, 'lg_kappa', 1), self.n_vox,
+                                         self._tied.ptr))
+        return self._tied
+
+    def tied_grad(self):
+        """The buffer for dL/d(tied object), the engine's own and NOT initialised: the forward model overwrites it, or the caller
+        zero-fills it where the model accumulates."""
+        return self._grad
+
+    def fold(self, obj, lg_kappa, grad_obj, grad_lg_kappa, overwrite=False):
+        """tied_grad() folded into the gradients of the free unknowns: grad_obj.delta (+)= g_delta + fl32(kappa) g_beta and, if
+        given, grad_lg_kappa[0] (+)= ln10 kappa sum(delta g_beta).  ``overwrite``: both are set ('=') and grad_obj.beta is zeroed --
+        for buffers that hold garbage; otherwise both are added to and grad_obj.beta is left as it is."""
+        gk = None if grad_lg_kappa is None else self._checked(grad_lg_kappa, 'grad_lg_kappa', 1)
+        check(self.ctx.lib.adm_kappa_fold(self.ctx.handle, self._checked(obj, 'obj'), self._checked(lg_kappa, 'lg_kappa', 1), self._grad.ptr,
+                                          self.n_vox, 2 if overwrite else 1, self._checked(grad_obj, 'grad_obj'), gk, self._scratch.ptr))

@@ -18,6 +18,9 @@ def _refuse(what, cv, flags, served, message):
         raise NotImplementedError(message % what)
 
 
+KAPPA_REFUSED = "optimize_ctf_lg_kappa with forward_algorithm='fresnel' and %s is outside the accelerated path"
+
+
 def _served(path, free_prop, prj_affine):
     """What a path serves of the two: the former if its engine refines the distances, the latter if the caller brought a registration."""
     return ((free_prop,) if path.refine else ()) + ((prj_affine,) if path.m.registration is not None else ())
@@ -28,8 +31,21 @@ def _check_fresnel(m, safe_zone_width, probe_pos_correction, served=None):
     that takes no 3-D object at all."""
     cv = m.common_vars
     if cv.get('optimize_ctf_lg_kappa'):
-        # (the reference threads kappa into multislice_propagate_batch there, forward_model.py:878, 1010)
-        raise NotImplementedError("optimize_ctf_lg_kappa with forward_algorithm='fresnel' is outside the accelerated path")
+        # (the reference threads kappa into multislice_propagate_batch there, forward_model.py:878, 1010: beta = kappa delta)
+        if cv.get('homogeneous_object') is None:
+            raise NotImplementedError("optimize_ctf_lg_kappa with forward_algorithm='fresnel' is outside the accelerated path")
+        # served by the HomogeneousObject the caller brought, on the undivided 2-D field and on the fan-out path, on one rank
+        what = None
+        if m.tile_engine is not None or safe_zone_width not in (0, None) or int(cv.get('safe_zone_width') or 0) > 0:
+            what = 'data divided into sub-tiles or safe_zone_width > 0'
+        elif cv.get('unknown_type', 'delta_beta') == 'real_imag':
+            what = "unknown_type='real_imag'"             # (the reference ignores kappa there without a word)
+        elif cv.get('optimize_all_probe_pos'):
+            what = 'optimize_all_probe_pos'
+        elif int(cv.get('n_ranks') or 1) > 1:
+            what = 'more than one rank'
+        if what is not None:
+            raise NotImplementedError(KAPPA_REFUSED % what)
     if cv.get('optimize_all_probe_pos'):
         # one (sy, sx) per distance applied to the measured holograms (forward_model.py:1075-1085)
         if cv.get('optimize_prj_affine'):
@@ -79,6 +95,10 @@ class MultiDistModel(PtychographyModel):
         # the holograms are registered by kernels of their own when the caller brought that engine; only these two paths look at it
         self.registration = cv.get('hologram_registration') if (fanout or is_ctf) else None
         self.register_3d = fanout and self.registration is not None
+        # the single-material constraint of the Fresnel model (beta = kappa delta, kappa = 10^ctf_lg_kappa[0]: the OPPOSITE sense of
+        # the CTF model's cos(xi) / kappa, as in the reference) wraps the object of the paths that serve it, when, and only when,
+        # the caller brought the HomogeneousObject and the parameter is refined; _check_fresnel refuses it anywhere else
+        self.homogeneous = cv.get('homogeneous_object') if (not is_ctf and cv.get('optimize_ctf_lg_kappa')) else None
         if is_ctf and self.ctf is None:
             raise ValueError("MultiDistModel with forward_algorithm='ctf' needs common_vars_dict['ctf_engine'] (an adorym_amd.CTFEngine)")
         self._path = (_CTFPath(self, self.ctf, cv.get('ctf_projector')) if is_ctf else _FanoutPath(self, self.engine) if fanout
@@ -111,6 +131,37 @@ class MultiDistModel(PtychographyModel):
             self._data_dev = self.device.array(t)
             self._data_key = key
         return self._data_dev
+
+    def _tied(self, a):
+        """The arguments the forward path runs on: ``a`` itself, or -- on a model that carries the single-material constraint -- a
+        copy whose 'obj' is the tied object (delta, kappa delta) made in front of the launch (adm_kappa_tie; 3-D: in front of the
+        rotation, which is linear), with the device copy of ctf_lg_kappa under '_lg_kappa'.  Regularisers keep seeing a['obj']."""
+        h = self.homogeneous
+        if h is None:
+            return a
+        if a['ctf_lg_kappa'] is None:
+            raise ValueError("optimize_ctf_lg_kappa with forward_algorithm='fresnel' needs ctf_lg_kappa")
+        lgk = self._dev('ctf_lg_kappa', a['ctf_lg_kappa'], (1,))
+        return dict(a, obj=h.tie(a['obj'], lgk), _lg_kappa=lgk)
+
+    def _fold_tied(self, a, t, grad_obj, grads, wanted, init_grad):
+        """Behind a data term that left dL/d(tied object) in homogeneous.tied_grad(): the regulariser of the USER's object (its free
+        beta channel included, like the reference's) and the fold (adm_kappa_fold) into ``grad_obj`` and, if wanted, into the [1]
+        gradient w.r.t. ctf_lg_kappa, which joins ``grads``.  grad_obj's beta channel receives what the regulariser gives it and
+        nothing from the data term.  ``init_grad``: grad_obj holds garbage -- without a regulariser the fold writes it ('set', beta =
+        0: no zero fill), with one the regulariser initialises it and the fold adds.  Returns whether a regulariser value is pending."""
+        h = self.homogeneous
+        gk = self._small_grad('_grad_lg_kappa_dev', (1,)) if 'ctf_lg_kappa' in wanted else None
+        if gk is not None:
+            grads['ctf_lg_kappa'] = gk
+        if init_grad and not self.reg_list:
+            h.fold(a['obj'], t['_lg_kappa'], grad_obj, gk, overwrite=True)
+            return False
+        if gk is not None:
+            gk.zero_()
+        pending = self._regularize_launch(a['obj'], grad_obj, init_grad=bool(init_grad))
+        h.fold(a['obj'], t['_lg_kappa'], grad_obj, gk)
+        return pending
 
     def _check_registration(self, n_dists, field):
         """The HologramRegistration the caller brought fits the engine's distances and ``field`` (ny, nx), and the run's data."""
@@ -208,11 +259,11 @@ class _FieldPath(object):
                              grad_affine=g.get('prj_affine_ls') if aff is not None else None, want_pred=want_pred, overwrite=overwrite)
 
     def predict(self, a):
-        self._run(a, want_grad=False, want_pred=True)
+        self._run(self.m._tied(a), want_grad=False, want_pred=True)
         return self.holo.pred()
 
     def loss(self, a):
-        self._run(a, want_grad=False)
+        self._run(self.m._tied(a), want_grad=False)
         self.m.current_loss = float(self.holo.loss() + self.m._regularize(a['obj'], None))
         return self.m.current_loss
 
@@ -222,6 +273,10 @@ class _FieldPath(object):
             side_hook()
         nd = holo.n_dists
         fa = getattr(m, 'fused_adam', None)
+        h = m.homogeneous
+        if fa is not None and h is not None:
+            raise RuntimeError('fused holography update: it cannot carry ctf_lg_kappa (a run with the single-material constraint '
+                               'takes the separate launches)')
         if fa is not None:
             # the driver has established that this minibatch's update is plain Adam on exactly these gradients (one rank, no
             # regulariser / constraint / mask): gradient launch group and optimiser steps are ONE call, nothing is returned
@@ -252,9 +307,16 @@ class _FieldPath(object):
                 grads[name] = g if init_grad else g.zero_()
         if 'probe_pos_correction' in wanted:
             grads['probe_pos_correction'] = m._small_grad('_gs', (nd, 2), owner=self).zero_()           # (adm_holo_shift_grad accumulates)
-        self._run(a, want_grad=True, grad_obj=grad_obj, grads=grads, overwrite=bool(init_grad))
+        if h is None:
+            self._run(a, want_grad=True, grad_obj=grad_obj, grads=grads, overwrite=bool(init_grad))
+            pending = m._regularize_launch(a['obj'], grad_obj)
+        else:
+            # the data term on the tied object, into the tied-gradient buffer (grad_obj may hold earlier minibatches); then the fold
+            t, gt = m._tied(a), h.tied_grad()
+            self._run(t, want_grad=True, grad_obj=gt if init_grad else gt.zero_(), grads=grads, overwrite=bool(init_grad))
+            pending = m._fold_tied(a, t, grad_obj, grads, wanted, init_grad)
         # loss and regulariser value are read back lazily (the driver looks at them after the next minibatch has been queued)
-        regv = m._reg_value_async(m._regularize_launch(a['obj'], grad_obj))
+        regv = m._reg_value_async(pending)
         datav = holo.loss_async()
         m._loss_thunk = lambda: datav() + regv()
         return m._ordered_grads(opt_args_ls, grads)
@@ -463,24 +525,39 @@ class _FanoutPath(object):
     def predict(self, a):
         # (distance-major like the reference's; for one block that is the launch's order)
         zeros = np.zeros((self.eng.n_dists,) + tuple(self.eng.probe_size), np.float32)
-        self._run(a, zeros, want_grad=False, want_pred=True, regularize=False)
+        self._run(self.m._tied(a), zeros, want_grad=False, want_pred=True, regularize=False)
         return self.eng.pred()
 
     def loss(self, a):
-        self._run(a, None, want_grad=False)
-        self.m._queue_loss()
-        return self.m.current_loss
+        m = self.m
+        if m.homogeneous is None:
+            self._run(a, None, want_grad=False)
+        else:
+            # (the data term on the tied object, the regulariser on the user's)
+            self._run(m._tied(a), None, want_grad=False, regularize=False)
+            m._reg_pending = m._regularize_launch(a['obj'], None)
+        m._queue_loss()
+        return m.current_loss
 
     def loss_and_gradients(self, opt_args_ls, grad_obj, a, side_hook, init_grad):
-        m = self.m
-        served = ('obj', 'probe_real', 'probe_imag') + _served(self, 'free_prop_cm', 'prj_affine_ls')
+        m, h = self.m, self.m.homogeneous
+        served = ('obj', 'probe_real', 'probe_imag') + _served(self, 'free_prop_cm', 'prj_affine_ls') + (('ctf_lg_kappa',) if h is not None else ())
         m._ordered_grads(opt_args_ls, dict.fromkeys(served), 'multi-distance holography of a 3-D object: the ')      # (in front of the launch)
         wanted = set(m.argument_ls[i] for i in opt_args_ls)
         more = dict(grad_dists=m._small_grad('_grad_dists_dev', self.eng.dists.shape)) if 'free_prop_cm' in wanted else None
-        gp, _ = self._run(a, None, want_grad=True, grad_obj=grad_obj, want_probe_grad='probe_real' in wanted or 'probe_imag' in wanted,
-                          side_hook=side_hook, init_grad=init_grad, more_grads=more, want_affine_grad='prj_affine_ls' in wanted)
+        kw = dict(want_probe_grad='probe_real' in wanted or 'probe_imag' in wanted, side_hook=side_hook, more_grads=more,
+                  want_affine_grad='prj_affine_ls' in wanted)
+        grads = {}
+        if h is None:
+            gp, _ = self._run(a, None, want_grad=True, grad_obj=grad_obj, init_grad=init_grad, **kw)
+        else:
+            # the data term alone on the tied object (tied BEFORE the rotation, which is linear), zero-filled tied-gradient buffer
+            # and no regulariser; then the regulariser of the user's object and the fold, behind the back-rotation
+            t = m._tied(a)
+            gp, _ = self._run(t, None, want_grad=True, grad_obj=h.tied_grad(), init_grad=True, regularize=False, **kw)
+            m._reg_pending = m._fold_tied(a, t, grad_obj, grads, wanted, init_grad)
         m._queue_loss()          # m.current_loss fetches it on first access
-        return m._ordered_grads(opt_args_ls, dict(obj=grad_obj, probe_real=gp, probe_imag=gp, free_prop_cm=getattr(m, '_grad_dists_dev', None),
+        return m._ordered_grads(opt_args_ls, dict(grads, obj=grad_obj, probe_real=gp, probe_imag=gp, free_prop_cm=getattr(m, '_grad_dists_dev', None),
                                                   prj_affine_ls=getattr(m, '_grad_affine_dev', None)))
 
 

@@ -338,6 +338,9 @@ class _Run(object):
         self.ctf_prj_affine = bool(kwargs.pop('ctf_prj_affine', False))
         # optimizer='cg': conjugate gradient with a line search for the object (CGOptimizer), on request
         self.device_cg = bool(kwargs.pop('device_cg', False))
+        # optimize_ctf_lg_kappa under forward_algorithm='fresnel': the single-material constraint beta = kappa delta wrapped around
+        # the object of the multi-distance Fresnel models (HomogeneousObject), on request
+        self.fresnel_kappa = bool(kwargs.pop('fresnel_kappa', False))
         self.ops =kwargs.pop('ops', None)
         kwargs.pop('probe_size', None)
         self.kwargs = kwargs
@@ -416,7 +419,20 @@ class _Run(object):
         for nm in ('optimize_probe_defocusing', 'optimize_probe_pos_offset', 'optimize_tilt'):
             _not_implemented(getattr(self, nm), nm)
         # (the reference threads kappa into multislice_propagate_batch there, forward_model.py:878, 1010: not built)
-        _not_implemented(bool(self.optimize_ctf_lg_kappa) and self.forward_algorithm != 'ctf', "optimize_ctf_lg_kappa with forward_algorithm='fresnel'")
+        # (fresnel_kappa=True: the object is tied in front of the forward model and the gradient folded behind it, HomogeneousObject)
+        _not_implemented(bool(self.optimize_ctf_lg_kappa) and self.forward_algorithm != 'ctf' and not self.fresnel_kappa,
+                         "optimize_ctf_lg_kappa with forward_algorithm='fresnel'")
+        if self.fresnel_kappa:
+            if not self.optimize_ctf_lg_kappa:
+                # (the reference ties the object only while it refines kappa, forward_model.py:876-878; a fixed kappa is
+                # ctf_lg_kappa_learning_rate=0)
+                raise ValueError('fresnel_kappa=True needs optimize_ctf_lg_kappa=True (a fixed kappa: ctf_lg_kappa_learning_rate=0)')
+            if self.forward_algorithm != 'fresnel':
+                raise ValueError("fresnel_kappa=True needs forward_algorithm='fresnel' (the CTF model carries kappa itself)")
+            what = "optimize_ctf_lg_kappa with forward_algorithm='fresnel' and %s"
+            _not_implemented(self.unknown_type == 'real_imag', what % "unknown_type='real_imag'")
+            _not_implemented(bool(self.optimize_all_probe_pos), what % 'optimize_all_probe_pos')
+            _not_implemented(self.n_ranks > 1, what % 'more than one rank')
         if self.update_scheme not in ('immediate', 'per angle'):
             raise ValueError("update_scheme must be 'immediate' or 'per angle'")
 
@@ -532,6 +548,8 @@ class _Run(object):
             _not_implemented(self.loss_function_type != 'lsq', "forward_algorithm='ctf' with loss_function_type='%s'" % self.loss_function_type
                              if self.forward_algorithm == 'ctf' else 'Poisson loss with multi-distance data')
             self.holo_tiled = len(probe_pos) > 1 or safe_zone_width > 0
+            _not_implemented(self.fresnel_kappa and self.holo_tiled, "optimize_ctf_lg_kappa with forward_algorithm='fresnel' and data divided "
+                             'into sub-tiles or safe_zone_width > 0')
             if self.is_ctf:
                 # modulate_and_get_ctf (adorym/propagate.py:467-476): no probe, one slice in delta/beta, one undivided field of view,
                 # fixed distances, no registration of the holograms
@@ -567,6 +585,7 @@ class _Run(object):
             self.probe_size = [int(v) for v in obj_size[:2]]          # subdiv_probe (ptychography.py:312-314)
         else:
             _not_implemented(self.optimize_free_prop or self.optimize_prj_affine, 'optimize_free_prop / optimize_prj_affine without multi-distance data')
+            _not_implemented(self.fresnel_kappa, "optimize_ctf_lg_kappa with forward_algorithm='fresnel' without multi-distance data")
             if isinstance(self.free_prop_cm, np.ndarray):
                 free_prop_cm = self.free_prop_cm.reshape(-1)[0]
                 self.free_prop_cm = free_prop_cm if isinstance(free_prop_cm, str) else float(free_prop_cm)
@@ -668,6 +687,10 @@ class _Run(object):
                     'sub-pixel probe positions (optimize_all_probe_pos or fractional probe_pos) with a %d x %d probe (streamed multislice) '
                     'is outside the accelerated path of adorym_amd (see DESIGN.md, out of scope).  The keyword '
                     'streamed_probe_shift=True applies them inside the streamed sweep.' % tuple(probe_size))
+        self.homogeneous = None
+        if self.fresnel_kappa:
+            from .holography import HomogeneousObject
+            self.homogeneous = HomogeneousObject(ctx, [*obj_size, 2])
         tables, theta_ls = {}, self.theta_ls
 
         def rotation_tables(i_theta):
@@ -787,6 +810,8 @@ class _Run(object):
             common_vars['hologram_registration'] = self.registration
         if self.ctf_projector is not None:
             common_vars.update(ctf_projector=self.ctf_projector, n_ranks=self.n_ranks)
+        if self.homogeneous is not None:
+            common_vars.update(homogeneous_object=self.homogeneous, n_ranks=self.n_ranks)
         fm_args = dict(loss_function_type=self.loss_function_type, distribution_mode=self.distribution_mode, device=ctx,
                        common_vars_dict=common_vars, raw_data_type=self.raw_data_type, run_bfloat16=self.run_bfloat16,
                        run_float64=self.run_float64)
@@ -911,7 +936,7 @@ class _Run(object):
         if self.is_sparse_multislice and self.optimize_slice_pos:
             # optimizers.py:891-903, 1051-1060: Adam on the slice positions (+ "prevent position drifting": subtract the first)
             self._add_small('slice_pos_cm_ls', self.optimizer_slice_pos, self.slice_pos_learning_rate, anchor=True)
-        if self.is_multi_dist and self.is_ctf:
+        if self.is_multi_dist and (self.is_ctf or self.fresnel_kappa):
             # a [1] array like the reference's (ptychography.py:732-733; float32 here), on the device whether it is refined or not:
             # the kernels read it there
             params['ctf_lg_kappa'] = ctx.array(np.array([float(self.ctf_lg_kappa)]), np.float32)
@@ -949,7 +974,7 @@ class _Run(object):
                 if mom_ is not None and 'free_prop_cm_moments' in restored:
                     for m_, h_ in zip(mom_, restored['free_prop_cm_moments']):
                         m_.set(np.asarray(h_, dtype=np.float32).reshape(m_.shape))
-            if self.ctf_3d or self.refine_ctf_dists or self.register_ctf:
+            if self.ctf_3d or self.refine_ctf_dists or self.register_ctf or self.fresnel_kappa:
                 mom_ = self._small_moments('ctf_lg_kappa')
                 if mom_ is not None and 'ctf_lg_kappa_moments' in restored:
                     for m_, h_ in zip(mom_, restored['ctf_lg_kappa_moments']):
@@ -992,8 +1017,8 @@ class _Run(object):
             mom_ = self._small_moments('free_prop_cm')
             if mom_ is not None:
                 out_['free_prop_cm_moments'] = [m_.get() for m_ in mom_]
-        if self.ctf_3d or self.refine_ctf_dists or self.register_ctf:
-            mom_ = self._small_moments('ctf_lg_kappa')        # (likewise, for the 3-D CTF run and the CTF runs that refine more)
+        if self.ctf_3d or self.refine_ctf_dists or self.register_ctf or self.fresnel_kappa:
+            mom_ = self._small_moments('ctf_lg_kappa')        # (likewise, for the 3-D CTF run, the CTF runs that refine more and the tied Fresnel runs)
             if mom_ is not None:
                 out_['ctf_lg_kappa_moments'] = [m_.get() for m_ in mom_]
         if self.register_3d or self.register_ctf:

@@ -628,6 +628,24 @@ int adm_cg_direction(adm_ctx* ctx, const float* g, float* s, float* d_old, size_
 int adm_cg_fallback(adm_ctx* ctx, const float* g, float* s, size_t n);
 int adm_cg_trial(adm_ctx* ctx, const float* x0, const float* s, float alpha, float* x_trial, size_t n);
 int adm_cg_accept(adm_ctx* ctx, float* x, const float* x_src, size_t lo, size_t hi, int flags, const float* mask);
+/* The single-material constraint of Fresnel multi-distance holography, beta = kappa delta with kappa = 10^lg_kappa[0]
+ * (multislice_propagate_batch(..., kappa=...), adorym/propagate.py:223-225; adorym/forward_model.py:876-878, 1003-1010): it wraps the
+ * OBJECT, n_vox interleaved (delta, beta) voxels of any shape, in front of and behind an unchanged forward model.  NOTE the sense:
+ * here beta = kappa delta, while the CTF model (adm_ctf_fwd_adj) uses cos(xi) / kappa -- the reference's two meanings of one number.
+ * lg_kappa: 1 float on the device; kappa = exp(ln10 (double)lg_kappa[0]) in double, rounded once to float (kappa32).
+ *   adm_kappa_tie   out[v] = (obj[v].delta, kappa32 * obj[v].delta); obj's beta channel is not used.
+ *   adm_kappa_fold  the transpose, from grad_tied = dL/d(tied object):  u = grad_tied[v].delta + kappa32 * grad_tied[v].beta (the
+ *                   product and the sum each rounded to float, no contraction);  mode 1: grad_obj[v].delta += u, grad_obj[v].beta
+ *                   untouched;  mode 2: grad_obj[v] = (u, 0), for a buffer that holds garbage.  With grad_lg_kappa (may be NULL):
+ *                   S = sum_v (double)obj[v].delta * (double)grad_tied[v].beta and grad_lg_kappa[0] (+)= (float)(ln10 * kappa * S),
+ *                   kappa in double, added in mode 1 and set in mode 2.
+ * Arrays of voxels are 8-byte aligned; 16-byte accesses are used when every array of a call is 16-byte aligned.  scratch:
+ * ADM_KAPPA_SCRATCH_DOUBLES doubles on the device, the caller's (not needed without grad_lg_kappa): [0] = S once the stream has
+ * reached that point, then one partial per workgroup.  S: fixed order, no atomics -- the same inputs give the same bits. */
+#define ADM_KAPPA_SCRATCH_DOUBLES (ADM_CG_MAX_BLOCKS + 1)
+int adm_kappa_tie(adm_ctx* ctx, const float* obj, const float* lg_kappa, size_t n_vox, float* out);
+int adm_kappa_fold(adm_ctx* ctx, const float* obj, const float* lg_kappa, const float* grad_tied, size_t n_vox, int mode,
+                   float* grad_obj, float* grad_lg_kappa, double* scratch);
 /* Reweighted L1 (adorym/regularizers.py:49-84).  adm_rwl1_update: weight = max(obj) / (|obj| + 1e-4*mean(obj)) over both
  * channels jointly (adorym/ptychography.py:995-1000); scratch = device float[2*1024+2].  adm_reg_grad_weighted:
  * grad_obj += alpha_c * weight * sign(obj) / V, reg_value += alpha_d*mean(w_d|delta|) + alpha_b*mean(w_b|beta|).
