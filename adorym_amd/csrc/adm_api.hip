@@ -398,9 +398,6 @@ extern "C" int adm_plan_set_detector_kernels(adm_plan* plan, int n, const float*
     if (n > 1 && plan->streamed)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_kernels: several detector kernels need one probe set per position "
                                          "(adm_multislice_fwd_adj_pp), which streamed plans do not run");
-    if (n > 1 && plan->probe_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_kernels: several detector kernels on a plan with probe shifts "
-                                         "(adm_plan_set_probe_shift) are not implemented");
     if (plan->d.det_mode != ADM_DET_FRESNEL) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_kernels: the plan's det_mode is not ADM_DET_FRESNEL");
     const size_t npx = (size_t)plan->d.probe_y * plan->d.probe_x, tot = npx * (size_t)n;
     float2 *a = nullptr, *b = nullptr;
@@ -424,21 +421,33 @@ extern "C" int adm_plan_set_detector_kernels(adm_plan* plan, int n, const float*
     return ADM_OK;
 }
 
+// The options that live on a streamed plan and exclude one another: what a message calls each, how it joins it to the option in
+// its way, the setter it points to, and the plan state that says the option is on.  (The fan-out has two setters, which replace
+// each other.)
+enum PlanOption { OPT_SLICE_POS, OPT_EXIT_SHIFT, OPT_PROBE_SHIFT, OPT_FANOUT };
+static const struct { const char *noun, *join, *setter; bool plural; bool (*on)(const adm_plan*); } PLAN_OPTIONS[] = {
+    {"slice positions", " together with ", "adm_plan_set_slice_positions", true, [](const adm_plan* p) { return p->n_zpos > 0; }},
+    {"exit-wave shifts", " on a plan with ", "adm_plan_set_exit_shift", true, [](const adm_plan* p) { return p->exit_shift; }},
+    {"probe shifts", " on a plan with ", "adm_plan_set_probe_shift", true, [](const adm_plan* p) { return p->probe_shift; }},
+    {"a detector fan-out", " on a plan with ", "adm_plan_set_detector_fanout", false, [](const adm_plan* p) { return p->n_fan > 0; }},
+};
+// Every setter of the table asks this first: the plan is streamed (a fan-out also needs the Fresnel detector step) and, unless the
+// call switches the option off, no other option of the table is on.
+static int plan_option_check(const adm_plan* plan, PlanOption opt, const std::string& who, bool on) {
+    const auto& me = PLAN_OPTIONS[opt];
+    if (!plan->streamed)
+        return fail(ADM_ERR_UNSUPPORTED, who + ": " + me.noun + (me.plural ? " need" : " needs") + " a streamed plan (adm_plan_create_streamed)");
+    if (opt == OPT_FANOUT && plan->d.det_mode != ADM_DET_FRESNEL) return fail(ADM_ERR_INVALID, who + ": the plan's det_mode is not ADM_DET_FRESNEL");
+    for (const auto& other : PLAN_OPTIONS)
+        if (on && &other != &me && other.on(plan))
+            return fail(ADM_ERR_UNSUPPORTED, who + ": " + me.noun + me.join + other.noun + " (" + other.setter + ")" +
+                                                 (me.plural ? " are" : " is") + " not implemented");
+    return ADM_OK;
+}
+
 extern "C" int adm_plan_set_detector_fanout(adm_plan* plan, int n, const float* hfree_re, const float* hfree_im) {
     if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_fanout: null plan");
-    if (!plan->streamed)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_fanout: a detector fan-out needs a streamed plan (adm_plan_create_streamed); "
-                                         "the one-workgroup kernels take several distances through adm_plan_set_detector_kernels");
-    if (plan->d.det_mode != ADM_DET_FRESNEL) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_fanout: the plan's det_mode is not ADM_DET_FRESNEL");
-    if (n != 0 && plan->exit_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_fanout: a detector fan-out on a plan with exit-wave shifts "
-                                         "(adm_plan_set_exit_shift) is not implemented");
-    if (n != 0 && plan->probe_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_fanout: a detector fan-out on a plan with probe shifts "
-                                         "(adm_plan_set_probe_shift) is not implemented");
-    if (n != 0 && plan->n_zpos > 0)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_detector_fanout: a detector fan-out on a plan with slice positions "
-                                         "(sparse multislice) is not implemented");
+    if (const int rc = plan_option_check(plan, OPT_FANOUT, "adm_plan_set_detector_fanout", n != 0)) return rc;
     if (n < 0 || n > 64) return fail(ADM_ERR_INVALID, "adm_plan_set_detector_fanout: n must be in [1, 64] (0 switches the fan-out off)");
     float2* hs = nullptr;
     if (n > 0) {
@@ -462,18 +471,7 @@ extern "C" int adm_plan_set_detector_fanout(adm_plan* plan, int n, const float* 
 extern "C" int adm_plan_set_fanout_distances(adm_plan* plan, const float* dists_cm_dev, int n, double lambda_nm, double voxel_nm_y,
                                              double voxel_nm_x) {
     if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: null plan");
-    if (!plan->streamed)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_fanout_distances: a detector fan-out needs a streamed plan (adm_plan_create_streamed)");
-    if (plan->d.det_mode != ADM_DET_FRESNEL) return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: the plan's det_mode is not ADM_DET_FRESNEL");
-    if (plan->exit_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_fanout_distances: a detector fan-out on a plan with exit-wave shifts "
-                                         "(adm_plan_set_exit_shift) is not implemented");
-    if (plan->probe_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_fanout_distances: a detector fan-out on a plan with probe shifts "
-                                         "(adm_plan_set_probe_shift) is not implemented");
-    if (plan->n_zpos > 0)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_fanout_distances: a detector fan-out on a plan with slice positions "
-                                         "(sparse multislice) is not implemented");
+    if (const int rc = plan_option_check(plan, OPT_FANOUT, "adm_plan_set_fanout_distances", true)) return rc;     // (no n switches it off)
     if (n < 1 || n > 64) return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: n must be in [1, 64]");
     if (!dists_cm_dev) return fail(ADM_ERR_INVALID, "adm_plan_set_fanout_distances: null distances");
     if (!(lambda_nm > 0) || !(voxel_nm_y > 0) || !(voxel_nm_x > 0))
@@ -610,18 +608,7 @@ hipError_t probe_grad_reduce(const float2* part, int batch, size_t n, float2* ou
 extern "C" int adm_plan_set_slice_positions(adm_plan* plan, const float* z_cm_dev, int n, double lambda_nm, double voxel_nm_y,
                                             double voxel_nm_x) {
     if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_slice_positions: null plan");
-    if (!plan->streamed)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions (sparse multislice) need a streamed plan "
-                                         "(adm_plan_create_streamed); the one-workgroup kernels keep one transfer function");
-    if (n != 0 && plan->exit_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions together with exit-wave shifts "
-                                         "(adm_plan_set_exit_shift) are not implemented");
-    if (n != 0 && plan->probe_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions together with probe shifts "
-                                         "(adm_plan_set_probe_shift) are not implemented");
-    if (n != 0 && plan->n_fan > 0)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_slice_positions: slice positions together with a detector fan-out "
-                                         "(adm_plan_set_detector_fanout) are not implemented");
+    if (const int rc = plan_option_check(plan, OPT_SLICE_POS, "adm_plan_set_slice_positions", n != 0)) return rc;
     if (n == 0) {
         plan->zpos_dev = nullptr;
         plan->n_zpos = 0;
@@ -660,8 +647,8 @@ extern "C" int adm_slice_positions_anchor(adm_ctx* ctx, float* z_cm_dev, int n) 
 
 // The launch of a streamed plan: fields and loss partials from the layout; on a sparse plan also the tables of the gaps (rebuilt
 // first if the slice positions changed), the kept spectra and the dL/dd partials.
-static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* ws, const WsLayout& w, float* grad_slice_pos,
-                           const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift, float* grad_dists) {
+static int streamed_launch(adm_plan* plan, const MsParams& p, char* ws, const WsLayout& w, const MsCall& c) {
+    const int batch = c.batch;
     StFanoutLaunch fo;
     const bool fan = plan->n_fan > 0;
     if (fan) {
@@ -679,8 +666,8 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
                                                 plan->ctx->stream));
             }
             plan->fan_dists_dirty = false;
-            if (grad_dists && p.want_grad) {
-                fo.grad_dists = grad_dists;
+            if (c.grad_dists && p.want_grad) {
+                fo.grad_dists = c.grad_dists;
                 fo.keep = (float2*)(ws + w.fan_keep);
                 fo.part = (double*)(ws + w.fan_part);
                 fo.ay = plan->fan_a_dev;
@@ -688,15 +675,13 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
             }
         }
     }
-    StProbeShiftLaunch ps;
-    if (pshift) {
-        ps = *pshift;
+    StProbeShiftLaunch ps = c.ps;
+    if (ps.shifts) {
         ps.phat = (float2*)(ws + w.ps_phat);
         ps.part = (double*)(ws + w.ps_part);
     }
-    StExitShiftLaunch xs;
-    if (shift) {
-        xs = *shift;
+    StExitShiftLaunch xs = c.xs;
+    if (xs.shifts) {
         xs.keep = (float2*)(ws + w.xs_keep);
         xs.part = (double*)(ws + w.xs_part);
     }
@@ -716,45 +701,45 @@ static int streamed_launch(adm_plan* plan, const MsParams& p, int batch, char* w
         sp.part = (double*)(ws + w.dd_part);
         sp.ay = plan->sp_a_dev;
         sp.ax = plan->sp_a_dev ? plan->sp_a_dev + Py : nullptr;
-        sp.grad_z = grad_slice_pos;
+        sp.grad_z = c.grad_slice_pos;
     }
     ADM_HIP(ms_streamed_launch(p, batch, (float2*)(ws + w.field), (float*)(ws + w.loss_part), plan->ctx->stream, sparse ? &sp : nullptr,
-                               shift ? &xs : nullptr, fan ? &fo : nullptr, pshift ? &ps : nullptr));
+                               xs.shifts ? &xs : nullptr, fan ? &fo : nullptr, ps.shifts ? &ps : nullptr));
     return ADM_OK;
 }
 
-int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
-                         const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
-                         float grad_scale, void* workspace, size_t workspace_bytes, bool per_position, float* grad_slice_pos,
-                         const StExitShiftLaunch* shift, const StProbeShiftLaunch* pshift, float* grad_dists) {
-    if (!plan || !obj_rot || !probe || !pos || !target || !loss_sum)
+// The body of every adm_multislice_fwd_adj* entry point.
+int adm::multislice_call(adm_plan* plan, const MsCall& c) {
+    if (!plan || !c.obj_rot || !c.probe || !c.pos || !c.target || !c.loss_sum)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: null argument");
+    const int batch = c.batch, want_grad = c.want_grad;
+    float* const grad_probe = c.grad_probe;
+    const bool per_position = c.per_position;
     if (batch <= 0) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: batch must be positive");
     const adm_plan_desc& d = plan->d;
     if (plan->streamed && per_position)
         return fail(ADM_ERR_UNSUPPORTED, "adm_multislice_fwd_adj_pp: a streamed plan runs one probe set shared by all positions "
                                          "(per-position probes are not implemented on the streamed path)");
     const WsLayout w = ws_layout(plan, batch);
-    char* ws = (char*)workspace;
-    if (want_grad || plan->streamed) {      // (a streamed plan keeps its fields in the workspace even for want_grad = 0)
-        if (!workspace || workspace_bytes < w.total)
-            return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: workspace too small");
-    }
+    char* ws = (char*)c.workspace;
+    const bool ws_ok = ws && c.workspace_bytes >= w.total;
+    if ((want_grad || plan->streamed) && !ws_ok)      // (a streamed plan keeps its fields in the workspace even for want_grad = 0)
+        return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: workspace too small");
     MsParams p;
     std::memset(&p, 0, sizeof(p));
-    p.obj_rot = (const float2*)obj_rot;
+    p.obj_rot = (const float2*)c.obj_rot;
     p.want_grad = want_grad ? 1 : 0;
-    p.probe = (const float2*)probe;
+    p.probe = (const float2*)c.probe;
     p.grad_probe = (float2*)grad_probe;
-    p.pos = (const int2*)pos;
-    p.target = target;
-    p.pred = pred;
-    p.loss_sum = loss_sum;
+    p.pos = (const int2*)c.pos;
+    p.target = c.target;
+    p.pred = c.pred;
+    p.loss_sum = c.loss_sum;
     p.stash = ws ? (float2*)(ws + w.stash) : nullptr;
     p.gtile = ws ? (float2*)(ws + w.gtile) : nullptr;
     p.det = ws ? (float2*)(ws + w.det) : nullptr;
     p.n_modes = d.n_modes;
-    if (d.n_modes > 1 && (!workspace || workspace_bytes < w.total))
+    if (d.n_modes > 1 && !ws_ok)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: several probe modes need the workspace even for want_grad = 0");
     p.h = plan->h_dev;
     p.hfree = plan->hfree_dev;
@@ -774,7 +759,7 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
     else p.det_scale = p.det_inverse ? (float)(1.0 / npx) : 1.0f;             // ifft2 carries 1/N, fft2 none
     p.k1 = d.k1;
     p.sigma = (float)d.sign_convention;
-    p.grad_scale = grad_scale;
+    p.grad_scale = c.grad_scale;
     p.loss_type = d.loss_type;
     p.poisson_mult = d.poisson_multiplier;
     p.real_imag = d.unknown_type;
@@ -793,7 +778,7 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         p.gprobe_bstride = probe_elems;
     }
     // cached slice transmissions: only for the buffer they were computed from
-    const bool use_t = plan->trans_dev && plan->trans_src == (const void*)obj_rot && d.unknown_type == 0 && d.binning == 1;
+    const bool use_t = plan->trans_dev && plan->trans_src == (const void*)c.obj_rot && d.unknown_type == 0 && d.binning == 1;
     if (plan->trans_only && !use_t)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj: the plan keeps slice transmissions only (cache mode 2) and this obj_rot was not "
                                      "produced by adm_rotate_fwd on it");
@@ -804,8 +789,7 @@ int adm::multislice_impl(adm_plan* plan, const float* obj_rot, const float* prob
         for (int i = 0; i < 8; ++i) { p.gen_rx[i] = plan->gen_rx[i]; p.gen_ry[i] = plan->gen_ry[i]; }
         p.gen_twid_y = plan->twid_y_dev; p.gen_hs = plan->hs_dev; p.gen_hfree_s = plan->hfree_s_dev;
         if (plan->streamed) {
-            const int rc = streamed_launch(plan, p, batch, ws, w, grad_slice_pos, shift, pshift, grad_dists);
-            if (rc) return rc;
+            if (const int rc = streamed_launch(plan, p, ws, w, c)) return rc;
         } else {
             ADM_HIP(ms_generic_launch(p, batch, plan->ctx->stream));
         }
@@ -830,8 +814,9 @@ extern "C" int adm_plan_set_generic(adm_plan* plan, int on) {
 extern "C" int adm_multislice_fwd_adj(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
                                       const float* target, int want_grad, float* grad_probe, float* pred, float* loss_sum,
                                       float grad_scale, void* workspace, size_t workspace_bytes) {
-    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
-                           workspace_bytes, false);
+    return multislice_call(plan, {.obj_rot = obj_rot, .probe = probe, .pos = pos, .batch = batch, .target = target, .want_grad = want_grad,
+                                  .grad_probe = grad_probe, .pred = pred, .loss_sum = loss_sum, .grad_scale = grad_scale,
+                                  .workspace = workspace, .workspace_bytes = workspace_bytes});
 }
 
 extern "C" int adm_multislice_fwd_adj_sparse(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
@@ -842,8 +827,9 @@ extern "C" int adm_multislice_fwd_adj_sparse(adm_plan* plan, const float* obj_ro
                                          "(adm_plan_create_streamed)");
     if (plan && plan->n_zpos == 0)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_sparse: the plan has no slice positions (adm_plan_set_slice_positions)");
-    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
-                           workspace_bytes, false, grad_slice_pos);
+    return multislice_call(plan, {.obj_rot = obj_rot, .probe = probe, .pos = pos, .batch = batch, .target = target, .want_grad = want_grad,
+                                  .grad_probe = grad_probe, .pred = pred, .loss_sum = loss_sum, .grad_scale = grad_scale,
+                                  .workspace = workspace, .workspace_bytes = workspace_bytes, .grad_slice_pos = grad_slice_pos});
 }
 
 extern "C" int adm_multislice_fwd_adj_fanout_dist(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch,
@@ -854,26 +840,16 @@ extern "C" int adm_multislice_fwd_adj_fanout_dist(adm_plan* plan, const float* o
                                          "(adm_plan_create_streamed)");
     if (plan && !(plan->n_fan > 0 && plan->fan_dists_dev))
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_fanout_dist: the plan has no fan-out distances (adm_plan_set_fanout_distances)");
-    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
-                           workspace_bytes, false, nullptr, nullptr, nullptr, grad_dists_dev);
+    return multislice_call(plan, {.obj_rot = obj_rot, .probe = probe, .pos = pos, .batch = batch, .target = target, .want_grad = want_grad,
+                                  .grad_probe = grad_probe, .pred = pred, .loss_sum = loss_sum, .grad_scale = grad_scale,
+                                  .workspace = workspace, .workspace_bytes = workspace_bytes, .grad_dists = grad_dists_dev});
 }
 
 extern "C" int adm_plan_set_exit_shift(adm_plan* plan, int on) {
     if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_exit_shift: null plan");
-    if (!plan->streamed)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts (per-angle projection alignment) need a streamed plan "
-                                         "(adm_plan_create_streamed); the one-workgroup kernels do not apply them");
-    if (on && plan->n_zpos > 0)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with slice positions (sparse multislice) "
-                                         "are not implemented");
+    if (const int rc = plan_option_check(plan, OPT_EXIT_SHIFT, "adm_plan_set_exit_shift", on != 0)) return rc;
     if (on && plan->n_hfree > 1)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with several detector kernels are not implemented");
-    if (on && plan->n_fan > 0)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with a detector fan-out "
-                                         "(adm_plan_set_detector_fanout) are not implemented");
-    if (on && plan->probe_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_exit_shift: exit-wave shifts on a plan with probe shifts (adm_plan_set_probe_shift) "
-                                         "are not implemented");
     plan->exit_shift = on != 0;
     return ADM_OK;
 }
@@ -887,28 +863,17 @@ extern "C" int adm_multislice_fwd_adj_exit_shift(adm_plan* plan, const float* ob
     if (plan && !plan->exit_shift)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_exit_shift: the plan was not switched to exit-wave shifts (adm_plan_set_exit_shift)");
     if (!shifts) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_exit_shift: null shifts");
-    StExitShiftLaunch xs;
-    xs.shifts = shifts; xs.index = index; xs.grad_shifts = grad_shifts; xs.keep = nullptr; xs.part = nullptr;
-    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
-                           workspace_bytes, false, nullptr, &xs);
+    return multislice_call(plan, {.obj_rot = obj_rot, .probe = probe, .pos = pos, .batch = batch, .target = target, .want_grad = want_grad,
+                                  .grad_probe = grad_probe, .pred = pred, .loss_sum = loss_sum, .grad_scale = grad_scale,
+                                  .workspace = workspace, .workspace_bytes = workspace_bytes,
+                                  .xs = {.shifts = shifts, .index = index, .grad_shifts = grad_shifts}});
 }
 
 extern "C" int adm_plan_set_probe_shift(adm_plan* plan, int on) {
     if (!plan) return fail(ADM_ERR_INVALID, "adm_plan_set_probe_shift: null plan");
-    if (!plan->streamed)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts inside the sweep need a streamed plan "
-                                         "(adm_plan_create_streamed); the one-workgroup kernels take them through adm_probe_shift");
-    if (on && plan->n_zpos > 0)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with slice positions (sparse multislice) "
-                                         "are not implemented");
-    if (on && plan->exit_shift)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with exit-wave shifts (adm_plan_set_exit_shift) "
-                                         "are not implemented");
+    if (const int rc = plan_option_check(plan, OPT_PROBE_SHIFT, "adm_plan_set_probe_shift", on != 0)) return rc;
     if (on && plan->n_hfree > 1)
         return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with several detector kernels are not implemented");
-    if (on && plan->n_fan > 0)
-        return fail(ADM_ERR_UNSUPPORTED, "adm_plan_set_probe_shift: probe shifts on a plan with a detector fan-out "
-                                         "(adm_plan_set_detector_fanout) are not implemented");
     plan->probe_shift = on != 0;
     return ADM_OK;
 }
@@ -923,17 +888,18 @@ extern "C" int adm_multislice_fwd_adj_probe_shift(adm_plan* plan, const float* o
     if (plan && !plan->probe_shift)
         return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_probe_shift: the plan was not switched to probe shifts (adm_plan_set_probe_shift)");
     if (!shifts) return fail(ADM_ERR_INVALID, "adm_multislice_fwd_adj_probe_shift: null shifts");
-    StProbeShiftLaunch ps;
-    ps.shifts = shifts; ps.index = index; ps.grad_shifts = want_grad ? grad_shifts : nullptr; ps.phat = nullptr; ps.part = nullptr;
-    return multislice_impl(plan, obj_rot, probe, pos, batch, target, want_grad, grad_probe, pred, loss_sum, grad_scale, workspace,
-                           workspace_bytes, false, nullptr, nullptr, &ps);
+    return multislice_call(plan, {.obj_rot = obj_rot, .probe = probe, .pos = pos, .batch = batch, .target = target, .want_grad = want_grad,
+                                  .grad_probe = grad_probe, .pred = pred, .loss_sum = loss_sum, .grad_scale = grad_scale,
+                                  .workspace = workspace, .workspace_bytes = workspace_bytes,
+                                  .ps = {.shifts = shifts, .index = index, .grad_shifts = want_grad ? grad_shifts : nullptr}});
 }
 
 extern "C" int adm_multislice_fwd_adj_pp(adm_plan* plan, const float* obj_rot, const float* probes, const int32_t* pos, int batch,
                                          const float* target, int want_grad, float* grad_probes, float* pred, float* loss_sum,
                                          float grad_scale, void* workspace, size_t workspace_bytes) {
-    return multislice_impl(plan, obj_rot, probes, pos, batch, target, want_grad, grad_probes, pred, loss_sum, grad_scale, workspace,
-                           workspace_bytes, true);
+    return multislice_call(plan, {.obj_rot = obj_rot, .probe = probes, .pos = pos, .batch = batch, .target = target, .want_grad = want_grad,
+                                  .grad_probe = grad_probes, .pred = pred, .loss_sum = loss_sum, .grad_scale = grad_scale,
+                                  .workspace = workspace, .workspace_bytes = workspace_bytes, .per_position = true});
 }
 
 extern "C" int adm_probe_shift(adm_plan* plan, const float* probe, const float* shifts, const int32_t* index, int batch,

@@ -105,14 +105,6 @@ WsLayout ws_layout(const adm_plan* plan, int batch);
 hipError_t probe_grad_reduce(const float2* part, int batch, size_t n, float2* out, hipStream_t st);
 hipError_t probe_grad_reduce_large(float2* part, int batch, size_t n, float2* out, hipStream_t st);   // two levels, `part` is scratch
 hipError_t ms_launch(int n, const MsParams& p, int batch, hipStream_t st);
-struct StExitShiftLaunch;
-struct StFanoutLaunch;
-struct StProbeShiftLaunch;
-// adm_multislice_fwd_adj's body (per_position: one probe set per position)
-int multislice_impl(adm_plan* plan, const float* obj_rot, const float* probe, const int32_t* pos, int batch, const float* target,
-                    int want_grad, float* grad_probe, float* pred, float* loss_sum, float grad_scale, void* workspace,
-                    size_t workspace_bytes, bool per_position, float* grad_slice_pos = nullptr,
-                    const StExitShiftLaunch* shift = nullptr, const StProbeShiftLaunch* pshift = nullptr, float* grad_dists = nullptr);
 bool ms_generic_supported(int py, int px);
 int ms_generic_threads(int py, int px);
 hipError_t ms_generic_launch(const MsParams& p, int batch, hipStream_t st);
@@ -204,6 +196,18 @@ hipError_t ms_multidist_fanin_launch(const MsParams& p, int batch, float2* fld, 
 hipError_t ms_streamed_launch(const MsParams& p, int batch, float2* fld, float* part, hipStream_t st, const StSparseLaunch* sp = nullptr,
                               const StExitShiftLaunch* xs = nullptr, const StFanoutLaunch* fo = nullptr,
                               const StProbeShiftLaunch* ps = nullptr);
+// One multislice launch: the arguments every adm_multislice_fwd_adj* entry point takes behind the plan, then what single entry
+// points add, absent unless set (xs / ps: absent = no shifts; their keep / phat / part come from the workspace)
+struct MsCall {
+    const float* obj_rot; const float* probe; const int32_t* pos; int batch; const float* target; int want_grad;
+    float* grad_probe; float* pred; float* loss_sum; float grad_scale; void* workspace; size_t workspace_bytes;
+    bool per_position = false;        // adm_multislice_fwd_adj_pp: one probe set per position
+    float* grad_slice_pos = nullptr;  // adm_multislice_fwd_adj_sparse
+    StExitShiftLaunch xs = {};        // adm_multislice_fwd_adj_exit_shift
+    StProbeShiftLaunch ps = {};       // adm_multislice_fwd_adj_probe_shift
+    float* grad_dists = nullptr;      // adm_multislice_fwd_adj_fanout_dist
+};
+int multislice_call(adm_plan* plan, const MsCall& c);
 hipError_t shift_launch(int n, const ShiftParams& q, int batch, bool adjoint, hipStream_t st);
 inline int stream_grid(size_t n) {      // blocks of 256 threads for a grid-stride pass over n elements
     size_t b = (n + 255) / 256;

@@ -115,6 +115,53 @@ def equal_parts(B, cap):
     return [(i * (B // n) + min(i, B % n), B // n + (1 if i < B % n else 0)) for i in range(n)]
 
 
+def _shift_table(name, table, index, grad, B):
+    """(table, index, grad) of ``multislice(exit_shifts=...)`` or a streamed engine's ``multislice(shifts=...)`` for a batch of B
+    positions, checked: float32 [n_entries, 2] tables, an int32 [B] index or at least B entries."""
+    iname, gname = name[:-1] + '_index', 'grad_' + name
+    for a_, n_ in ((table, name), (grad, gname)):
+        if a_ is not None and (a_.dtype != np.float32 or a_.size % 2):
+            raise ValueError('%s must be float32 [n_entries, 2]' % n_)
+    if grad is not None and grad.size != table.size:
+        raise ValueError('%s must have the shape of %s' % (gname, name))
+    if index is None and table.size < 2 * B:
+        raise ValueError('%s holds %d entries for %d positions and no %s' % (name, table.size // 2, B, iname))
+    if index is not None and (index.dtype != np.int32 or index.size != B):
+        raise ValueError('%s must be int32 [%d]' % (iname, B))
+    return table, index, grad
+
+
+class _Extras(collections.namedtuple('_Extras', 'grad_slice_pos xs ps grad_dists', defaults=(None,) * 4)):
+    """What a launch takes beside the arguments of adm_multislice_fwd_adj: ``xs`` = (exit_shifts, exit_shift_index, grad_exit_shifts),
+    ``ps`` = (shifts, shift_index, grad_shifts) of a streamed engine with ``probe_shift``, each of the whole batch."""
+
+    def call(self, lib, o):
+        """(C function, its arguments behind the common ones) of the launch that starts at position ``o`` of the batch."""
+        if self.xs is not None or self.ps is not None:
+            s, idx, g = self.xs if self.xs is not None else self.ps
+            # without an index, position b of the batch uses entry b: the round starting at o reads (and adds to) the entries from o on
+            so = 0 if idx is not None else 8 * o
+            return (lib.adm_multislice_fwd_adj_exit_shift if self.xs is not None else lib.adm_multislice_fwd_adj_probe_shift,
+                    (s.ptr + so, idx.ptr + 4 * o if idx is not None else None, g.ptr + so if g is not None else None))
+        if self.grad_slice_pos is not None:
+            return lib.adm_multislice_fwd_adj_sparse, (self.grad_slice_pos.ptr,)
+        if self.grad_dists is not None:
+            return lib.adm_multislice_fwd_adj_fanout_dist, (self.grad_dists.ptr,)
+        return lib.adm_multislice_fwd_adj, ()
+
+
+# Engine options that exclude one another (MultisliceEngine.__init__), and the arguments of multislice() that do, each with the
+# exception that says so; the first pair of a list that is on decides the message.
+_SEQUENCE = 'a sequence of detector distances'
+_OPTION_PAIRS = (('detector_fanout', 'exit_shift'), ('detector_fanout', 'probe_shift'), ('detector_fanout', 'slice_pos_cm'),
+                 ('slice_pos_cm', _SEQUENCE), ('exit_shift', 'slice_pos_cm'), ('exit_shift', _SEQUENCE),
+                 ('probe_shift', 'slice_pos_cm'), ('probe_shift', 'exit_shift'), ('probe_shift', _SEQUENCE))
+_CALL_PAIRS = (('detector_fanout', 'shifts', NotImplementedError), ('detector_fanout', 'probes_b', NotImplementedError),
+               ('detector_fanout', 'exit_shifts', NotImplementedError), ('exit_shifts', 'shifts', NotImplementedError),
+               ('exit_shifts', 'probes_b', NotImplementedError), ('exit_shifts', 'slice_pos_cm', NotImplementedError),
+               ('probes_b', 'shifts', ValueError), ('probes_b', 'grad_probe', ValueError))
+
+
 class MultisliceEngine(object):
     """
     Device-resident state for the accelerated path of one reconstruction:
@@ -201,10 +248,12 @@ class MultisliceEngine(object):
         if streamed not in (False, True, 'auto'):
             raise ValueError("streamed must be False, True or 'auto', got %r" % (streamed,))
         self.detector_fanout = bool(detector_fanout)
+        on = {'detector_fanout': detector_fanout, 'exit_shift': exit_shift, 'probe_shift': probe_shift, 'slice_pos_cm': slice_pos_cm is not None,
+              _SEQUENCE: self.n_dists > 1 and not detector_fanout}
+        for a_, b_ in _OPTION_PAIRS:
+            if on[a_] and on[b_]:
+                raise NotImplementedError('%s together with %s is not implemented' % (a_, b_))
         if self.detector_fanout:
-            for flag, name in ((exit_shift, 'exit_shift'), (probe_shift, 'probe_shift'), (slice_pos_cm is not None, 'slice_pos_cm')):
-                if flag:
-                    raise NotImplementedError('detector_fanout together with %s is not implemented' % name)
             if not dists or len(dists) < 2:
                 raise ValueError('detector_fanout needs a sequence of at least two detector distances in free_prop_cm, got %r'
                                  % (free_prop_cm,))
@@ -221,23 +270,10 @@ class MultisliceEngine(object):
                 raise ValueError('slice_pos_cm: %d slice positions for an object of %d slices' % (len(slice_pos_cm), self.obj_size[2]))
             if binning != 1:
                 raise ValueError('slice_pos_cm: sparse multislice needs binning = 1, got %r' % (binning,))
-            if dists and len(dists) > 1:
-                raise NotImplementedError('slice_pos_cm: sparse multislice with a sequence of detector distances is not implemented')
             streamed = True                   # (the one path that applies a transfer function of its own per gap)
         self.exit_shift = bool(exit_shift)
         if self.exit_shift:
-            if slice_pos_cm is not None:
-                raise NotImplementedError('exit_shift together with slice_pos_cm (sparse multislice) is not implemented')
-            if dists and len(dists) > 1:
-                raise NotImplementedError('exit_shift together with a sequence of detector distances is not implemented')
             streamed = True                   # (the one path whose detector convolution is a launch of its own)
-        if probe_shift:
-            if slice_pos_cm is not None:
-                raise NotImplementedError('probe_shift together with slice_pos_cm (sparse multislice) is not implemented')
-            if self.exit_shift:
-                raise NotImplementedError('probe_shift together with exit_shift (per-angle projection alignment) is not implemented')
-            if dists and len(dists) > 1:
-                raise NotImplementedError('probe_shift together with a sequence of detector distances is not implemented')
         plan_kw = dict(binning=binning, n_modes=n_probe_modes, sign_convention=sign_convention, det_mode=det, normalize_fft=normalize_fft,
                        h_free=h_free, loss_type={'lsq': _lib.LOSS_LSQ, 'poisson': _lib.LOSS_POISSON}[loss_function_type],
                        poisson_multiplier=poisson_multiplier, unknown_type=unknown_type)
@@ -501,35 +537,23 @@ class MultisliceEngine(object):
         if grad_scale is None:
             grad_scale = 2.0 / (B * self.det_per_pos * self.n_det)       # d mean((pred-target)^2) / d pred
         lib = self.ctx.lib
-        if self.detector_fanout:
-            for other, name in ((shifts, 'shifts'), (probes_b, 'probes_b'), (exit_shifts, 'exit_shifts')):
-                if other is not None:
-                    raise NotImplementedError('detector_fanout together with %s is not implemented' % name)
+        on = {'detector_fanout': self.detector_fanout, 'slice_pos_cm': self.slice_pos is not None, 'shifts': shifts is not None,
+              'probes_b': probes_b is not None, 'exit_shifts': exit_shifts is not None, 'grad_probe': grad_probe is not None}
+        for a_, b_, refusal in _CALL_PAIRS:
+            if on[a_] and on[b_]:
+                raise refusal('%s together with %s is not implemented' % (a_, b_))
         if grad_dists is not None:
             if self.dists is None:
                 raise ValueError('grad_dists: the engine was built without refine_distances=True')
             if grad_dists.size != self.dists.size or grad_dists.dtype != np.float32:
                 raise ValueError('grad_dists must be float32 [%d]' % self.dists.size)
-        xs = None
+        xs = ps = None
         if exit_shifts is not None:
-            for other, name in ((shifts, 'shifts'), (probes_b, 'probes_b'), (self.slice_pos, 'slice_pos_cm')):
-                if other is not None:
-                    raise NotImplementedError('exit_shifts together with %s is not implemented' % name)
             if not self.exit_shift:
                 raise ValueError('exit_shifts: the engine was built without exit_shift=True')
-            for a_, name in ((exit_shifts, 'exit_shifts'), (grad_exit_shifts, 'grad_exit_shifts')):
-                if a_ is not None and (a_.dtype != np.float32 or a_.size % 2):
-                    raise ValueError('%s must be float32 [n_entries, 2]' % name)
-            if grad_exit_shifts is not None and grad_exit_shifts.size != exit_shifts.size:
-                raise ValueError('grad_exit_shifts must have the shape of exit_shifts')
-            if exit_shift_index is None and exit_shifts.size < 2 * B:
-                raise ValueError('exit_shifts holds %d entries for %d positions and no exit_shift_index' % (exit_shifts.size // 2, B))
-            if exit_shift_index is not None and (exit_shift_index.dtype != np.int32 or exit_shift_index.size != B):
-                raise ValueError('exit_shift_index must be int32 [%d]' % B)
-            xs = (exit_shifts, exit_shift_index, grad_exit_shifts)
+            xs = _shift_table('exit_shifts', exit_shifts, exit_shift_index, grad_exit_shifts, B)
         elif exit_shift_index is not None or grad_exit_shifts is not None:
             raise ValueError('exit_shift_index / grad_exit_shifts need exit_shifts')
-        ps = None
         if self.streamed and (probes_b is not None or (shifts is not None and not self.probe_shift)):
             raise NotImplementedError('streamed multislice (probe %dx%d): sub-pixel probe shifts and per-position probes are not '
                                       'implemented on the streamed path' % (Py, Px))
@@ -539,30 +563,20 @@ class MultisliceEngine(object):
             if grad_slice_pos.size != self.slice_pos.size or grad_slice_pos.dtype != np.float32:
                 raise ValueError('grad_slice_pos must be float32 [%d]' % self.slice_pos.size)
         if self.streamed and shifts is not None:
-            for a_, name in ((shifts, 'shifts'), (grad_shifts, 'grad_shifts')):
-                if a_ is not None and (a_.dtype != np.float32 or a_.size % 2):
-                    raise ValueError('%s must be float32 [n_entries, 2]' % name)
-            if grad_shifts is not None and grad_shifts.size != shifts.size:
-                raise ValueError('grad_shifts must have the shape of shifts')
-            if shift_index is None and shifts.size < 2 * B:
-                raise ValueError('shifts holds %d entries for %d positions and no shift_index' % (shifts.size // 2, B))
-            if shift_index is not None and (shift_index.dtype != np.int32 or shift_index.size != B):
-                raise ValueError('shift_index must be int32 [%d]' % B)
-            ps = (shifts, shift_index, grad_shifts)
+            ps = _shift_table('shifts', shifts, shift_index, grad_shifts, B)
+        extras = _Extras(grad_slice_pos, xs, ps, grad_dists)
         self._acc_done = False
         self._next_loss_buffer()
         if self.streamed and len(self.rounds(B)) > 1:
-            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos, xs, ps, grad_dists)
+            self._multislice_rounds(probe, grad_probe, want_grad, want_pred, grad_scale, extras)
             return
         args = lambda pr_, gp_: self._ms_args(pr_, gp_, want_grad, want_pred, grad_scale, 0, B, self._ws)      # (the whole batch)
         if probes_b is not None:
-            if shifts is not None or grad_probe is not None:
-                raise ValueError('probes_b excludes shifts and grad_probe')
             if tuple(probes_b.shape) != (B, self.n_probe_modes, Py, Px, 2):
                 raise ValueError('probes_b must be [%d, %d, %d, %d, 2], got %r' % (B, self.n_probe_modes, Py, Px, tuple(probes_b.shape)))
             check(lib.adm_multislice_fwd_adj_pp(*args(probes_b, None)))
         elif shifts is None or ps is not None:
-            self._launch(args(probe, grad_probe), grad_slice_pos, xs, ps=ps, grad_dists=grad_dists)
+            self._launch(args(probe, grad_probe), extras)
         else:
             M = self.n_probe_modes
             if self._probes_b is None or self._probes_b.shape[0] < B:
@@ -590,21 +604,10 @@ class MultisliceEngine(object):
                 1 if want_grad else 0, grad_probe.ptr if grad_probe is not None else None,
                 self._pred.ptr + px if want_pred else None, self._loss.ptr + 4 * e, float(grad_scale), ws.ptr, ws.nbytes)
 
-    def _launch(self, args, grad_slice_pos=None, xs=None, o=0, ps=None, grad_dists=None):
-        """``xs``: (exit_shifts, exit_shift_index, grad_exit_shifts) of the whole batch, ``ps``: (shifts, shift_index, grad_shifts) of
-        a streamed engine with ``probe_shift``; the launch starts at position ``o`` of the batch."""
-        if xs is not None or ps is not None:
-            s, idx, g = xs if xs is not None else ps
-            fn = self.ctx.lib.adm_multislice_fwd_adj_exit_shift if xs is not None else self.ctx.lib.adm_multislice_fwd_adj_probe_shift
-            # without an index, position b of the batch uses entry b: the round starting at o reads (and adds to) the entries from o on
-            so = 0 if idx is not None else 8 * o
-            check(fn(*(args + (s.ptr + so, idx.ptr + 4 * o if idx is not None else None, g.ptr + so if g is not None else None))))
-        elif grad_slice_pos is not None:
-            check(self.ctx.lib.adm_multislice_fwd_adj_sparse(*(args + (grad_slice_pos.ptr,))))
-        elif grad_dists is not None:
-            check(self.ctx.lib.adm_multislice_fwd_adj_fanout_dist(*(args + (grad_dists.ptr,))))
-        else:
-            check(self.ctx.lib.adm_multislice_fwd_adj(*args))
+    def _launch(self, args, extras=_Extras(), o=0):
+        """One launch that starts at position ``o`` of the batch, with the ``extras`` of the whole batch."""
+        fn, tail = extras.call(self.ctx.lib, o)
+        check(fn(*(args + tail)))
 
     def _overlap_add(self, ws, o, n, add, window=(0, 0), passes=False):
         """Overlap-add the tile gradients of positions [o, o + n), launched into ``ws``, into grad_rot: ``add`` = 0 writes the rows
@@ -618,17 +621,15 @@ class MultisliceEngine(object):
         for lo in range(0, n, self.MAX_COVER):
             check(lib.adm_tile_grad_accumulate_range(*(head + (lo, min(lo + self.MAX_COVER, n), 1 if add or lo else 0))))
 
-    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, grad_slice_pos=None, xs=None, ps=None,
-                           grad_dists=None):
+    def _multislice_rounds(self, probe, grad_probe, want_grad, want_pred, grad_scale, extras):
         """A streamed engine's batch that does not fit the workspace budget: one launch per round into the same workspace, each
         round's tile gradients overlap-added into grad_rot (zeroed first) before the next round overwrites them.  Losses,
         predictions and the probe gradient are those of one launch; the object gradient too, up to the order of the additions.
-        Every round adds its share to ``grad_slice_pos``, to ``grad_dists`` and to the gradient of the exit-wave shifts ``xs`` or
-        the probe shifts ``ps``."""
+        Every round adds its share to the gradients of ``extras``."""
         if want_grad:
             check(self.ctx.lib.adm_memset(self.ctx.handle, self.grad_rot.ptr, 0, self.grad_rot.nbytes))
         for o, n in self.rounds(self._B):
-            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), grad_slice_pos, xs, o, ps, grad_dists)
+            self._launch(self._ms_args(probe, grad_probe, want_grad, want_pred, grad_scale, o, n, self._ws), extras, o)
             if want_grad:
                 self._overlap_add(self._ws, o, n, 1, passes=self._check_cover(self._pos_host[o:o + n]) > self.MAX_COVER)
         # (every overlap-add above saw at most MAX_COVER tiles per pixel: nothing to check afterwards)

@@ -44,10 +44,19 @@ def test_the_entry_points_are_declared_exported_and_bound():
     assert restype is ctypes.c_int and argtypes == _lib.SIGNATURES['adm_multislice_fwd_adj_sparse'][1]
     assert 'adm_plan_set_fanout_distances' in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     # the same limits and refusals as the host-table setter
-    body = _function_body(_read('adm_api.hip'), r'extern "C" int adm_plan_set_fanout_distances\s*\(')
-    assert 'if (n < 1 || n > 64)' in body
-    for what in ('!plan->streamed', 'ADM_DET_FRESNEL', 'plan->exit_shift', 'plan->probe_shift', 'plan->n_zpos > 0', 'fan_dists_dirty = true'):
-        assert what in body, what
+    api = _read('adm_api.hip')
+    body = _function_body(api, r'extern "C" int adm_plan_set_fanout_distances\s*\(')
+    assert 'if (n < 1 || n > 64)' in body and 'fan_dists_dirty = true' in body
+    # (both ask the one check of the exclusive plan options, as the fan-out, and that check and its table hold the refusals)
+    host_setter = _function_body(api, r'extern "C" int adm_plan_set_detector_fanout\s*\(')
+    for b, who, on in ((body, 'adm_plan_set_fanout_distances', 'true'), (host_setter, 'adm_plan_set_detector_fanout', 'n != 0')):
+        assert 'if (const int rc = plan_option_check(plan, OPT_FANOUT, "%s", %s)) return rc;' % (who, on) in b, who
+    check = _function_body(api, r'static int plan_option_check\s*\(')
+    for what in ('!plan->streamed', 'opt == OPT_FANOUT && plan->d.det_mode != ADM_DET_FRESNEL', '&other != &me && other.on(plan)'):
+        assert what in check, what
+    table = api[api.index('PLAN_OPTIONS[] = {'):api.index('static int plan_option_check')]
+    for what in ('return p->exit_shift;', 'return p->probe_shift;', 'return p->n_zpos > 0;', 'return p->n_fan > 0;'):
+        assert what in table, what
 
 
 def test_every_kernel_is_named_by_a_gpu_test():
@@ -95,10 +104,12 @@ def test_without_a_request_the_streamed_launch_does_not_reach_the_gradient_code(
     assert len(re.findall(r'\bgrad_dists\b', re.sub(r'//.*', '', md + st))) == 4          # (two launch lines, the condition, the argument)
     assert 'ms_distgrad_' not in md + st + api + _read('adm_host.h')
     assert 'float* grad_dists = nullptr;' in _read('adm_host.h')
+    # (two assignments: the launch record's into the launch, and further down the entry point's caller's buffer into the record)
     sets = re.findall(r'^.*\bgrad_dists\s*=[^=].*$', api, re.M)
-    assert len(sets) == 1 and 'fo.grad_dists = grad_dists;' in sets[0], sets
+    assert len(sets) == 2 and 'fo.grad_dists = c.grad_dists;' in sets[0] and '.grad_dists = grad_dists_dev}' in sets[1], sets
+    assert sets[1] in _function_body(api, r'extern "C" int adm_multislice_fwd_adj_fanout_dist\s*\(')
     body = _function_body(api, r'static int streamed_launch\s*\(')
-    assert re.search(r'if \(grad_dists && p\.want_grad\) \{\s*fo\.grad_dists = grad_dists;', body)
+    assert re.search(r'if \(c\.grad_dists && p\.want_grad\) \{\s*fo\.grad_dists = c\.grad_dists;', body)
     # the table is rebuilt only behind the dirty flag, by the launcher it shares with the sparse plan's gaps
     assert re.search(r'if \(plan->fan_dists_dirty\) \{[^}]*q\.gaps = 0;[^}]*ms_fresnel_table_launch\(q, plan->fan_dists_dev,', body, re.S)
     assert len(re.findall(r'ms_fresnel_table_launch\(q, plan->fan_dists_dev', api)) == 1 and len(re.findall(r'ms_fresnel_table_launch\(', api)) == 2

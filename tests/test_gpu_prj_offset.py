@@ -265,6 +265,28 @@ def test_rounds_within_workspace_budget(A, ctx):
         assert rel(parts['gs'], one['gs']) <= gs_bar(e32[4])
 
 
+def test_round_offsets_into_the_entries_and_into_the_index(A, ctx):
+    """What a round starting at position o is handed: without an index the entries from o on (8 * o bytes into both tables), with
+    one the index from o on (4 * o bytes) and the tables whole.  5 positions at 24 x 20 in 3 rounds against one launch, without
+    an index and with a permutation: loss sums and predictions bit for bit, dL/ds inside the bar of the test above."""
+    base = make_case((24, 20), seed=6)
+    for index in (None, np.array([3, 0, 4, 1, 2], np.int32)):
+        case = dict(base, index=index)
+        one = run_shifted(A, ctx, case, keep_engine=True)
+        eng = one['engine']
+        budget, sums = eng.plan.workspace_bytes(2), eng._loss.view(0, (5,)).get()
+        eng.plan.close()
+        parts = run_shifted(A, ctx, case, workspace_budget=budget, canaries=True, keep_engine=True)
+        assert one['n_rounds'] == 1 and parts['n_rounds'] == 3
+        assert np.array_equal(parts['engine']._loss.view(0, (5,)).get(), sums) and np.all(sums > 0)
+        parts['engine'].plan.close()
+        assert parts['loss'] == one['loss'] and np.array_equal(parts['pred'], one['pred'])
+        e32 = yardstick(case)[1]
+        e = rel(parts['gs'], one['gs'])
+        print('index' if index is not None else 'no index', 'rounds vs one launch: dL/ds %.2e (bar %.2e)' % (e, gs_bar(e32[4])))
+        assert np.linalg.norm(one['gs']) > 0 and e <= gs_bar(e32[4])
+
+
 def test_workspace_grows_by_the_kept_spectrum_and_stays_linear(A, ctx):
     from adorym_amd._lib import check
     for probe, M in (((256, 256), 1), ((1025, 132), 3), ((40, 24), 2)):

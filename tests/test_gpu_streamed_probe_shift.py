@@ -95,7 +95,7 @@ def run_ps(A, ctx, case, want_grad=True, want_gs=True, want_gp=True, use_index=T
     out['pred'] = eng.pred()
     out['loss'] = eng.loss()
     out['n_rounds'] = len(eng.rounds(B))
-    out['ws_bytes_4'] = eng.plan.workspace_bytes(4)
+    out['ws_bytes_4'], out['ws_bytes_2'] = eng.plan.workspace_bytes(4), eng.plan.workspace_bytes(2)
     if canaries:
         assert np.array_equal(all_s.get(), host_s)
         assert np.all(g_all[:pad] == -7.25) and np.all(g_all[pad + n:] == -7.25)
@@ -289,6 +289,25 @@ def test_rounds_within_workspace_budget(A, ctx, use_index):
     print('rounds vs one launch: dL/ds %.2e, gprobe %.2e' % (e, MM.rel(parts['gprobe'], one['gprobe'])))
     assert e <= shift_bar(parts)
     assert MM.rel(parts['gprobe'], one['gprobe']) < 1e-6
+
+
+def test_round_offsets_into_the_entries_and_into_the_index(A, ctx):
+    """What a round starting at position o is handed: without an index the entries from o on (8 * o bytes into both tables), with
+    one the index from o on (4 * o bytes) and the tables whole.  5 positions of 24 x 24 in 3 rounds against one launch, with one
+    entry per position and no index, then with the same entries behind a permutation: loss and predictions bit for bit, dL/ds
+    inside the bar of the test above."""
+    case = case_of((24, 24), S=2, B=5, pp='shifts')
+    perm = np.array([3, 0, 4, 1, 2], np.int32)
+    entries = np.empty((5, 2))
+    entries[perm] = np.asarray(case['shifts'])[case['idx']]           # position b keeps its shift, now at entry perm[b]
+    for what, c, use_index in (('no index', case, False), ('index', dict(case, shifts=entries, idx=perm), True)):
+        one = run_ps(A, ctx, c, use_index=use_index)
+        parts = run_ps(A, ctx, c, use_index=use_index, workspace_budget=one['ws_bytes_2'], canaries=True)
+        assert one['n_rounds'] == 1 and parts['n_rounds'] == 3
+        assert parts['loss'] == one['loss'] and np.array_equal(parts['pred'], one['pred'])
+        e = MM.rel(parts['gshift'], one['gshift'])
+        print(what, 'rounds vs one launch: dL/ds %.2e (bar %.2e)' % (e, shift_bar(parts)))
+        assert np.linalg.norm(one['gshift']) > 0 and e <= shift_bar(parts)
 
 
 # ---------------------------------------------------------------------------------------------------- 5. workspace
